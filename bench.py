@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """Headline benchmark: train rays/sec of the MC-NeRF hot path on MI355X (BASELINE.json metric).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--rays R] [--precision P] [--also P,P,...] [--mode train|render]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--rays R] [--precision P] [--mode train|render] [--dump-outputs DIR]
+    python bench.py --full [--also P,P,...] [--occupancy F,F,...] [--no-extra] [--no-cpu-baseline] [--full-json PATH] ...
 
 Workload = BASELINE.json configs[1]: Ball_Lego-shaped rig (110 cameras, 800x800), coarse 4x128 (64 samples)
 + fine 8x256 (128-sample grid), joint intrinsic/extrinsic optimisation stage (GLOBAL_OPTIM_EPOCH), synthetic
@@ -16,9 +17,11 @@ processes with RANK / LOCAL_RANK / WORLD_SIZE / MASTER_* set and waits for them;
 Rank 0 prints ONE JSON line (see DESIGN.md "Measurement"): the headline precision mode (`--precision`; default `f16x3h`: the
 split-f16 forward and dX chains of `f16x3` -- 22-bit operands, fp32-grade colours: the reference's arithmetic is fp32 -- with the
 weight gradients taken from the hi planes of the saved operands; `f16x3`, all operands 22-bit, is in `by_precision` beside it;
-DESIGN.md 2 has the parity evidence of both) timed for `--steps` steps with nothing but the
-step itself inside the timed region, the per-kernel HIP-event times from a separate untimed pass right after it, plus
-`by_precision` with the other modes of `--also` timed in the same run (>= 20 steps each).
+DESIGN.md 2 has the parity evidence of both) timed for `--steps` steps with nothing but the step itself inside the timed region.
+A plain run does nothing else: set-up, `--warmup` steps, the timed steps, the outputs of the last timed step to `--dump-outputs DIR`
+(one .npy per array), the line.  `--full` adds the rest of the record: the per-kernel HIP-event times from a separate untimed pass
+right after the timed steps and the roofline built on them, `by_precision` with the other modes of `--also` timed in the same run
+(>= 20 steps each), `by_occupancy`, `extra_lines`, the parity probe and the CPU baseline, and writes the whole record to `--full-json`.
 """
 import argparse
 import json
@@ -281,9 +284,9 @@ def parity_probe(precisions, dev):
 
 def compact_line(full, full_name="bench_full.json"):
     """The ONE stdout line: bench.py's contract fields + roofline + cpu_baseline, and every secondary measurement of the full record
-    as a scalar (the fp32-grade `f16x3` mode beside the headline, the pinned-occupancy lines, N = 65536 / 7000, render)."""
+    as a scalar (the fp32-grade `f16x3` mode beside the headline, the pinned-occupancy lines, N = 65536 / 7000, render).  A plain
+    run's record has no roofline and no file (`full_name` None): its line is the contract's fields, the config and the validity flags."""
     sig = lambda v, n=5: (None if v is None else float(f"{v:.{n}g}"))
-    r = full["roofline"]
     line = {k: full[k] for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling",
                                  "vs_baseline") if k in full}
     line["value"], line["ms_per_step"] = sig(full["value"], 7), sig(full["ms_per_step"], 6)
@@ -292,10 +295,12 @@ def compact_line(full, full_name="bench_full.json"):
     c = full["config"]
     line["config"] = {"workload": c["workload"], "precision": c["precision"], "rays_per_step_per_gpu": c["rays_per_step_per_gpu"],
                       "fine_samples_per_ray": sig(c["fine_samples_per_ray"]), "parallelism": c["parallelism"].split(" (")[0]}
-    line["roofline"] = {"bound": r["bound"], "kernel": r["kernel"], "ms": sig(r["ms"]), "achieved": sig(r["achieved"]), "peak": r["peak"],
-                        "unit": r["unit"], "frac": sig(r["frac"]), "traffic": sig(r["traffic"]),
-                        "step_mfma_frac": sig(r["step_mfma_frac"]), "step_traffic_bytes": sig(r.get("step_traffic_bytes")),
-                        "algorithmic_bytes_per_step": r.get("algorithmic_bytes_per_step")}
+    if "roofline" in full:
+        r = full["roofline"]
+        line["roofline"] = {"bound": r["bound"], "kernel": r["kernel"], "ms": sig(r["ms"]), "achieved": sig(r["achieved"]), "peak": r["peak"],
+                            "unit": r["unit"], "frac": sig(r["frac"]), "traffic": sig(r["traffic"]),
+                            "step_mfma_frac": sig(r["step_mfma_frac"]), "step_traffic_bytes": sig(r.get("step_traffic_bytes")),
+                            "algorithmic_bytes_per_step": r.get("algorithmic_bytes_per_step")}
     if "cpu_baseline" in full:
         cb = full["cpu_baseline"]
         line["cpu_baseline"] = {"value": sig(cb["value"]), "unit": cb["unit"], "cores": cb["cores"], "kind": cb["kind"],
@@ -329,7 +334,8 @@ def compact_line(full, full_name="bench_full.json"):
             v = full[k]["all"] if isinstance(full[k], dict) and "all" in full[k] else full[k]      # (rank_ms_per_step: every rank's own time)
             line[k] = [sig(x, 4) for x in v] if isinstance(v, (list, tuple)) else (sig(v, 4) if isinstance(v, float) else v)
     line["dist"] = full.get("dist")
-    line["full_record"] = full_name
+    if full_name:
+        line["full_record"] = full_name
     return fit_line(line)
 
 
@@ -394,10 +400,52 @@ def calibrate_occupancy(model, step_nograd, target, n_grid):
     return shift, frac(shift)
 
 
+DUMP_BUDGET_BYTES = 64 << 20          # --dump-outputs: all arrays of a run together
+DUMP_MAX_ROWS = 1 << 20               # per-ray arrays longer than this are reduced to a fixed, seeded sample of their rows
+
+
+def write_outputs(path, arrays):
+    """{name: tensor} -> path/<name>.npy, float32 (float64 stays float64).  An array of more than DUMP_MAX_ROWS rows keeps the same
+    seeded sample of its rows in every run; the whole set must fit DUMP_BUDGET_BYTES."""
+    import numpy as np
+    out = {}
+    for name, t in arrays.items():
+        a = t.detach().cpu().numpy()
+        a = a.astype(np.float64 if a.dtype == np.float64 else np.float32)
+        if a.ndim and a.shape[0] > DUMP_MAX_ROWS:
+            a = a[np.sort(np.random.default_rng(0).choice(a.shape[0], DUMP_MAX_ROWS, replace=False))]
+        out[name] = a
+    total = sum(a.nbytes for a in out.values())
+    if total > DUMP_BUDGET_BYTES:
+        raise SystemExit(f"bench.py: --dump-outputs would write {total / 2**20:.1f} MB (budget {DUMP_BUDGET_BYTES >> 20} MB)")
+    os.makedirs(path, exist_ok=True)
+    for name, a in out.items():
+        np.save(os.path.join(path, name + ".npy"), a)
+
+
+def dump_train_outputs(path, model, last):
+    """What a caller of the train step receives from its last timed step: the loss, both renders of the batch, the reprojected
+    calibration pixels, and after the optimiser step every parameter with the gradient it was updated with."""
+    arrays = {"loss": last["loss"]}
+    rgb_c, rgb_f, _ = last["loss_dict"]["rgb"]
+    arrays["rgb_c"] = rgb_c
+    if rgb_f is not None:
+        arrays["rgb_f"] = rgb_f
+    for key in ("intr", "extr"):
+        if key in last["loss_dict"]:
+            arrays[f"reproj_{key}"] = last["loss_dict"][key][0]
+    for name, p in model.named_parameters():
+        arrays[f"param.{name}"] = p
+        if p.grad is not None:
+            arrays[f"grad.{name}"] = p.grad
+    write_outputs(path, arrays)
+
+
 def run_precision(precision, args, steps, warmup, rank, world, dev, timer, images_cache, *, rays=None, samples=None, scale=None,
-                  coarse=None, occupancy=None):
+                  coarse=None, occupancy=None, dump=None):
     """Builds the model in `precision` (cfg-2 shape unless overridden), runs warmup + `steps` timed steps; returns the per-mode
-    record.  `occupancy` = target selected fraction of the fine grid (None: random-init weights as they are)."""
+    record.  `occupancy` = target selected fraction of the fine grid (None: random-init weights as they are).  `timer` None: no
+    per-kernel pass after the timed steps.  `dump`: directory that receives the outputs of the last timed step (dump_train_outputs)."""
     import torch
     import torch.distributed as dist
     from mc_nerf_amd import distributed as D
@@ -427,6 +475,7 @@ def run_precision(precision, args, steps, warmup, rank, world, dev, timer, image
     wpts, pts, images = images_cache["wpts"], images_cache["pts"], images_cache["images"]
     cams = D.shard_cameras(C, 0, rank, world, seed=42)
     counts, ar_events = [], []
+    last = {}
     occ = None
     if occupancy is not None and args.sigma_bias_shift is not None:      # (a shift calibrated by an earlier run: no calibration renders in a profiled run)
         with torch.no_grad():
@@ -449,6 +498,8 @@ def run_precision(precision, args, steps, warmup, rank, world, dev, timer, image
         data = (images, torch.tensor([cam]), wpts, pts, wpts, pts)
         loss_dict, _, _, _ = model(data, 20, "GLOBAL_OPTIM_EPOCH", 0.6)
         loss = loss_fn(loss_dict, "GLOBAL_OPTIM_EPOCH")
+        if dump is not None and i == warmup + steps - 1:       # (references only: read back after the timed region)
+            last.update(loss=loss, loss_dict=loss_dict)
         opt.zero_grad(set_to_none=True)
         sync.prepare()
         loss.backward()
@@ -480,14 +531,17 @@ def run_precision(precision, args, steps, warmup, rank, world, dev, timer, image
     dt_local = time.perf_counter() - t0             # this rank's own completion (before it waits for the others): a straggler shows here
     barrier()
     dt = time.perf_counter() - t0
-    # per-kernel launch durations (HIP events on the launch stream around the three fine / coarse MLP calls): a separate,
-    # untimed pass over the same workload
-    timer.reset()
-    timer.enabled = True
-    for i in range(min(5, steps)):
-        step(warmup + steps + i, False)
-    barrier()
-    timer.enabled = False
+    if dump is not None:
+        dump_train_outputs(dump, model, last)
+    if timer is not None:
+        # per-kernel launch durations (HIP events on the launch stream around the three fine / coarse MLP calls): a separate,
+        # untimed pass over the same workload
+        timer.reset()
+        timer.enabled = True
+        for i in range(min(5, steps)):
+            step(warmup + steps + i, False)
+        barrier()
+        timer.enabled = False
     tmax = torch.tensor([dt], device=dev)
     if world > 1:
         dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
@@ -503,7 +557,7 @@ def run_precision(precision, args, steps, warmup, rank, world, dev, timer, image
     finite = bool(all(torch.isfinite(p).all() for p in model.parameters()))
     skipped = int(opt.skipped_steps())              # optimiser steps the overflow guard refused (inf / NaN gradients): must be 0
     k_mean = float(torch.stack(counts).float().mean())
-    ks = timer.summary()
+    ks = timer.summary() if timer is not None else {}
     rec = {"precision": precision, "value": rays * world * steps / dt, "unit": "rays/s", "steps": steps,
            "ms_per_step": dt / steps * 1e3, "rays_per_step_per_gpu": rays, "fine_samples_per_ray": k_mean / rays,
            "selected_fraction": k_mean / (rays * samples * scale), "finite": finite,
@@ -629,6 +683,34 @@ def pmc_step_traffic(precision):
     return (tot or None), path
 
 
+def roofline_record(args, head, k_mean, default_shape):
+    """`roofline` of the headline mode from its per-kernel pass (--full).
+    SURVEY 8(d): the path is MFMA-bound by construction (> 10^6 FLOP per algorithmic byte), so `roofline` prices the dominant
+    kernel -- the longest single launch -- by its ALGORITHMIC FLOPs (2 x weight MACs per evaluated sample; the three MFMAs per
+    product of the split-f16 mode and any recomputation are not counted) over its HIP-event duration against the dense f16
+    MFMA peak (fp32 MFMA peak in the exact-fp32 mode).  What the kernel's own design moves through HBM (its contract bytes:
+    the saved operands of the weight-gradient GEMMs) is in `other_roof`, with the PMC-measured bytes as `traffic`; the bytes a
+    step would move if activations never left the CU are `algorithmic_bytes_per_step`."""
+    pc = head["per_call"]
+    single = pc if args.precision != "f32" else {k: v for k, v in pc.items() if k != "mlp_dw<256>"}    # (f32: mlp_dw is 15 launches)
+    dom = max(single, key=lambda k: single[k]["ms"])
+    mfma_peak = PEAK_F32_MFMA_TFLOPS if args.precision == "f32" else PEAK_F16_MFMA_TFLOPS
+    traffic, tsrc = pmc_traffic(args.precision, dom) if default_shape else (None, None)
+    step_traffic, _ = pmc_step_traffic(args.precision) if default_shape else (None, None)
+    hbm_roof = {"bound": "hbm", "achieved": pc[dom]["hbm_GBs"], "peak": PEAK_HBM_GBS, "unit": "GB/s", "frac": pc[dom]["hbm_frac"],
+                "what": "the kernel's CONTRACT bytes (saved GEMM operands it is designed to move; not algorithmic) / duration",
+                "contract_bytes_per_launch": pc[dom]["contract_bytes_per_launch"],
+                "pmc_over_contract": (traffic / pc[dom]["contract_bytes_per_launch"]) if traffic else None}
+    return {"bound": "mfma", "kernel": dom, "ms": pc[dom]["ms"], "achieved": pc[dom]["mfma_TFLOPs"], "peak": mfma_peak,
+            "unit": "TFLOP/s", "frac": pc[dom]["mfma_frac"], "traffic": traffic, "traffic_unit": "HBM bytes per launch (PMC)",
+            "traffic_source": tsrc, "other_roof": hbm_roof,
+            "algorithmic_bytes_per_step": head["algorithmic_bytes_per_step"],
+            "step_traffic_bytes": step_traffic,
+            "traffic_over_algorithmic": (step_traffic / head["algorithmic_bytes_per_step"]) if step_traffic else None,
+            "per_call": pc, "step_algorithmic_tflop": head["step_algorithmic_tflop"], "step_mfma_frac": head["step_mfma_frac"],
+            "design_floor": design_floor(args.precision, head, k_mean, args.rays, args.samples, parse_net(args.coarse)) if default_shape else None}
+
+
 def run_rank(args):
     import torch
     import torch.distributed as dist
@@ -644,8 +726,13 @@ def run_rank(args):
             raise SystemExit(f"bench.py: rank {rank} is on cuda:{torch.cuda.current_device()}, LOCAL_RANK is {local}")
         if dist.get_backend() != "nccl":
             raise SystemExit(f"bench.py: backend {dist.get_backend()!r} with one GPU per rank: the multi-GPU line is measured over RCCL (backend nccl)")
-    if args.also is None:          # defaults: every mode beside the headline at N = 1; at N > 1 the headline + the all-22-bit mode only,
-        args.also = "f16x3,f16,bf16,f32" if world == 1 else "f16x3"        # so that the line arrives well inside a driver's per-run timeout
+    if not args.full:              # a plain run measures the headline and nothing else
+        asked = [o for o, v in (("--also", args.also), ("--occupancy", args.occupancy), ("--extra", args.extra)) if v]
+        if asked:
+            raise SystemExit(f"bench.py: {', '.join(asked)} belong to the full record: add --full")
+        args.also, args.occupancy, args.extra = "", "", False
+    if args.also is None:          # --full defaults: every mode beside the headline at N = 1; at N > 1 the headline + the all-22-bit
+        args.also = "f16x3,f16,bf16,f32" if world == 1 else "f16x3"        # mode only, so that the line arrives well inside a driver's per-run timeout
     if args.occupancy is None:
         args.occupancy = "0.25,0.05" if world == 1 else ""
     if args.extra is None:
@@ -662,17 +749,20 @@ def run_rank(args):
         return
     if not torch.cuda.is_available():
         raise SystemExit("bench.py needs an MI355X (no CPU fallback)")
-    timer = KernelTimer()
-    timer.install()
+    timer = None
+    if args.full:
+        timer = KernelTimer()
+        timer.install()
+    dump = args.dump_outputs if rank == 0 else None
     cache = {}
     if args.mode == "render":
-        out = run_render(args, rank, world, dev)
+        out = run_render(args, rank, world, dev, dump=dump)
         if rank == 0:
             print(json.dumps(out))
         if world > 1:
             dist.destroy_process_group()
         return
-    head, k_mean = run_precision(args.precision, args, args.steps, args.warmup, rank, world, dev, timer, cache, occupancy=args.rho)
+    head, k_mean = run_precision(args.precision, args, args.steps, args.warmup, rank, world, dev, timer, cache, occupancy=args.rho, dump=dump)
     others = {}
     for p in [q for q in args.also.split(",") if q and q != args.precision]:
         others[p], _ = run_precision(p, args, max(20, args.steps // 5), 3, rank, world, dev, timer, cache)
@@ -700,30 +790,6 @@ def run_rank(args):
             extra["render"] = {"value": r["value"], "unit": r["unit"], "ms_per_image": r["ms_per_step"], "images": r["steps"],
                                "what": r["metric"] + ", " + r["config"]["workload"]}
     if rank == 0:
-        pc = head["per_call"]
-        # the path is MFMA-bound by construction (> 10^6 FLOP per algorithmic byte), so `roofline` prices the dominant
-        # kernel -- the longest single launch -- by its ALGORITHMIC FLOPs (2 x weight MACs per evaluated sample; the three MFMAs per
-        # product of the split-f16 mode and any recomputation are not counted) over its HIP-event duration against the dense f16
-        # MFMA peak (fp32 MFMA peak in the exact-fp32 mode).  What the kernel's own design moves through HBM (its contract bytes:
-        # the saved operands of the weight-gradient GEMMs) is in `other_roof`, with the PMC-measured bytes as `traffic`; the bytes a
-        # step would move if activations never left the CU are `algorithmic_bytes_per_step`.
-        single = pc if args.precision != "f32" else {k: v for k, v in pc.items() if k != "mlp_dw<256>"}    # (f32: mlp_dw is 15 launches)
-        dom = max(single, key=lambda k: single[k]["ms"])
-        mfma_peak = PEAK_F32_MFMA_TFLOPS if args.precision == "f32" else PEAK_F16_MFMA_TFLOPS
-        traffic, tsrc = pmc_traffic(args.precision, dom) if default_shape else (None, None)
-        step_traffic, _ = pmc_step_traffic(args.precision) if default_shape else (None, None)
-        hbm_roof = {"bound": "hbm", "achieved": pc[dom]["hbm_GBs"], "peak": PEAK_HBM_GBS, "unit": "GB/s", "frac": pc[dom]["hbm_frac"],
-                    "what": "the kernel's CONTRACT bytes (saved GEMM operands it is designed to move; not algorithmic) / duration",
-                    "contract_bytes_per_launch": pc[dom]["contract_bytes_per_launch"],
-                    "pmc_over_contract": (traffic / pc[dom]["contract_bytes_per_launch"]) if traffic else None}
-        roof = {"bound": "mfma", "kernel": dom, "ms": pc[dom]["ms"], "achieved": pc[dom]["mfma_TFLOPs"], "peak": mfma_peak,
-                "unit": "TFLOP/s", "frac": pc[dom]["mfma_frac"], "traffic": traffic, "traffic_unit": "HBM bytes per launch (PMC)",
-                "traffic_source": tsrc, "other_roof": hbm_roof,
-                "algorithmic_bytes_per_step": head["algorithmic_bytes_per_step"],
-                "step_traffic_bytes": step_traffic,
-                "traffic_over_algorithmic": (step_traffic / head["algorithmic_bytes_per_step"]) if step_traffic else None,
-                "per_call": pc, "step_algorithmic_tflop": head["step_algorithmic_tflop"], "step_mfma_frac": head["step_mfma_frac"],
-                "design_floor": design_floor(args.precision, head, k_mean, args.rays, args.samples, parse_net(args.coarse)) if default_shape else None}
         out = {
             "metric": "train rays/sec (coarse+fine, 64+128 samples)", "value": head["value"], "unit": "rays/s",
             "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": head["ms_per_step"],
@@ -733,12 +799,15 @@ def run_rank(args):
                        "fine_samples_per_ray": head["fine_samples_per_ray"], "selected_fraction": head["selected_fraction"],
                        "occupancy": head.get("occupancy"),
                        "parallelism": f"dp{world} (cameras sharded, 1 flat all-reduce/step)"},
-            "roofline": roof,
-            "kernel_ms": head["kernel_ms"],
-            "by_precision": {p: {k: v for k, v in r.items() if k != "precision"} for p, r in others.items()},
-            "by_occupancy": by_occ,
-            "extra_lines": extra,
         }
+        if args.full:
+            out.update({
+                "roofline": roofline_record(args, head, k_mean, default_shape),
+                "kernel_ms": head["kernel_ms"],
+                "by_precision": {p: {k: v for k, v in r.items() if k != "precision"} for p, r in others.items()},
+                "by_occupancy": by_occ,
+                "extra_lines": extra,
+            })
         for k in ("allreduce_ms", "rank_ms_per_step", "rank_allreduce_ms", "params_identical_across_ranks", "asymmetric_grad_steps", "finite", "skipped_optimizer_steps", "valid"):
             if k in head:
                 out[k] = head[k]
@@ -746,19 +815,19 @@ def run_rank(args):
         out["dist"] = {"world_size": world, "backend": (dist.get_backend() if world > 1 else None),
                        "rccl_ranks": (world if (world > 1 and dist.get_backend() == "nccl") else 0),      # (no process group at world 1: none exercised)
                        "one_gpu_per_rank": os.environ.get("MCNERF_SHARE_GPU") != "1"}
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             # (the default mode beside the mode whose every operand is 22-bit, and the exact-fp32 mode: the same probe in each)
             out["parity"] = parity_probe(list(dict.fromkeys([args.precision, "f16x3", "f32"])), dev)
             out["cpu_baseline"] = cpu_baseline()
-        # the whole record goes to a file; stdout gets ONE compact line (< 2 KB) that carries the contract's fields and the secondary
-        # lines as scalars -- the driver keeps the stdout line, and round 4's 8 KB line was cut in its record
-        for path in dict.fromkeys([args.full_json] + ([os.path.join("gpurun_out", "bench_full.json")] if os.path.isdir("gpurun_out") else [])):
+        if args.full:
+            # the whole record goes to a file; stdout gets ONE compact line (< 2 KB) that carries the contract's fields and the secondary
+            # lines as scalars -- the driver keeps the stdout line, and round 4's 8 KB line was cut in its record
             try:
-                with open(path, "w") as fh:
+                with open(args.full_json, "w") as fh:
                     json.dump(out, fh)
             except OSError as e:
-                print(f"bench.py: could not write {path}: {e}", file=sys.stderr)
-        print(json.dumps(compact_line(out, os.path.basename(args.full_json))))
+                print(f"bench.py: could not write {args.full_json}: {e}", file=sys.stderr)
+        print(json.dumps(compact_line(out, os.path.basename(args.full_json) if args.full else None)))
         allrecs = [(args.precision, head)] + list(others.items()) + [(f"occupancy {o}/{p}", r) for o, d in by_occ.items() for p, r in d.items()] \
             + [(k, r) for k, r in extra.items() if "valid" in r]
         bad = [p for p, r in allrecs if not r["valid"]]
@@ -773,9 +842,10 @@ def run_rank(args):
         dist.destroy_process_group()
 
 
-def run_render(args, rank, world, dev):
+def run_render(args, rank, world, dev, dump=None):
     """No-grad demo / validation render (model/mc_nerf.py:106-122): whole 800x800 images of the
-    cfg-2 model in `batch`-ray chunks, uncapped fine selection; rays/s of render_rays_test."""
+    cfg-2 model in `batch`-ray chunks, uncapped fine selection; rays/s of render_rays_test.  `dump`: directory that receives
+    the last timed image (colour, depth, opacity)."""
     import torch
     import torch.distributed as dist
     from mc_nerf_amd import distributed as D
@@ -803,9 +873,11 @@ def run_render(args, rank, world, dev):
         barrier()
         t0 = time.perf_counter()
         for i in range(n_img):
-            model.render_image_device(cams[i % len(cams)])
+            img = model.render_image_device(cams[i % len(cams)])
         barrier()
         dt = time.perf_counter() - t0
+    if dump is not None:
+        write_outputs(dump, dict(zip(("rgb", "depth", "opacity"), img)))
     tmax = torch.tensor([dt], device=dev)
     if world > 1:
         dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
@@ -829,23 +901,27 @@ def main():
     ap.add_argument("--img", type=int, default=800, help="image side (BASELINE cfg 5: 1600)")
     ap.add_argument("--rig", default="ball", choices=["ball", "array", "halfball", "room"], help="camera rig of the synthetic scene")
     ap.add_argument("--coarse", default="4x128x2", help="coarse net depth x width x skip (config/config.yaml:76-78); 8x256x4 = SURVEY 8's second variant")
-    ap.add_argument("--occupancy", default=None, help="selected fractions of the fine grid measured beside the random-init line "
+    ap.add_argument("--full", action="store_true", help="the whole record: per-kernel pass + roofline, by_precision, by_occupancy, "
+                    "extra_lines, parity probe, CPU baseline, --full-json file (a plain run times the headline steps only)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR", help="write the outputs of the last timed step as DIR/<name>.npy "
+                    "(float32; at most 64 MB, per-ray arrays beyond 2^20 rays as a fixed, seeded sample of rows)")
+    ap.add_argument("--occupancy", default=None, help="(--full) selected fractions of the fine grid measured beside the random-init line "
                     "(by_occupancy; sigma-head bias shift, SURVEY 8(d)); empty = none; default 0.25,0.05 at --gpus 1, none at --gpus > 1")
     ap.add_argument("--rho", type=float, default=None, help="pin the selected fraction of the HEADLINE run itself (profiling a low-occupancy step: "
                     "scripts/evidence.sh); the default line leaves the random-init weights as they are")
     ap.add_argument("--sigma-bias-shift", type=float, default=None, help="with --rho: apply this shift (from an earlier run's "
                     "`occupancy.sigma_bias_shift`) instead of calibrating")
-    ap.add_argument("--no-extra", dest="extra", action="store_false", default=None, help="skip extra_lines (8x256 coarse, N = 7000, 128x5, render)")
-    ap.add_argument("--extra", dest="extra", action="store_true", help="extra_lines also at --gpus > 1 (default: only at --gpus 1)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-extra", dest="extra", action="store_false", default=None, help="(--full) skip extra_lines (8x256 coarse, N = 7000, 128x5, render)")
+    ap.add_argument("--extra", dest="extra", action="store_true", help="(--full) extra_lines also at --gpus > 1 (default: only at --gpus 1)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="(--full) skip the parity probe and the CPU baseline")
     ap.add_argument("--precision", default="f16x3h", choices=["f32", "f16x3", "f16x3h", "f16", "bf16"],
                     help="MFMA mode of the MLP kernels: split-f16 f16x3h (the headline: fp32-grade forward and dX chains, weight gradients from "
                          "the hi operand planes), f16x3 (every operand 22-bit) or exact f32 -- the 1e-4 parity modes; single-pass f16 / bf16 -- "
                          "16-bit operand modes with their own stated error")
-    ap.add_argument("--also", default=None, help="other precision modes measured in the same run (by_precision); default f16x3,f16,bf16,f32 "
+    ap.add_argument("--also", default=None, help="(--full) other precision modes measured in the same run (by_precision); default f16x3,f16,bf16,f32 "
                     "at --gpus 1, f16x3 at --gpus > 1")
     ap.add_argument("--mode", default="train", choices=["train", "render"])
-    ap.add_argument("--full-json", default=os.path.join(ROOT, "bench_full.json"), help="where rank 0 writes the whole record (stdout gets the compact line)")
+    ap.add_argument("--full-json", default=os.path.join(ROOT, "bench_full.json"), help="(--full) where rank 0 writes the whole record (stdout gets the compact line)")
     ap.add_argument("--selftest", action="store_true", help="rendezvous / launcher check only (no kernels; works on CPU)")
     args = ap.parse_args()
     if args.gpus > 1 and "RANK" not in os.environ:

@@ -110,10 +110,10 @@ def test_bench_two_ranks_share_one_gpu(gpu_device, tmp_path, world):
     for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK"):
         env.pop(k, None)
     full = os.path.join(str(tmp_path), "bench_full.json")
-    # world 2: the pinned-occupancy lines asked for explicitly (the DDP invariant on them); world 8: the DRIVER's form, nothing but --gpus /
-    # --steps / --warmup decided here -- at N > 1 bench.py then measures the headline mode + f16x3 only (no by_occupancy, no extra_lines)
+    # world 2: the pinned-occupancy lines asked for explicitly (the DDP invariant on them); world 8: the full record's defaults, nothing but
+    # --gpus / --steps / --warmup decided here -- at N > 1 bench.py --full then measures the headline mode + f16x3 only (no by_occupancy, no extra_lines)
     extra = ["--also=", "--occupancy=0.25,0.05"] if world == 2 else []
-    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", str(world), "--rays", "2048", "--steps", "6", "--warmup", "2",
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--full", "--gpus", str(world), "--rays", "2048", "--steps", "6", "--warmup", "2",
                         "--no-cpu-baseline", "--full-json", full] + extra, capture_output=True, text=True, timeout=400, env=env)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
     line = [l for l in r.stdout.splitlines() if l.startswith("{")][-1]
@@ -160,19 +160,52 @@ def test_bench_under_torchrun_with_one_rank_is_the_plain_line(gpu_device, tmp_pa
     assert abs(a - b) < 0.5 * max(a, b), (a, b)           # (a 2048-ray step is ~2.5 ms and host-bound: a loose gate -- the claim is the PATH, checked above)
 
 
+@pytest.mark.timeout(400)
+def test_bench_plain_run_times_its_steps_and_dumps_the_last_one(gpu_device, tmp_path):
+    """A plain `bench.py --gpus 1 --steps K --warmup W` measures the headline and nothing else (no roofline pass, no other mode, no record
+    file), and `--dump-outputs DIR` leaves what the last timed step computed: loss, both renders, every parameter after the RAdam step and
+    its gradient, float32.  Two runs with the same arguments start from the same inputs, so their outputs agree to the weight-gradient
+    atomics' order."""
+    import json
+    import numpy as np
+    outs = []
+    for k in range(2):
+        dump = os.path.join(str(tmp_path), f"out{k}")
+        full = os.path.join(str(tmp_path), f"full{k}.json")
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--rays", "2048", "--steps", "3", "--warmup", "1",
+                            "--dump-outputs", dump, "--full-json", full], capture_output=True, text=True, timeout=180, env=_clean_env())
+        assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-3000:]
+        lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
+        assert len(lines) == 1
+        c = json.loads(lines[0])
+        assert c["steps"] == 3 and c["warmup"] == 1 and c["n_gpus"] == 1 and c["valid"] is True and c["dtype"] == "f16x3h"
+        assert c["unit"] == "rays/s" and c["higher_is_better"] is True and abs(c["value"] - 2048 / (c["ms_per_step"] * 1e-3)) < 1e-3 * c["value"]
+        assert "roofline" not in c and "f16x3_value" not in c and "cpu_baseline" not in c and not os.path.exists(full)
+        files = sorted(os.listdir(dump))
+        arrays = {f[:-4]: np.load(os.path.join(dump, f)) for f in files}
+        assert sum(a.nbytes for a in arrays.values()) <= 64 << 20 and all(a.dtype == np.float32 for a in arrays.values())
+        assert arrays["rgb_c"].shape == (2048, 3) and arrays["rgb_f"].shape == (2048, 3) and np.isfinite(arrays["loss"]).all()
+        assert "param.nerf.nerf_fine.sh.2.weight" in arrays and "grad.nerf.nerf_fine.sh.2.weight" in arrays
+        outs.append(arrays)
+    assert outs[0].keys() == outs[1].keys()
+    for name in outs[0]:                                    # (>= 99.9 % of the elements: a sample at the selection threshold may flip)
+        a, b = outs[0][name], outs[1][name]
+        assert a.shape == b.shape and np.mean(np.abs(a - b) <= 1e-3 * max(1.0, float(np.abs(a).max()))) >= 0.999, name
+
+
 @pytest.mark.timeout(460)
 def test_bench_under_the_drivers_torchrun_command_with_two_ranks(gpu_device, tmp_path):
     """The driver's N > 1 launch, verbatim -- `python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1
-    --master-port P bench.py --gpus 2 --steps K --warmup W` -- with the real kernels: the ranks are torchrun's processes (bench.py starts
-    none), they bind through LOCAL_RANK, and rank 0 alone prints the compact line with the multi-rank fields and (the N > 1 default) the
-    headline mode + `f16x3` only.  (Two ranks share this box's one GPU over gloo, which they declare with MCNERF_SHARE_GPU=1; with one GPU
+    --master-port P bench.py --gpus 2 --steps K --warmup W` -- with the real kernels and `--full`: the ranks are torchrun's processes (bench.py
+    starts none), they bind through LOCAL_RANK, and rank 0 alone prints the compact line with the multi-rank fields and (the N > 1 default
+    of the full record) the headline mode + `f16x3` only.  (Two ranks share this box's one GPU over gloo, which they declare with MCNERF_SHARE_GPU=1; with one GPU
     per rank the same command runs over RCCL and bench.py refuses anything else.)"""
     import json
     env = dict(_clean_env(), MCNERF_SHARE_GPU="1", MCNERF_DIST_BACKEND="gloo")
     full = os.path.join(str(tmp_path), "bench_full.json")
     r = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
                         "--master-port", str(_free_port()), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "6", "--warmup", "2",
-                        "--rays", "2048", "--no-cpu-baseline", "--full-json", full], capture_output=True, text=True, timeout=420, env=env)
+                        "--rays", "2048", "--full", "--no-cpu-baseline", "--full-json", full], capture_output=True, text=True, timeout=420, env=env)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-3000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1 and len(lines[0]) < 2048, (len(lines), [len(l) for l in lines])
