@@ -37,7 +37,7 @@
 extern "C" {
 #endif
 
-#define MCNERF_ABI_VERSION 6      /* 6: dtype 3 (f16x3h) of the register-chain entry points */
+#define MCNERF_ABI_VERSION 7      /* 7: per-ray depth rows (z_stride) and mcnerf_sample_pdf; 6: dtype 3 (f16x3h) of the register-chain entry points */
 
 int mcnerf_abi_version(void);
 const char* mcnerf_last_error(void);
@@ -70,6 +70,10 @@ int mcnerf_raygen_bwd(const float* pose, const float* kinv, const int64_t* pix, 
  * SinCosEmbedding.forward (model/net_block.py:20-35), CorseFine_NeRF.forward (model/net_block.py:67-78)
  * and eval_sh (model/net_utils.py:103-191).
  *   rays_o, rays_d [n_rays,3]; zgrid [S] = linspace(near,far,S); jitter [n_rays] or NULL;
+ *   z_stride: 0 = every ray samples zgrid [S]; S = zgrid is [n_rays,S], one row of depths per ray (the dense fine pass of
+ *        mcnerf_sample_pdf's z_all, with jitter NULL: its rows already hold it).  Sample j of ray r sits at
+ *        zgrid[r * z_stride + j] + jitter[r] -- the only thing that ties these kernels to a shared grid.  The same argument,
+ *        with the same meaning, is taken by mcnerf_mlp_bwd, the _16 entry points and both composites;
  *   barf_w [10] per-frequency mask (ones when BARF is off);
  *   idx  NULL  -> dense: every (ray, sample) of the [n_rays,S] grid is evaluated (coarse pass);
  *        !NULL -> [max_rows] int32 (ray, sample) pairs, *count of them valid (fine pass); workgroups
@@ -81,7 +85,7 @@ int mcnerf_raygen_bwd(const float* pose, const float* kinv, const int64_t* pix, 
  *        uint32 (1-bit ReLU masks) that receive what mcnerf_mlp_bwd / mcnerf_mlp_dw need
  *        (capacity >= number of evaluated samples). */
 int mcnerf_mlp_fwd(int depth, int width, int skip, const float* params, const float* packed,
-                   const float* rays_o, const float* rays_d, const float* zgrid, const float* jitter,
+                   const float* rays_o, const float* rays_d, const float* zgrid, int z_stride, const float* jitter,
                    const float* barf_w, const int32_t* idx, const int32_t* count, int max_rows,
                    int n_rays, int S, float* out,
                    float* act_save, long long capacity, float* enc_save, float* sh_save, uint32_t* mask_save,
@@ -124,7 +128,7 @@ int mcnerf_mlp_apply_bwd(int depth, int width, int skip, const float* params, co
  * direction; either may be NULL).  All weight gradients come from mcnerf_mlp_dw.
  * Replaces autograd through model/net_block.py:22-33, 67-78 and model/mc_nerf.py:602, 635, 690-691. */
 int mcnerf_mlp_bwd(int depth, int width, int skip, const float* params, const float* packed,
-                   const float* rays_o, const float* rays_d, const float* zgrid, const float* jitter,
+                   const float* rays_o, const float* rays_d, const float* zgrid, int z_stride, const float* jitter,
                    const float* barf_w, const int32_t* idx, const int32_t* count, int max_rows,
                    int n_rays, int S, const float* out, const float* d_out,
                    const uint32_t* mask_save, long long capacity, const float* enc_save, const float* sh_save,
@@ -176,14 +180,14 @@ int mcnerf_pack_weights_16(int depth, int width, int skip, const float* params, 
 long long mcnerf_ws_bytes_16(int depth, int width, int dtype, long long capacity, int which);
 /* mcnerf_mlp_fwd in these modes.  act_ws / enc_ws / mask_ws / sh_ws: NULL (all four) for the no-grad path. */
 int mcnerf_mlp_fwd_16(int depth, int width, int skip, int dtype, const float* params, const void* packed_fwd,
-                      const float* rays_o, const float* rays_d, const float* zgrid, const float* jitter,
+                      const float* rays_o, const float* rays_d, const float* zgrid, int z_stride, const float* jitter,
                       const float* barf_w, const int32_t* idx, const int32_t* count, int max_rows,
                       int n_rays, int S, float* out,
                       void* act_ws, long long capacity, void* enc_ws, uint32_t* mask_ws, void* sh_ws, void* stream);
 /* mcnerf_mlp_bwd in these modes: dy_ws / dsh_ws receive 16-bit (f16x3: hi + lo) gradients scaled by the power of two derived from
  * *gmax_bits (f16 range); d_rays_o / d_rays_d are accumulated in fp32. */
 int mcnerf_mlp_bwd_16(int depth, int width, int skip, int dtype, const float* params, const void* packed_bwd,
-                      const float* rays_o, const float* rays_d, const float* zgrid, const float* jitter,
+                      const float* rays_o, const float* rays_d, const float* zgrid, int z_stride, const float* jitter,
                       const float* barf_w, const int32_t* idx, const int32_t* count, int max_rows,
                       int n_rays, int S, const float* out, const float* d_out,
                       const uint32_t* mask_ws, long long capacity, const void* enc_ws, const void* sh_ws,
@@ -198,13 +202,14 @@ int mcnerf_mlp_dw_16(int depth, int width, int skip, int dtype, const int32_t* c
  * (model/mc_nerf.py:729-736); the N(0,1) draws of sigma2weights are explicit inputs.
  *   eps [N,S]: draw of the rgb composite; eps_sel [N,S] or NULL: draw of the selection weights
  *   (model/mc_nerf.py:619 / 662), which are written to w_sel [N,S] and max-reduced into *wmax_bits
- *   (float bits; caller zeroes it);  depth/opacity [N] may be NULL (training). */
-int mcnerf_composite_fwd(const float* sig_rgb, const float* rays_d, const float* zgrid, const float* jitter,
+ *   (float bits; caller zeroes it);  depth/opacity [N] may be NULL (training).
+ *   zgrid [S] (z_stride 0) or [N,S] depth rows (z_stride S), as mcnerf_mlp_fwd: delta_j = z_{j+1} - z_j of the ray's own row. */
+int mcnerf_composite_fwd(const float* sig_rgb, const float* rays_d, const float* zgrid, int z_stride, const float* jitter,
                          const float* eps, const float* eps_sel, int N, int S, int white_back,
                          float* rgb, float* depth, float* opacity, float* w_sel, uint32_t* wmax_bits, void* stream);
 /* Backward of the rgb composite: d_rgb [N,3] -> d_sig_rgb [N,S,4].  gmax_bits (or NULL): max |d_sig_rgb| of the
  * launch as float bits, max-reduced into a caller-zeroed word (the gradient scale of mcnerf_mlp_bwd_16). */
-int mcnerf_composite_bwd(const float* sig_rgb, const float* zgrid, const float* jitter, const float* eps,
+int mcnerf_composite_bwd(const float* sig_rgb, const float* zgrid, int z_stride, const float* jitter, const float* eps,
                          const float* d_rgb, int N, int S, int white_back, float* d_sig_rgb, uint32_t* gmax_bits,
                          void* stream);
 
@@ -216,6 +221,18 @@ int mcnerf_composite_bwd(const float* sig_rgb, const float* zgrid, const float* 
 int mcnerf_select_fine(const float* w_sel, const uint32_t* wmax_bits, float thresh, int N, int Sc, int scale,
                        float sigma_default, int32_t* ray_counts, int32_t* ray_offsets,
                        int32_t* idx, int32_t* count, float* out_f, void* stream);
+/* Inverse-CDF hierarchical sampling, the fine sampler of `fine_sampler = "pdf"` (a sys_param key of this build; the default,
+ * "threshold", is the reference's weight-threshold refinement above, model/mc_nerf.py:613-632, which has no such sampler).
+ * Vanilla NeRF's sample_pdf in a deterministic form, per ray n (csrc/sample_pdf.hip states it in full):
+ *   zc = zgrid + jitter[n] (the coarse pass's depths, bit for bit; jitter NULL = 0), bin edges mid[i] = (zc[i] + zc[i+1]) / 2,
+ *   pdf = (w[n, 1 .. Sc-2] + 1e-5) / sum, cdf = [0, cumsum(pdf)] (sum and running sums accumulated in fp64, each rounded once to
+ *   fp32: independent of the summation order); each u[n,k] in [0,1] is inverted through the right-sided
+ *   search ind = #{cdf <= u} with denom = pdf[ind-1] (the bin's OWN pdf entry, not a difference of CDF entries; < 1e-5 -> 1);
+ *   z_all [N, Sc+I] = sort(zc ++ zs) ascending.  w [N,Sc] are the coarse selection weights (w_sel of mcnerf_composite_fwd),
+ *   u [N,I] in any order.  3 <= Sc, 1 <= I, Sc + I <= 1024.  Not differentiated (z_all is a constant of the fine pass). */
+int mcnerf_sample_pdf(const float* w, const float* zgrid, const float* jitter, const float* u, int N, int Sc, int I,
+                      float* z_all, void* stream);
+
 /* The random cap of model/mc_nerf.py:630-632: idx_out[i] = idx_in[perm[i]], i < keep; *count = keep. */
 int mcnerf_cap_gather(const int32_t* idx_in, const int64_t* perm, int keep, int32_t* idx_out, int32_t* count, void* stream);
 

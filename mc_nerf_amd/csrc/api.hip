@@ -30,6 +30,8 @@ static bool net_ok(int depth, int width, int skip) {
 static bool net16_ok(int depth, int width, int skip) {
     return net_ok(depth, width, skip) && mcn_single_skip(mcn_skip_mask(depth, skip)) != -2 && mcn_topo_deg(skip) <= 2;
 }
+// the depth layout of the sample-evaluating entry points: one grid (0) or one row per ray (S)
+static bool z_ok(int z_stride, int S) { return z_stride == 0 || z_stride == S; }
 #define REQ(cond, name) do { if (!(cond)) return fail(name, "invalid argument: " #cond); } while (0)
 
 extern "C" {
@@ -77,7 +79,7 @@ int mcnerf_raygen_bwd(const float* pose, const float* kinv, const int64_t* pix, 
 }
 
 int mcnerf_mlp_fwd(int depth, int width, int skip, const float* params, const float* packed,
-                   const float* rays_o, const float* rays_d, const float* zgrid, const float* jitter,
+                   const float* rays_o, const float* rays_d, const float* zgrid, int z_stride, const float* jitter,
                    const float* barf_w, const int32_t* idx, const int32_t* count, int max_rows,
                    int n_rays, int S, float* out,
                    float* act_save, long long capacity, float* enc_save, float* sh_save, uint32_t* mask_save, void* stream) {
@@ -86,6 +88,7 @@ int mcnerf_mlp_fwd(int depth, int width, int skip, const float* params, const fl
     REQ((idx == nullptr) == (count == nullptr), "mcnerf_mlp_fwd");
     REQ(!idx || max_rows >= 0, "mcnerf_mlp_fwd");
     REQ((long long)n_rays * S < (1ll << 31), "mcnerf_mlp_fwd");
+    REQ(z_ok(z_stride, S), "mcnerf_mlp_fwd");
     if (act_save) {
         REQ(enc_save && sh_save && mask_save, "mcnerf_mlp_fwd");
         REQ(capacity >= (idx ? (long long)max_rows : (long long)n_rays * S), "mcnerf_mlp_fwd");
@@ -95,6 +98,7 @@ int mcnerf_mlp_fwd(int depth, int width, int skip, const float* params, const fl
     a.params = params; a.packed = packed; a.rays_o = rays_o; a.rays_d = rays_d; a.zgrid = zgrid; a.jitter = jitter;
     a.barf_w = barf_w; a.idx = (const int2*)idx; a.count = count; a.max_rows = max_rows; a.n_rays = n_rays; a.S = S;
     a.out = out; a.act_save = act_save; a.act_stride = MCN_ACT_STRIDE(capacity, width); a.enc_save = enc_save; a.sh_save = sh_save; a.mask_save = mask_save;
+    a.z_stride = z_stride;
     return check("mcnerf_mlp_fwd", mcn_launch_mlp_fwd(a, (hipStream_t)stream));
 }
 
@@ -171,7 +175,7 @@ int mcnerf_mlp_apply_bwd(int depth, int width, int skip, const float* params, co
 
 
 int mcnerf_mlp_bwd(int depth, int width, int skip, const float* params, const float* packed,
-                   const float* rays_o, const float* rays_d, const float* zgrid, const float* jitter,
+                   const float* rays_o, const float* rays_d, const float* zgrid, int z_stride, const float* jitter,
                    const float* barf_w, const int32_t* idx, const int32_t* count, int max_rows,
                    int n_rays, int S, const float* out, const float* d_out,
                    const uint32_t* mask_save, long long capacity, const float* enc_save, const float* sh_save,
@@ -181,13 +185,14 @@ int mcnerf_mlp_bwd(int depth, int width, int skip, const float* params, const fl
     REQ(mask_save && enc_save && sh_save && dy_save && dsh_save, "mcnerf_mlp_bwd");
     REQ((idx == nullptr) == (count == nullptr), "mcnerf_mlp_bwd");
     REQ(capacity >= (idx ? (long long)max_rows : (long long)n_rays * S), "mcnerf_mlp_bwd");
+    REQ(z_ok(z_stride, S) && (long long)n_rays * S < (1ll << 31), "mcnerf_mlp_bwd");
     McnMlpBwdArgs a;
     a.lay = mcn_make_layout(depth, width, skip);
     a.params = params; a.packed = packed; a.rays_o = rays_o; a.rays_d = rays_d; a.zgrid = zgrid; a.jitter = jitter;
     a.barf_w = barf_w; a.idx = (const int2*)idx; a.count = count; a.max_rows = max_rows; a.n_rays = n_rays; a.S = S;
     a.out = out; a.d_out = d_out; a.mask_save = mask_save; a.act_stride = MCN_ACT_STRIDE(capacity, width);
     a.enc_save = enc_save; a.sh_save = sh_save; a.dy_save = dy_save; a.dsh_save = dsh_save;
-    a.d_rays_o = d_rays_o; a.d_rays_d = d_rays_d; a.gmax_bits = nullptr;
+    a.d_rays_o = d_rays_o; a.d_rays_d = d_rays_d; a.gmax_bits = nullptr; a.z_stride = z_stride;
     return check("mcnerf_mlp_bwd", mcn_launch_mlp_bwd(a, (hipStream_t)stream));
 }
 
@@ -236,7 +241,7 @@ long long mcnerf_ws_bytes_16(int depth, int width, int dtype, long long capacity
     return -1;
 }
 int mcnerf_mlp_fwd_16(int depth, int width, int skip, int dtype, const float* params, const void* packed_fwd,
-                      const float* rays_o, const float* rays_d, const float* zgrid, const float* jitter,
+                      const float* rays_o, const float* rays_d, const float* zgrid, int z_stride, const float* jitter,
                       const float* barf_w, const int32_t* idx, const int32_t* count, int max_rows,
                       int n_rays, int S, float* out,
                       void* act_ws, long long capacity, void* enc_ws, uint32_t* mask_ws, void* sh_ws, void* stream) {
@@ -245,6 +250,7 @@ int mcnerf_mlp_fwd_16(int depth, int width, int skip, int dtype, const float* pa
     REQ((idx == nullptr) == (count == nullptr), "mcnerf_mlp_fwd_16");
     REQ(!idx || max_rows >= 0, "mcnerf_mlp_fwd_16");
     REQ((long long)n_rays * S < (1ll << 31), "mcnerf_mlp_fwd_16");
+    REQ(z_ok(z_stride, S), "mcnerf_mlp_fwd_16");
     REQ((act_ws == nullptr) == (enc_ws == nullptr) && (act_ws == nullptr) == (mask_ws == nullptr) && (act_ws == nullptr) == (sh_ws == nullptr), "mcnerf_mlp_fwd_16");
     if (act_ws) REQ(capacity >= (idx ? (long long)max_rows : (long long)n_rays * S), "mcnerf_mlp_fwd_16");
     Mcn16FwdArgs a;
@@ -254,11 +260,11 @@ int mcnerf_mlp_fwd_16(int depth, int width, int skip, int dtype, const float* pa
     a.rays_o = rays_o; a.rays_d = rays_d; a.zgrid = zgrid; a.jitter = jitter; a.barf_w = barf_w;
     a.idx = (const int2*)idx; a.count = count; a.max_rows = max_rows; a.n_rays = n_rays; a.S = S; a.out = out;
     a.act_ws = act_ws; a.slot_bytes = slot_bytes_of(dtype, capacity, width); a.enc_ws = enc_ws;
-    a.mask_ws = mask_ws; a.mask_slot_words = mcn16_mask_slot_bytes(capacity, width) / 4; a.sh_ws = sh_ws;
+    a.mask_ws = mask_ws; a.mask_slot_words = mcn16_mask_slot_bytes(capacity, width) / 4; a.sh_ws = sh_ws; a.z_stride = z_stride;
     return check("mcnerf_mlp_fwd_16", x3_chain(dtype) ? mcnx3_launch_fwd(a, (hipStream_t)stream) : mcn16_launch_fwd(a, (hipStream_t)stream));
 }
 int mcnerf_mlp_bwd_16(int depth, int width, int skip, int dtype, const float* params, const void* packed_bwd,
-                      const float* rays_o, const float* rays_d, const float* zgrid, const float* jitter,
+                      const float* rays_o, const float* rays_d, const float* zgrid, int z_stride, const float* jitter,
                       const float* barf_w, const int32_t* idx, const int32_t* count, int max_rows,
                       int n_rays, int S, const float* out, const float* d_out,
                       const uint32_t* mask_ws, long long capacity, const void* enc_ws, const void* sh_ws,
@@ -268,6 +274,7 @@ int mcnerf_mlp_bwd_16(int depth, int width, int skip, int dtype, const float* pa
     REQ(mask_ws && enc_ws && sh_ws && dy_ws && dsh_ws, "mcnerf_mlp_bwd_16");
     REQ((idx == nullptr) == (count == nullptr), "mcnerf_mlp_bwd_16");
     REQ(capacity >= (idx ? (long long)max_rows : (long long)n_rays * S), "mcnerf_mlp_bwd_16");
+    REQ(z_ok(z_stride, S) && (long long)n_rays * S < (1ll << 31), "mcnerf_mlp_bwd_16");
     Mcn16BwdArgs a;
     a.lay = mcn_make_layout(depth, width, skip);
     a.params = params; a.packed = packed_bwd; a.bf16 = dtype;
@@ -276,7 +283,7 @@ int mcnerf_mlp_bwd_16(int depth, int width, int skip, int dtype, const float* pa
     a.idx = (const int2*)idx; a.count = count; a.max_rows = max_rows; a.n_rays = n_rays; a.S = S;
     a.out = out; a.d_out = d_out; a.mask_ws = mask_ws; a.mask_slot_words = mcn16_mask_slot_bytes(capacity, width) / 4;
     a.enc_ws = enc_ws; a.sh_ws = sh_ws; a.dy_ws = dy_ws; a.slot_bytes = slot_bytes_of(dtype, capacity, width); a.dsh_ws = dsh_ws;
-    a.d_rays_o = d_rays_o; a.d_rays_d = d_rays_d; a.gmax_bits = gmax_bits;
+    a.d_rays_o = d_rays_o; a.d_rays_d = d_rays_d; a.gmax_bits = gmax_bits; a.z_stride = z_stride;
     return check("mcnerf_mlp_bwd_16", x3_chain(dtype) ? mcnx3_launch_bwd(a, (hipStream_t)stream) : mcn16_launch_bwd(a, (hipStream_t)stream));
 }
 int mcnerf_mlp_dw_16(int depth, int width, int skip, int dtype, const int32_t* count, int rows,
@@ -292,20 +299,22 @@ int mcnerf_mlp_dw_16(int depth, int width, int skip, int dtype, const int32_t* c
     return check("mcnerf_mlp_dw_16", dtype == 2 ? mcnx3_launch_dw(a, (hipStream_t)stream) : mcn16_launch_dw(a, (hipStream_t)stream));
 }
 
-int mcnerf_composite_fwd(const float* sig_rgb, const float* rays_d, const float* zgrid, const float* jitter,
+int mcnerf_composite_fwd(const float* sig_rgb, const float* rays_d, const float* zgrid, int z_stride, const float* jitter,
                          const float* eps, const float* eps_sel, int N, int S, int white_back,
                          float* rgb, float* depth, float* opacity, float* w_sel, uint32_t* wmax_bits, void* stream) {
     REQ(sig_rgb && rays_d && zgrid && eps && rgb && N >= 0 && S > 0, "mcnerf_composite_fwd");
     REQ((depth == nullptr) == (opacity == nullptr), "mcnerf_composite_fwd");
     REQ(!eps_sel || w_sel, "mcnerf_composite_fwd");
-    McnCompositeArgs a = {sig_rgb, rays_d, zgrid, jitter, eps, eps_sel, N, S, white_back, rgb, depth, opacity, w_sel, wmax_bits};
+    REQ(z_ok(z_stride, S), "mcnerf_composite_fwd");
+    McnCompositeArgs a = {sig_rgb, rays_d, zgrid, jitter, eps, eps_sel, N, S, white_back, rgb, depth, opacity, w_sel, wmax_bits, z_stride};
     return check("mcnerf_composite_fwd", mcn_launch_composite_fwd(a, (hipStream_t)stream));
 }
-int mcnerf_composite_bwd(const float* sig_rgb, const float* zgrid, const float* jitter, const float* eps,
+int mcnerf_composite_bwd(const float* sig_rgb, const float* zgrid, int z_stride, const float* jitter, const float* eps,
                          const float* d_rgb, int N, int S, int white_back, float* d_sig_rgb, uint32_t* gmax_bits, void* stream) {
     REQ(sig_rgb && zgrid && eps && d_rgb && d_sig_rgb && N >= 0 && S > 0, "mcnerf_composite_bwd");
     REQ((size_t)4 * 5 * S * sizeof(float) <= 160 * 1024, "mcnerf_composite_bwd");
-    McnCompositeBwdArgs a = {sig_rgb, zgrid, jitter, eps, d_rgb, N, S, white_back, d_sig_rgb, gmax_bits};
+    REQ(z_ok(z_stride, S), "mcnerf_composite_bwd");
+    McnCompositeBwdArgs a = {sig_rgb, zgrid, jitter, eps, d_rgb, N, S, white_back, d_sig_rgb, gmax_bits, z_stride};
     return check("mcnerf_composite_bwd", mcn_launch_composite_bwd(a, (hipStream_t)stream));
 }
 
@@ -316,6 +325,13 @@ int mcnerf_select_fine(const float* w_sel, const uint32_t* wmax_bits, float thre
     REQ((long long)N * Sc * scale < (1ll << 31), "mcnerf_select_fine");
     McnSelectArgs a = {w_sel, wmax_bits, thresh, N, Sc, scale, sigma_default, ray_counts, ray_offsets, (int2*)idx, count, out_f};
     return check("mcnerf_select_fine", mcn_launch_select(a, (hipStream_t)stream));
+}
+int mcnerf_sample_pdf(const float* w, const float* zgrid, const float* jitter, const float* u, int N, int Sc, int I,
+                      float* z_all, void* stream) {
+    REQ(w && zgrid && u && z_all && N >= 0 && Sc >= 3 && I >= 1 && Sc + I <= MCN_PDF_MAX_SAMPLES, "mcnerf_sample_pdf");
+    REQ((long long)N * (Sc + I) < (1ll << 31), "mcnerf_sample_pdf");
+    McnSamplePdfArgs a = {w, zgrid, jitter, u, N, Sc, I, z_all};
+    return check("mcnerf_sample_pdf", mcn_launch_sample_pdf(a, (hipStream_t)stream));
 }
 int mcnerf_cap_gather(const int32_t* idx_in, const int64_t* perm, int keep, int32_t* idx_out, int32_t* count, void* stream) {
     REQ(idx_in && perm && idx_out && count && keep >= 0, "mcnerf_cap_gather");

@@ -6,39 +6,13 @@
 // NeRF_Model.sigma2weights (model/mc_nerf.py:729-736), plus the weights used for the fine-sample
 // selection (model/mc_nerf.py:613-621).  The N(0,1) draws are inputs.
 #include "mcnerf_kernels.h"
+#include "mcnerf_wave.h"
 
 #define MCN_COMPOSITE_BLOCKS 2048      // 4 waves each: 32 waves per CU, every ray-wave resident at once
 
 __device__ __forceinline__ float softplus_t(float x) {      // torch.nn.Softplus(beta=1, threshold=20)
     return x > 20.f ? x : log1pf(expf(x));
 }
-// Wavefront scans on the DPP path (row shifts inside each 16-lane row, then row_bcast:15 / row_bcast:31 carry the row totals
-// across: six full-rate vector ops with a DPP operand) instead of six ds_bpermute round trips through the LDS crossbar; lane 63 of
-// an inclusive scan is the reduction (v_readlane).  A lane whose DPP source is out of range keeps `old` = the identity.
-template <int CTRL, int ROW_MASK>
-__device__ __forceinline__ float dpp_f(float ident, float v) {
-    return __int_as_float(__builtin_amdgcn_update_dpp(__float_as_int(ident), __float_as_int(v), CTRL, ROW_MASK, 0xf, false));
-}
-#define MCN_WAVE_SCAN(OP, IDENT)                                                         \
-    v = OP(v, dpp_f<0x111, 0xf>(IDENT, v));   /* row_shr:1 */                             \
-    v = OP(v, dpp_f<0x112, 0xf>(IDENT, v));   /* row_shr:2 */                             \
-    v = OP(v, dpp_f<0x114, 0xf>(IDENT, v));   /* row_shr:4 */                             \
-    v = OP(v, dpp_f<0x118, 0xf>(IDENT, v));   /* row_shr:8 */                             \
-    v = OP(v, dpp_f<0x142, 0xa>(IDENT, v));   /* row_bcast:15 into rows 1, 3 */           \
-    v = OP(v, dpp_f<0x143, 0xc>(IDENT, v));   /* row_bcast:31 into rows 2, 3 */
-__device__ __forceinline__ float op_mul(float a, float b) { return a * b; }
-__device__ __forceinline__ float op_add(float a, float b) { return a + b; }
-__device__ __forceinline__ float wave_incl_prod(float v) { MCN_WAVE_SCAN(op_mul, 1.f) return v; }
-__device__ __forceinline__ float wave_incl_sum(float v) { MCN_WAVE_SCAN(op_add, 0.f) return v; }
-__device__ __forceinline__ float wave_shr1(float v, float ident) { return dpp_f<0x138, 0xf>(ident, v); }      // lane l <- lane l - 1, lane 0 <- ident (wave_shr:1)
-__device__ __forceinline__ float wave_last(float v) { return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), 63)); }
-__device__ __forceinline__ float wave_sum(float v) { return wave_last(wave_incl_sum(v)); }
-__device__ __forceinline__ float wave_max(float v) {
-    v = fmaxf(v, dpp_f<0x111, 0xf>(v, v)); v = fmaxf(v, dpp_f<0x112, 0xf>(v, v)); v = fmaxf(v, dpp_f<0x114, 0xf>(v, v));
-    v = fmaxf(v, dpp_f<0x118, 0xf>(v, v)); v = fmaxf(v, dpp_f<0x142, 0xa>(v, v)); v = fmaxf(v, dpp_f<0x143, 0xc>(v, v));
-    return wave_last(v);
-}
-
 // Running maximum of non-negative floats (as bit patterns) in ONE device word.  Every ray's wave contributes, and tens of
 // thousands of same-address atomics serialise in the L2 (~150 us per launch at 32768 rays): read the word first with an
 // L1-bypassing load and skip the atomic unless this wave would raise it -- after the first few waves almost none does.
@@ -57,6 +31,7 @@ __global__ __launch_bounds__(256) void composite_fwd_kernel(McnCompositeArgs a) 
     // kernel took at 32768 rays)
     for (int n = blockIdx.x * 4 + (threadIdx.x >> 6); n < a.N; n += gridDim.x * 4) {
     const float jit = a.jitter ? a.jitter[n] : 0.f;
+    const float* zrow = a.zgrid + (size_t)n * a.z_stride;
     const float dx = a.rays_d[n * 3], dy = a.rays_d[n * 3 + 1], dz = a.rays_d[n * 3 + 2];
     const float rlen = sqrtf(dx * dx + dy * dy + dz * dz);
     const f32x4* sr = reinterpret_cast<const f32x4*>(a.sig_rgb) + (size_t)n * S;
@@ -69,8 +44,8 @@ __global__ __launch_bounds__(256) void composite_fwd_kernel(McnCompositeArgs a) 
         float z = 0.f, delta = 0.f, e1 = 0.f, e2 = 0.f;
         if (ok) {
             v = sr[j];
-            z = __fadd_rn(a.zgrid[j], jit);
-            delta = (j + 1 < S) ? __fsub_rn(__fadd_rn(a.zgrid[j + 1], jit), z) : 1e10f;
+            z = __fadd_rn(zrow[j], jit);
+            delta = (j + 1 < S) ? __fsub_rn(__fadd_rn(zrow[j + 1], jit), z) : 1e10f;
             e1 = a.eps[(size_t)n * S + j];
             if (a.eps_sel) e2 = a.eps_sel[(size_t)n * S + j];
         }
@@ -138,6 +113,7 @@ __global__ __launch_bounds__(256) void composite_bwd_kernel(McnCompositeBwdArgs 
     float gmx = 0.f;                       // max |gradient| written by this lane (scale of the split-f16 backward)
     for (int n = blockIdx.x * 4 + wv; n < a.N; n += gridDim.x * 4) {      // (several rays per wave: see the forward kernel)
     const float jit = a.jitter ? a.jitter[n] : 0.f;
+    const float* zrow = a.zgrid + (size_t)n * a.z_stride;
     const float g0 = a.d_rgb[n * 3], g1 = a.d_rgb[n * 3 + 1], g2 = a.d_rgb[n * 3 + 2];
     const float wb = a.white_back ? 1.f : 0.f;
     const f32x4* sr = reinterpret_cast<const f32x4*>(a.sig_rgb) + (size_t)n * S;
@@ -150,8 +126,8 @@ __global__ __launch_bounds__(256) void composite_bwd_kernel(McnCompositeBwdArgs 
         float delta = 0.f, e1 = 0.f;
         if (ok) {
             v = sr[j];
-            const float z = __fadd_rn(a.zgrid[j], jit);
-            delta = (j + 1 < S) ? __fsub_rn(__fadd_rn(a.zgrid[j + 1], jit), z) : 1e10f;
+            const float z = __fadd_rn(zrow[j], jit);
+            delta = (j + 1 < S) ? __fsub_rn(__fadd_rn(zrow[j + 1], jit), z) : 1e10f;
             e1 = a.eps[(size_t)n * S + j];
         }
         const float sx = v[0] + e1;

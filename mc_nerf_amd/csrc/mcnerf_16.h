@@ -110,6 +110,7 @@ struct Mcn16FwdArgs {
     void* enc_ws;                             // fragment-major encodings
     unsigned* mask_ws; size_t mask_slot_words;  // [depth+2] slots of lane-local ReLU bit masks
     void* sh_ws;                              // fragment-major sh.2 outputs (the SH coefficients; the backward's view-direction term)
+    int z_stride = 0;                         // zgrid[ray * z_stride + j]: 0 = one grid for every ray, S = per-ray depth rows
 };
 hipError_t mcn16_launch_fwd(const Mcn16FwdArgs& a, hipStream_t st);
 
@@ -129,6 +130,7 @@ struct Mcn16BwdArgs {
     void* dsh_ws;                             // fragment-major d(sh.2 outputs) (columns 0..26) and d sigma_raw (column 27) (x SG)
     float* d_rays_o; float* d_rays_d;
     const unsigned* gmax_bits;
+    int z_stride = 0;                         // as Mcn16FwdArgs::z_stride
 };
 hipError_t mcn16_launch_bwd(const Mcn16BwdArgs& a, hipStream_t st);
 

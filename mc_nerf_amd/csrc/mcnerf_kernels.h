@@ -8,7 +8,7 @@ struct McnMlpFwdArgs {
     const float* packed;      // packed weights (mcn_launch_pack)
     const float* rays_o;      // [n_rays,3]
     const float* rays_d;      // [n_rays,3]
-    const float* zgrid;       // [S]  linspace(near, far, S)
+    const float* zgrid;       // [S]  linspace(near, far, S), or [n_rays][z_stride] per-ray depth rows
     const float* jitter;      // [n_rays] or null
     const float* barf_w;      // [10] per-frequency mask
     const int2* idx;          // [rows] (ray, sample) pairs, or null = dense ray-major
@@ -22,6 +22,7 @@ struct McnMlpFwdArgs {
     float* sh_save;           // [capacity][32]
     unsigned int* mask_save;  // [(depth+2)][capacity][width/32] ReLU masks (bit c of word g = column 32g+c is > 0)
     const float* enc_in = nullptr;   // fp32 kernel only: caller-supplied encodings [rows][63] instead of the fused positional encoding
+    int z_stride = 0;         // sample j of ray r sits at zgrid[r * z_stride + j]: 0 = one grid for every ray, S = per-ray rows
 };
 hipError_t mcn_launch_encode(const float* x, const float* barf_w, int n, int n_freqs, float* out, hipStream_t st);
 hipError_t mcn_launch_encode_bwd(const float* x, const float* barf_w, int n, int n_freqs, const float* d_out, float* d_x, hipStream_t st);
@@ -60,6 +61,7 @@ struct McnMlpBwdArgs {
     const unsigned int* gmax_bits;   // split-f16 mode only: float bits of max|d_out| over the launch (device scalar)
     float* d_enc_out = nullptr;      // stand-alone CorseFine_NeRF backward: the encoded-input gradient [rows][63] is the result
                                      // (no positional-encoding backward; d_rays_d then receives the SH view-direction term alone)
+    int z_stride = 0;         // as McnMlpFwdArgs::z_stride
 };
 hipError_t mcn_launch_mlp_bwd(const McnMlpBwdArgs& a, hipStream_t st);
 
@@ -84,7 +86,7 @@ hipError_t mcn_launch_sync_finish(float* arena, long long n_grad, int n_flags, f
 struct McnCompositeArgs {
     const float* sig_rgb;     // [N,S,4]
     const float* rays_d;      // [N,3]
-    const float* zgrid;       // [S]
+    const float* zgrid;       // [S], or [N][S] rows (z_stride = S)
     const float* jitter;      // [N] or null
     const float* eps;         // [N,S] noise of the rgb composite
     const float* eps_sel;     // [N,S] noise of the selection weights, or null
@@ -95,6 +97,7 @@ struct McnCompositeArgs {
     float* opacity;           // [N] or null
     float* w_sel;             // [N,S] or null
     unsigned int* wmax_bits;  // running max of w_sel as float bits (weights are >= 0), or null
+    int z_stride = 0;         // depth of sample j of ray n: zgrid[n * z_stride + j] (+ jitter[n])
 };
 hipError_t mcn_launch_composite_fwd(const McnCompositeArgs& a, hipStream_t st);
 
@@ -108,8 +111,21 @@ struct McnCompositeBwdArgs {
     int white_back;
     float* d_sig_rgb;         // [N,S,4]
     unsigned int* gmax_bits;  // running max of |d_sig_rgb| as float bits (for the split-f16 backward), or null
+    int z_stride = 0;         // as McnCompositeArgs::z_stride
 };
 hipError_t mcn_launch_composite_bwd(const McnCompositeBwdArgs& a, hipStream_t st);
+
+// inverse-CDF hierarchical sampling (sample_pdf.hip)
+#define MCN_PDF_MAX_SAMPLES 1024   // bound on Sc + n_importance
+struct McnSamplePdfArgs {
+    const float* w;           // [N,Sc] coarse selection weights
+    const float* zgrid;       // [Sc] coarse grid
+    const float* jitter;      // [N] or null
+    const float* u;           // [N,I] uniform draws in [0,1]
+    int N, Sc, I;
+    float* z_all;             // [N,Sc+I] out: sorted coarse + importance depths
+};
+hipError_t mcn_launch_sample_pdf(const McnSamplePdfArgs& a, hipStream_t st);
 
 struct McnSelectArgs {
     const float* w_sel;       // [N,Sc]

@@ -129,7 +129,7 @@ __global__ __launch_bounds__(64 * MCN16_WAVES, 2) void mlp16_bwd_kernel(Mcn16Bwd
     auto gather = [&](int ray, int j) -> In {
         In r;
         r.ray = ray;
-        r.zg = a.zgrid[j];
+        r.zg = a.zgrid[ray * a.z_stride + j];
         r.jit = a.jitter ? a.jitter[ray] : 0.f;
         const size_t addr = (size_t)ray * a.S + j;
         r.o = *reinterpret_cast<const f32x4*>(a.out + addr * 4);

@@ -198,7 +198,7 @@ __global__ __launch_bounds__(64 * MCN16_WAVES, 2) void mlp16_fwd_kernel(Mcn16Fwd
         int ray, j;
         if (a.idx) { const int2 rj = a.idx[gc]; ray = rj.x; j = rj.y; }
         else { ray = (int)(gc / a.S); j = (int)(gc - (long long)ray * a.S); }
-        float zv = a.zgrid[j];
+        float zv = a.zgrid[ray * a.z_stride + j];
         if (a.jitter) zv = __fadd_rn(zv, a.jitter[ray]);
         const float dx = a.rays_d[ray * 3 + 0], dy = a.rays_d[ray * 3 + 1], dz = a.rays_d[ray * 3 + 2];
         float p[3];

@@ -79,7 +79,7 @@ __device__ __forceinline__ void mcn_sh_bwd_general(const McnMlpBwdArgs& a, float
         int j;
         if (a.idx) { const int2 rj = a.idx[g]; ray = rj.x; j = rj.y; }
         else { ray = (int)(g / a.S); j = (int)(g - (long long)ray * a.S); }
-        zv = a.zgrid[j];
+        zv = a.zgrid[ray * a.z_stride + j];
         if (a.jitter) zv = __fadd_rn(zv, a.jitter[ray]);
         const size_t addr = (size_t)ray * a.S + j;
         const f32x4 o = *reinterpret_cast<const f32x4*>(a.out + addr * 4);
@@ -158,7 +158,7 @@ __global__ __launch_bounds__(McnGeom<WIDTH>::WN * McnGeom<WIDTH>::WM * 64, 2) vo
             int j;
             if (a.idx) { const int2 rj = a.idx[g]; ray = rj.x; j = rj.y; }
             else { ray = (int)(g / a.S); j = (int)(g - (long long)ray * a.S); }
-            zv = a.zgrid[j];
+            zv = a.zgrid[ray * a.z_stride + j];
             if (a.jitter) zv = __fadd_rn(zv, a.jitter[ray]);
             const size_t addr = (size_t)ray * a.S + j;
             const f32x4 o = *reinterpret_cast<const f32x4*>(a.out + addr * 4);

@@ -200,7 +200,7 @@ __global__ __launch_bounds__(McnGeom<WIDTH>::WN * McnGeom<WIDTH>::WM * 64, 2) vo
             int ray, j;
             if (a.idx) { const int2 rj = a.idx[g]; ray = rj.x; j = rj.y; }
             else { ray = (int)(g / a.S); j = (int)(g - (long long)ray * a.S); }
-            zv = a.zgrid[j];
+            zv = a.zgrid[ray * a.z_stride + j];
             if (a.jitter) zv = __fadd_rn(zv, a.jitter[ray]);
             dx = a.rays_d[ray * 3 + 0]; dy = a.rays_d[ray * 3 + 1]; dz = a.rays_d[ray * 3 + 2];
             // o + d*z with separate roundings, as the reference's broadcasted mul then add (mc_nerf.py:602)

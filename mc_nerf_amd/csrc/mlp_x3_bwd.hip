@@ -169,7 +169,7 @@ __global__ __launch_bounds__(64 * mcnx3_waves(W), mcnx3_waves(W) / 4) void mlp_x
     auto gather = [&](int ray, int j) -> In {
         In r;
         r.ray = ray;
-        r.zg = a.zgrid[j];
+        r.zg = a.zgrid[ray * a.z_stride + j];
         r.jit = a.jitter ? a.jitter[ray] : 0.f;
         const size_t addr = (size_t)ray * a.S + j;
         r.o = *reinterpret_cast<const f32x4*>(a.out + addr * 4);
@@ -194,7 +194,7 @@ __global__ __launch_bounds__(64 * mcnx3_waves(W), mcnx3_waves(W) / 4) void mlp_x
     const unsigned in_lds = (unsigned)reinterpret_cast<size_t>((mcn16_lds_ptr_t)smem) + SM::oIn + wave * (16 * 256);
     const float* in_rd = reinterpret_cast<const float*>(smem + SM::oIn + wave * (16 * 256)) + lane;
     auto gather_dma = [&](int ray, int j) {
-        mcn16_dma4(a.zgrid + j, in_lds);
+        mcn16_dma4(a.zgrid + ray * a.z_stride + j, in_lds);
         if (a.jitter) mcn16_dma4(a.jitter + ray, in_lds + 256);
         const size_t addr = ((size_t)ray * a.S + j) * 4;
 #pragma unroll

@@ -210,7 +210,7 @@ __global__ __launch_bounds__(64 * mcnx3_waves(W), mcnx3_waves(W) / 4) void mlp_x
         return g_ < total ? g_ : total - 1;
     };
     auto gather_dma = [&](int ray_, int j_) {
-        mcn16_dma4(a.zgrid + j_, in_lds);
+        mcn16_dma4(a.zgrid + ray_ * a.z_stride + j_, in_lds);
         if (a.jitter) mcn16_dma4(a.jitter + ray_, in_lds + 256);
 #pragma unroll
         for (int c = 0; c < 3; ++c) {
@@ -254,7 +254,7 @@ __global__ __launch_bounds__(64 * mcnx3_waves(W), mcnx3_waves(W) / 4) void mlp_x
         } else {
             if (a.idx) { const int2 rj = a.idx[gc]; ray = rj.x; j = rj.y; }
             else { ray = (int)(gc / a.S); j = (int)(gc - (long long)ray * a.S); }
-            zv = a.zgrid[j];
+            zv = a.zgrid[ray * a.z_stride + j];
             if (a.jitter) zv = __fadd_rn(zv, a.jitter[ray]);
             dx = a.rays_d[ray * 3 + 0]; dy = a.rays_d[ray * 3 + 1]; dz = a.rays_d[ray * 3 + 2];
             ox = a.rays_o[ray * 3 + 0]; oy = a.rays_o[ray * 3 + 1]; oz = a.rays_o[ray * 3 + 2];

@@ -70,9 +70,23 @@ class NeRF_Model(nn.Module):
         if self.precision != "f32" and (self.nerf_coarse.net.fp32_only or self.nerf_fine.net.fp32_only):
             raise ValueError("a net with more than one skip layer or SH degree 3 runs in precision 'f32' only "
                              f"(the register-chain kernels of '{self.precision}' take one skip layer and MLP_deg <= 2)")
+        # "fine_sampler" / "n_importance" are this build's own sys_param keys as well: the fine pass's sampler, "threshold" (the
+        # reference's weight-threshold refinement, :613-632; the default) or "pdf" (inverse-CDF hierarchical sampling of
+        # n_importance depths per ray from the coarse weights, the fine net evaluated on the Sc + n_importance sorted depths)
+        self.fine_sampler = sys_param.get("fine_sampler", "threshold")
+        self.n_importance = sys_param.get("n_importance", 128)
+        if self.fine_sampler not in ("threshold", "pdf"):
+            raise ValueError(f"fine_sampler must be 'threshold' or 'pdf', got {self.fine_sampler!r}")
+        if isinstance(self.n_importance, bool) or not isinstance(self.n_importance, int) or self.n_importance < 1:
+            raise ValueError(f"n_importance must be an integer >= 1, got {self.n_importance!r}")
+        if self.fine_sampler == "pdf" and not (self.samples_c >= 3 and self.samples_c + self.n_importance <= ops.PDF_MAX_SAMPLES):
+            raise ValueError(f"fine_sampler 'pdf' needs samples >= 3 and samples + n_importance <= {ops.PDF_MAX_SAMPLES}, "
+                             f"got samples = {self.samples_c}, n_importance = {self.n_importance}")
         self.settings = RenderSettings(self.samples_c, self.sample_scale, float(self.weight_thresh),
-                                       float(self.sigma_default), bool(self.white_back), precision=self.precision)
-        self.last_selection = None
+                                       float(self.sigma_default), bool(self.white_back), precision=self.precision,
+                                       fine_sampler=self.fine_sampler, n_importance=int(self.n_importance))
+        self.last_selection = None        # (idx, count) of the last fine pass in "threshold" mode; None in "pdf" mode
+        self.last_z_all = None            # the fine pass's depth rows [N, samples + n_importance] in "pdf" mode
         self.last_flat_grads = None
         self.grad_arena = None            # set per step by distributed.FlatGradSync.prepare()
         self.grad_arena_used = False
@@ -98,10 +112,11 @@ class NeRF_Model(nn.Module):
         return t.to(device=self.z_vals_c.device, dtype=torch.float32)
 
     def render_rays_train(self, rays_d, rays_o, cur_epoch, step_r, only_coarse=False, *,
-                          jitter=None, eps_c=None, eps_sel=None, eps_f=None, cap_perm=None):
+                          jitter=None, eps_c=None, eps_sel=None, eps_f=None, cap_perm=None, u=None):
         """Reference :598-646.  The keyword-only tensors are the reference's random draws
         (U(0,(far-near)/Sc) per ray; three N(0,1) tensors; the cap permutation); when omitted they are
-        drawn from torch's device generator in the reference's order."""
+        drawn from torch's device generator in the reference's order.  `fine_sampler = "pdf"`: `u` [N, n_importance] are the
+        sampler's U(0,1) draws (drawn after eps_sel), eps_f is [N, samples + n_importance] and cap_perm is not used."""
         N, dev = rays_d.shape[0], rays_d.device
         if N == 0:                                  # empty batch: empty results (the reference's tensor ops do the same)
             e3, e1 = rays_d.new_zeros(0, 3), rays_d.new_zeros(0, 1)
@@ -110,11 +125,14 @@ class NeRF_Model(nn.Module):
             jitter = torch.empty(N, 1, device=dev).uniform_(0.0, (self.far - self.near) / self.samples_c)
         if eps_c is None:
             eps_c = torch.randn(N, self.samples_c, device=dev)
+        pdf = self.settings.pdf and not only_coarse
         if not only_coarse:
             if eps_sel is None:
                 eps_sel = torch.randn(N, self.samples_c, device=dev)
+            if pdf and u is None:
+                u = torch.rand(N, self.n_importance, device=dev)
             if eps_f is None:
-                eps_f = torch.randn(N, self.samples_f, device=dev)
+                eps_f = torch.randn(N, self.settings.samples_pdf if pdf else self.samples_f, device=dev)
         params = self.nerf_coarse.ordered_parameters() + self.nerf_fine.ordered_parameters()
         self.nerf_coarse.flat_params()
         self.nerf_fine.flat_params()
@@ -122,14 +140,16 @@ class NeRF_Model(nn.Module):
                                                     self._dev(jitter), self._dev(eps_c).contiguous(),
                                                     None if eps_sel is None else self._dev(eps_sel).contiguous(),
                                                     None if eps_f is None else self._dev(eps_f).contiguous(),
-                                                    cap_perm, rays_d, rays_o, *params)
+                                                    cap_perm, self._dev(u).contiguous() if pdf else None, rays_d, rays_o, *params)
         if only_coarse:
             return rgb_c, None, depth_c
         return rgb_c, rgb_f
 
     @torch.no_grad()
-    def render_rays_test(self, rays_d, rays_o, model_coarse, model_fine, *, eps_c=None, eps_sel=None, eps_f=None, _prepared=None):
-        """Reference :648-680 (the nets are arguments because valid_train passes freshly loaded ones)."""
+    def render_rays_test(self, rays_d, rays_o, model_coarse, model_fine, *, eps_c=None, eps_sel=None, eps_f=None, _prepared=None, u=None):
+        """Reference :648-680 (the nets are arguments because valid_train passes freshly loaded ones).  `fine_sampler = "pdf"`:
+        `u` [N, n_importance] defaults to linspace(0, 1, n_importance) for every ray (a deterministic render) and eps_f is
+        [N, samples + n_importance]."""
         N, dev = rays_d.shape[0], rays_d.device
         if N == 0:
             return rays_d.new_zeros(0, 3), rays_d.new_zeros(0, 1), rays_d.new_zeros(0, 1)
@@ -137,17 +157,24 @@ class NeRF_Model(nn.Module):
             eps_c = torch.randn(N, self.samples_c, device=dev)
         if eps_sel is None:
             eps_sel = torch.randn(N, self.samples_c, device=dev)
+        pdf = self.settings.pdf
         if eps_f is None:
-            eps_f = torch.randn(N, self.samples_f, device=dev)
+            eps_f = torch.randn(N, self.settings.samples_pdf if pdf else self.samples_f, device=dev)
+        if pdf:
+            u = (torch.linspace(0.0, 1.0, self.n_importance, device=dev).expand(N, -1) if u is None else self._dev(u)).contiguous()
         return render_test(self, model_coarse, model_fine, rays_d.float(), rays_o.float(),
-                           self._dev(eps_c).contiguous(), self._dev(eps_sel).contiguous(), self._dev(eps_f).contiguous(), _prepared)
+                           self._dev(eps_c).contiguous(), self._dev(eps_sel).contiguous(), self._dev(eps_f).contiguous(), _prepared,
+                           u=u if pdf else None)
 
     def reserve_workspaces(self, n_rays: int):
         """Sizes the training workspaces of both nets for `n_rays`-ray steps now (they are re-used from step to step afterwards:
         render.WorkspacePool), so that the first timed / synchronised step of a multi-GPU run allocates nothing."""
         from .render import _cap_needed, _pool
         dev, st, pool = self.z_vals_c.device, self.settings, _pool(self)
-        rows_f = n_rays * (st.max_fine_per_ray if _cap_needed(st) else st.samples_f)
+        if st.pdf:
+            rows_f = n_rays * st.samples_pdf
+        else:
+            rows_f = n_rays * (st.max_fine_per_ray if _cap_needed(st) else st.samples_f)
         for net, rows in ((self.nerf_coarse.net, n_rays * st.samples_c), (self.nerf_fine.net, rows_f)):
             save = pool.take_save(net, rows, dev, st.precision)
             pool.give_grad(net, save, st.precision, pool.take_grad(net, save, st.precision))

@@ -5,9 +5,13 @@
 composite, with a hand-written backward (composite bwd -> dX chain -> dW) instead of autograd
 through ~900 ATen ops.  ``RaygenFn`` does the same for MC_Model.get_rays on selected pixels.
 
+The fine sampler is a setting (`fine_sampler`): "threshold" is the reference's weight-threshold selection above;
+"pdf" draws `n_importance` depths per ray by inverse CDF from the coarse selection weights (ops.sample_pdf) and runs
+the fine net densely on the sorted [coarse + importance] depth rows (no selection, cap or default prefill).
+
 Every random draw of the reference (jitter, the three N(0,1) tensors of sigma2weights, the cap
-permutation) is an explicit tensor argument: generated with torch's device RNG by the caller in
-normal operation, passed in verbatim by the parity tests.
+permutation; in "pdf" mode the U(0,1) draws of the sampler) is an explicit tensor argument: generated with
+torch's device RNG by the caller in normal operation, passed in verbatim by the parity tests.
 """
 from __future__ import annotations
 
@@ -31,10 +35,23 @@ class RenderSettings:
     # "f32": exact-fp32 MFMA; "f16x3": split-f16 MFMA (fp32-grade: the 1e-4 parity modes); "f16" / "bf16": single-pass
     # 16-bit MFMA with 2-byte workspaces (throughput modes, accuracy of the operand rounding: csrc/mcnerf_16.h)
     precision: str = "f32"
+    # "threshold": the reference's weight-threshold refinement (model/mc_nerf.py:613-632); "pdf": inverse-CDF hierarchical
+    # sampling of n_importance depths per ray, the fine net evaluated on Sc + n_importance sorted depths per ray
+    fine_sampler: str = "threshold"
+    n_importance: int = 128
 
     @property
     def samples_f(self):
         return self.samples_c * self.scale
+
+    @property
+    def samples_pdf(self):
+        """Depths per ray of the fine pass in "pdf" mode: the coarse ones and the importance samples."""
+        return self.samples_c + self.n_importance
+
+    @property
+    def pdf(self) -> bool:
+        return self.fine_sampler == "pdf"
 
 
 class WorkspacePool:
@@ -114,7 +131,7 @@ class RenderTrainFn(torch.autograd.Function):
     """rgb_c, rgb_f, depth_c = f(rays_d, rays_o, *coarse_params, *fine_params) with explicit draws."""
 
     @staticmethod
-    def forward(ctx, owner, model_c, model_f, step_r, only_coarse, jitter, eps_c, eps_sel, eps_f, cap_perm,
+    def forward(ctx, owner, model_c, model_f, step_r, only_coarse, jitter, eps_c, eps_sel, eps_f, cap_perm, u,
                 rays_d, rays_o, *params):
         st: RenderSettings = owner.settings
         dev = rays_d.device
@@ -146,20 +163,34 @@ class RenderTrainFn(torch.autograd.Function):
             ctx.mark_non_differentiable(depth_c)
             return rgb_c, None, depth_c
 
-        # ---- selection (no host sync) and fine pass on the compacted (ray, sample) list
-        idx, count, out_f, max_rows = select_and_cap(st, w_sel, wmax, N, cap_perm, train=True)
         net_f = model_f.net
         flat_f = model_f.flat_params()
         packed_f = ops.pack_weights(net_f, flat_f, precision=prec, range_flags=model_f.range_flags(prec, dev))
-        save_f = _pool(owner).take_save(net_f, max_rows, dev, prec) if need_grad else None
-        ops.mlp_fwd(net_f, flat_f, packed_f, rays_o, rays_d, owner.z_vals_f, jit, barf_w, out_f,
-                    idx=idx, count=count, max_rows=max_rows, save=save_f, precision=prec)
-        rgb_f, _, _, _, _ = ops.composite_fwd(out_f, rays_d, owner.z_vals_f, jit, eps_f, None, st.white_back)
+        if st.pdf:
+            # ---- inverse-CDF samples (a constant of the fine pass: no gradient through the sampler) and the dense fine pass on
+            # the sorted per-ray depth rows; the rows hold the jitter
+            z_all = ops.sample_pdf(w_sel, owner.z_vals_c, jit, u)
+            idx = count = None
+            max_rows = N * z_all.shape[1]
+            out_f = torch.empty(N, z_all.shape[1], 4, dtype=torch.float32, device=dev)
+            save_f = _pool(owner).take_save(net_f, max_rows, dev, prec) if need_grad else None
+            ops.mlp_fwd(net_f, flat_f, packed_f, rays_o, rays_d, None, None, barf_w, out_f, save=save_f, precision=prec, z_rows=z_all)
+            rgb_f, _, _, _, _ = ops.composite_fwd(out_f, rays_d, None, None, eps_f, None, st.white_back, z_rows=z_all)
+            owner.last_selection = None
+        else:
+            # ---- selection (no host sync) and fine pass on the compacted (ray, sample) list
+            z_all = None
+            idx, count, out_f, max_rows = select_and_cap(st, w_sel, wmax, N, cap_perm, train=True)
+            save_f = _pool(owner).take_save(net_f, max_rows, dev, prec) if need_grad else None
+            ops.mlp_fwd(net_f, flat_f, packed_f, rays_o, rays_d, owner.z_vals_f, jit, barf_w, out_f,
+                        idx=idx, count=count, max_rows=max_rows, save=save_f, precision=prec)
+            rgb_f, _, _, _, _ = ops.composite_fwd(out_f, rays_d, owner.z_vals_f, jit, eps_f, None, st.white_back)
+            owner.last_selection = (idx, count)
+        owner.last_z_all = z_all
         if need_grad:
             ctx.save_for_backward(rays_d, rays_o, jit, eps_c, barf_w, out_c, flat_c, packed_c,
-                                  eps_f, out_f, flat_f, packed_f, idx, count)
+                                  eps_f, out_f, flat_f, packed_f, idx, count, z_all)
             ctx.save_c, ctx.save_f, ctx.max_rows = save_c, save_f, max_rows
-        owner.last_selection = (idx, count)
         return rgb_c, rgb_f, None
 
     @staticmethod
@@ -175,7 +206,7 @@ class RenderTrainFn(torch.autograd.Function):
         rays_d, rays_o, jit, eps_c, barf_w, out_c, flat_c, packed_c = saved[:8]
         dev = rays_d.device
         N = rays_d.shape[0]
-        want_rays = ctx.needs_input_grad[10] or ctx.needs_input_grad[11]
+        want_rays = ctx.needs_input_grad[11] or ctx.needs_input_grad[12]
         d_od = torch.zeros(2, N, 3, dtype=torch.float32, device=dev) if want_rays else None      # (one fill for both)
         d_o, d_d = (d_od[0], d_od[1]) if want_rays else (None, None)
         # gradient buffers: slices of the step-level arena when a FlatGradSync provided one (so the whole
@@ -189,21 +220,23 @@ class RenderTrainFn(torch.autograd.Function):
             g_c = torch.zeros_like(flat_c)
         g_f = None
 
-        def net_backward(model, flat, packed, zgrid, eps, out, d_rgb, save, grads, idx=None, count=None, max_rows=0):
-            """One net's composite backward, dX chain and weight gradients.  The saved-operand set goes back to the pool on EVERY way
+        def net_backward(model, flat, packed, zgrid, eps, out, d_rgb, save, grads, idx=None, count=None, max_rows=0, z_rows=None):
+            """One net's composite backward, dX chain and weight gradients (`z_rows`: the per-ray depth rows of the "pdf" fine pass,
+            which hold the jitter).  The saved-operand set goes back to the pool on EVERY way
             out -- no gradient wanted, or an error (a range overflow raised by a kernel, out of memory in take_grad) --: a retried
             step must find the pool as the forward left it, not one set short."""
             net = model.net
             pool = _pool(owner)
+            jit_ = jit if z_rows is None else None
             try:
                 if d_rgb is None:
                     return
-                d_out, gmax = ops.composite_bwd(out, zgrid, jit, eps, d_rgb.contiguous(), st.white_back, want_gmax=True)
+                d_out, gmax = ops.composite_bwd(out, zgrid, jit_, eps, d_rgb.contiguous(), st.white_back, want_gmax=True, z_rows=z_rows)
                 dy, dsh = pool.take_grad(net, save, st.precision)
                 try:
-                    ops.mlp_bwd(net, flat, packed, rays_o, rays_d, zgrid, jit, barf_w, out, d_out, save, dy, dsh,
-                                d_o, d_d, idx=idx, count=count, max_rows=max_rows, precision=st.precision, gmax=gmax)
-                    rows = max_rows if idx is not None else N * zgrid.numel()
+                    ops.mlp_bwd(net, flat, packed, rays_o, rays_d, zgrid, jit_, barf_w, out, d_out, save, dy, dsh,
+                                d_o, d_d, idx=idx, count=count, max_rows=max_rows, precision=st.precision, gmax=gmax, z_rows=z_rows)
+                    rows = max_rows if idx is not None else N * (zgrid.numel() if z_rows is None else z_rows.shape[1])
                     ops.mlp_dw(net, save, dy, dsh, grads, rows, count=count, precision=st.precision, gmax=gmax)
                 finally:
                     pool.give_grad(net, save, st.precision, (dy, dsh))
@@ -215,11 +248,11 @@ class RenderTrainFn(torch.autograd.Function):
         ctx.save_c = ctx.save_f = None
         ctx.workspaces_given_back = True
         if not ctx.only_coarse:
-            eps_f, out_f, flat_f, packed_f, idx, count = saved[8:]
+            eps_f, out_f, flat_f, packed_f, idx, count, z_all = saved[8:]
             g_f = arena[n_c:n_c + n_f] if arena is not None else torch.zeros_like(flat_f)
             try:
                 net_backward(model_f, flat_f, packed_f, owner.z_vals_f, eps_f, out_f, d_rgb_f, save_f, g_f,
-                             idx=idx, count=count, max_rows=ctx.max_rows)
+                             idx=idx, count=count, max_rows=ctx.max_rows, z_rows=z_all)
             except BaseException:
                 _pool(owner).give_save(model_c.net, save_c, st.precision)      # (the coarse net's set never reaches its own backward)
                 raise
@@ -227,13 +260,14 @@ class RenderTrainFn(torch.autograd.Function):
         grads_c = model_c.grad_views(g_c)
         grads_f = model_f.grad_views(g_f) if g_f is not None else [None] * len(model_f.ordered_parameters())
         owner.last_flat_grads = (g_c, g_f)
-        return (None,) * 10 + (d_d if ctx.needs_input_grad[10] else None,
-                               d_o if ctx.needs_input_grad[11] else None) + tuple(grads_c) + tuple(grads_f)
+        return (None,) * 11 + (d_d if ctx.needs_input_grad[11] else None,
+                               d_o if ctx.needs_input_grad[12] else None) + tuple(grads_c) + tuple(grads_f)
 
 
-def render_test(owner, model_c, model_f, rays_d, rays_o, eps_c, eps_sel, eps_f, prepared=None):
+def render_test(owner, model_c, model_f, rays_d, rays_o, eps_c, eps_sel, eps_f, prepared=None, u=None):
     """NeRF_Model.render_rays_test (model/mc_nerf.py:648-680): no jitter, step_r = 1, no cap, no grad.
-    `prepared` = (packed_c, packed_f, barf_w) from an enclosing chunk loop (the weights do not change inside it)."""
+    `prepared` = (packed_c, packed_f, barf_w) from an enclosing chunk loop (the weights do not change inside it).
+    "pdf" mode: `u` [N, n_importance] are the sampler's draws (the caller passes linspace(0, 1) rows: a deterministic render)."""
     st: RenderSettings = owner.settings
     dev = rays_d.device
     N = rays_d.shape[0]
@@ -250,6 +284,13 @@ def render_test(owner, model_c, model_f, rays_d, rays_o, eps_c, eps_sel, eps_f, 
     out_c = torch.empty(N, st.samples_c, 4, dtype=torch.float32, device=dev)
     ops.mlp_fwd(net_c, flat_c, packed_c, rays_o, rays_d, owner.z_vals_c, None, barf_w, out_c, precision=prec)
     _, _, _, w_sel, wmax = ops.composite_fwd(out_c, rays_d, owner.z_vals_c, None, eps_c, eps_sel, st.white_back)
+    if st.pdf:
+        z_all = ops.sample_pdf(w_sel, owner.z_vals_c, None, u)
+        out_f = torch.empty(N, z_all.shape[1], 4, dtype=torch.float32, device=dev)
+        ops.mlp_fwd(net_f, flat_f, packed_f, rays_o, rays_d, None, None, barf_w, out_f, precision=prec, z_rows=z_all)
+        rgb, depth, opacity, _, _ = ops.composite_fwd(out_f, rays_d, None, None, eps_f, None, st.white_back, want_depth=True, z_rows=z_all)
+        owner.last_selection, owner.last_z_all = None, z_all
+        return rgb, depth, opacity
     idx, count, out_f, max_rows = select_and_cap(st, w_sel, wmax, N, None, train=False)
     ops.mlp_fwd(net_f, flat_f, packed_f, rays_o, rays_d, owner.z_vals_f, None, barf_w, out_f,
                 idx=idx, count=count, max_rows=max_rows, precision=prec)

@@ -145,6 +145,17 @@ def _stream():
     return torch.cuda.current_stream().cuda_stream
 
 
+def _depths(zgrid: Optional[Tensor], z_rows: Optional[Tensor], n_rays: int):
+    """(depth tensor, S, z_stride) of the ops that evaluate samples: the shared grid `zgrid` [S] (z_stride 0: sample j of ray r at
+    zgrid[j] + jitter[r]) or, when given, the per-ray depth rows `z_rows` [n_rays, S] (z_stride S: sample j of ray r at z_rows[r, j]
+    + jitter[r]; `zgrid` is then not read)."""
+    if z_rows is None:
+        return zgrid, zgrid.numel(), 0
+    if z_rows.dim() != 2 or z_rows.shape[0] != n_rays:
+        raise _lib.McnerfError(f"z_rows must be [n_rays = {n_rays}, S], got {tuple(z_rows.shape)}")
+    return z_rows, z_rows.shape[1], z_rows.shape[1]
+
+
 def flatten_params(net: Net, tensors, device) -> Tensor:
     """Copies per-tensor parameters (reference order) into a fresh flat buffer."""
     flat = torch.zeros(param_count(net), dtype=torch.float32, device=device)
@@ -271,17 +282,20 @@ def alloc_save(net: Net, capacity: int, device, precision: str = "f32") -> MlpSa
 def mlp_fwd(net: Net, params: Tensor, packed: Tensor, rays_o: Tensor, rays_d: Tensor, zgrid: Tensor,
             jitter: Optional[Tensor], barf_w: Tensor, out: Tensor, idx: Optional[Tensor] = None,
             count: Optional[Tensor] = None, max_rows: int = 0, save: Optional[MlpSave] = None,
-            precision: str = "f32") -> None:
-    n_rays, S = rays_d.shape[0], zgrid.numel()
+            precision: str = "f32", *, z_rows: Optional[Tensor] = None) -> None:
+    """`z_rows` [n_rays, S]: per-ray sample depths instead of the shared grid `zgrid` [S] (the dense fine pass on sample_pdf's rows,
+    jitter None: the rows hold it)."""
+    n_rays = rays_d.shape[0]
+    zgrid, S, zs = _depths(zgrid, z_rows, n_rays)
     assert out.numel() == n_rays * S * 4
     if is16(precision):
         _lib.call("mcnerf_mlp_fwd_16", *net.triple, DTYPE16[precision], _p(params), _p(packed16_split(net, packed, precision)[0], torch.uint8), _p(rays_o), _p(rays_d),
-                  _p(zgrid), _p(jitter), _p(barf_w), _p(idx, torch.int32), _p(count, torch.int32), int(max_rows), n_rays, S,
+                  _p(zgrid), zs, _p(jitter), _p(barf_w), _p(idx, torch.int32), _p(count, torch.int32), int(max_rows), n_rays, S,
                   _p(out), _p(save.act, torch.uint8) if save else None, save.capacity if save else 0,
                   _p(save.enc, torch.uint8) if save else None, _p(save.mask, torch.int32) if save else None,
                   _p(save.sh, torch.uint8) if save else None, _stream())
         return
-    _lib.call("mcnerf_mlp_fwd", *net.triple, _p(params), _p(packed), _p(rays_o), _p(rays_d), _p(zgrid),
+    _lib.call("mcnerf_mlp_fwd", *net.triple, _p(params), _p(packed), _p(rays_o), _p(rays_d), _p(zgrid), zs,
               _p(jitter), _p(barf_w), _p(idx, torch.int32), _p(count, torch.int32), int(max_rows), n_rays, S,
               _p(out), _p(save.act) if save else None, save.capacity if save else 0,
               _p(save.enc) if save else None, _p(save.sh) if save else None,
@@ -370,15 +384,17 @@ def mlp_bwd(net: Net, params: Tensor, packed: Tensor, rays_o: Tensor, rays_d: Te
             jitter: Optional[Tensor], barf_w: Tensor, out: Tensor, d_out: Tensor, save: MlpSave,
             dy: Tensor, dsh: Tensor, d_rays_o: Optional[Tensor], d_rays_d: Optional[Tensor],
             idx: Optional[Tensor] = None, count: Optional[Tensor] = None, max_rows: int = 0,
-            precision: str = "f32", gmax: Optional[Tensor] = None) -> None:
-    n_rays, S = rays_d.shape[0], zgrid.numel()
+            precision: str = "f32", gmax: Optional[Tensor] = None, *, z_rows: Optional[Tensor] = None) -> None:
+    """`z_rows`: as mlp_fwd's (the depths the forward was run on)."""
+    n_rays = rays_d.shape[0]
+    zgrid, S, zs = _depths(zgrid, z_rows, n_rays)
     if is16(precision):
         _lib.call("mcnerf_mlp_bwd_16", *net.triple, DTYPE16[precision], _p(params), _p(packed16_split(net, packed, precision)[1], torch.uint8), _p(rays_o), _p(rays_d),
-                  _p(zgrid), _p(jitter), _p(barf_w), _p(idx, torch.int32), _p(count, torch.int32), int(max_rows), n_rays, S,
+                  _p(zgrid), zs, _p(jitter), _p(barf_w), _p(idx, torch.int32), _p(count, torch.int32), int(max_rows), n_rays, S,
                   _p(out), _p(d_out), _p(save.mask, torch.int32), save.capacity, _p(save.enc, torch.uint8), _p(save.sh, torch.uint8),
                   _p(dy, torch.uint8), _p(dsh, torch.uint8), _p(d_rays_o), _p(d_rays_d), _p(gmax, torch.int32), _stream())
         return
-    args = [*net.triple, _p(params), _p(packed), _p(rays_o), _p(rays_d), _p(zgrid),
+    args = [*net.triple, _p(params), _p(packed), _p(rays_o), _p(rays_d), _p(zgrid), zs,
             _p(jitter), _p(barf_w), _p(idx, torch.int32), _p(count, torch.int32), int(max_rows), n_rays, S,
             _p(out), _p(d_out), _p(save.mask, torch.int32), save.capacity, _p(save.enc), _p(save.sh),
             _p(dy), _p(dsh), _p(d_rays_o), _p(d_rays_d)]
@@ -397,27 +413,31 @@ def mlp_dw(net: Net, save: MlpSave, dy: Tensor, dsh: Tensor, grads: Tensor, rows
 
 
 def composite_fwd(sig_rgb: Tensor, rays_d: Tensor, zgrid: Tensor, jitter: Optional[Tensor], eps: Tensor,
-                  eps_sel: Optional[Tensor] = None, white_back: bool = True, want_depth: bool = False):
-    """-> rgb [N,3], depth [N,1] | None, opacity [N,1] | None, w_sel [N,S] | None, wmax_bits | None"""
-    N, S = rays_d.shape[0], zgrid.numel()
+                  eps_sel: Optional[Tensor] = None, white_back: bool = True, want_depth: bool = False, *,
+                  z_rows: Optional[Tensor] = None):
+    """-> rgb [N,3], depth [N,1] | None, opacity [N,1] | None, w_sel [N,S] | None, wmax_bits | None.
+    `z_rows` [N,S]: per-ray depths instead of the shared grid (S is then its last dimension)."""
+    N = rays_d.shape[0]
+    zgrid, S, zs = _depths(zgrid, z_rows, N)
     dev = rays_d.device
     rgb = torch.empty(N, 3, dtype=torch.float32, device=dev)
     depth = torch.empty(N, 1, dtype=torch.float32, device=dev) if want_depth else None
     opac = torch.empty(N, 1, dtype=torch.float32, device=dev) if want_depth else None
     w_sel = torch.empty(N, S, dtype=torch.float32, device=dev) if eps_sel is not None else None
     wmax = torch.zeros(1, dtype=torch.int32, device=dev) if eps_sel is not None else None
-    _lib.call("mcnerf_composite_fwd", _p(sig_rgb), _p(rays_d), _p(zgrid), _p(jitter), _p(eps), _p(eps_sel), N, S,
+    _lib.call("mcnerf_composite_fwd", _p(sig_rgb), _p(rays_d), _p(zgrid), zs, _p(jitter), _p(eps), _p(eps_sel), N, S,
               int(bool(white_back)), _p(rgb), _p(depth), _p(opac), _p(w_sel), _p(wmax, torch.int32), _stream())
     return rgb, depth, opac, w_sel, wmax
 
 
 def composite_bwd(sig_rgb: Tensor, zgrid: Tensor, jitter: Optional[Tensor], eps: Tensor, d_rgb: Tensor,
-                  white_back: bool = True, want_gmax: bool = False):
-    """-> d_sig_rgb [N,S,4] (and, with want_gmax, the int32 word holding max|d_sig_rgb| as float bits)"""
-    N, S = d_rgb.shape[0], zgrid.numel()
+                  white_back: bool = True, want_gmax: bool = False, *, z_rows: Optional[Tensor] = None):
+    """-> d_sig_rgb [N,S,4] (and, with want_gmax, the int32 word holding max|d_sig_rgb| as float bits); `z_rows` as composite_fwd's"""
+    N = d_rgb.shape[0]
+    zgrid, S, zs = _depths(zgrid, z_rows, N)
     d = torch.empty(N, S, 4, dtype=torch.float32, device=d_rgb.device)
     gmax = torch.zeros(1, dtype=torch.int32, device=d_rgb.device) if want_gmax else None
-    _lib.call("mcnerf_composite_bwd", _p(sig_rgb), _p(zgrid), _p(jitter), _p(eps), _p(d_rgb), N, S,
+    _lib.call("mcnerf_composite_bwd", _p(sig_rgb), _p(zgrid), zs, _p(jitter), _p(eps), _p(d_rgb), N, S,
               int(bool(white_back)), _p(d), _p(gmax, torch.int32), _stream())
     return (d, gmax) if want_gmax else d
 
@@ -436,6 +456,22 @@ def select_fine(w_sel: Tensor, wmax: Tensor, thresh: float, scale: int, sigma_de
               float(sigma_default), _p(rc, torch.int32), _p(ro, torch.int32), _p(idx, torch.int32),
               _p(count, torch.int32), _p(out_f), _stream())
     return idx, count, out_f
+
+
+PDF_MAX_SAMPLES = 1024      # MCN_PDF_MAX_SAMPLES: bound on Sc + n_importance of sample_pdf
+
+
+def sample_pdf(w_sel: Tensor, zgrid: Tensor, jitter: Optional[Tensor], u: Tensor) -> Tensor:
+    """Inverse-CDF hierarchical sampling (include/mcnerf.h: mcnerf_sample_pdf): coarse selection weights w_sel [N,Sc], the coarse
+    grid zgrid [Sc], jitter [N] | None and uniform draws u [N,I] -> z_all [N,Sc+I] = sort(coarse depths ++ importance samples).
+    Not differentiable (z_all is a constant of the fine pass, as in vanilla NeRF)."""
+    N, Sc = w_sel.shape
+    if u.dim() != 2 or u.shape[0] != N or zgrid.numel() != Sc or (jitter is not None and jitter.numel() != N):
+        raise _lib.McnerfError(f"sample_pdf: w_sel [N,Sc] {tuple(w_sel.shape)}, zgrid [Sc] {tuple(zgrid.shape)}, u [N,I] {tuple(u.shape)}")
+    I = u.shape[1]
+    z_all = torch.empty(N, Sc + I, dtype=torch.float32, device=w_sel.device)
+    _lib.call("mcnerf_sample_pdf", _p(w_sel), _p(zgrid), _p(jitter), _p(u), N, Sc, I, _p(z_all), _stream())
+    return z_all
 
 
 def cap_gather(idx: Tensor, perm: Tensor, keep: int):
