@@ -13,7 +13,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 OUT = os.path.join(HERE, "libmcnerf.so")
 SOURCES = ["api.hip", "pack.hip", "mlp_fwd.hip", "mlp_bwd.hip", "mlp_dw.hip", "pack16.hip", "mlp16_fwd.hip", "mlp16_bwd.hip", "mlp16_dw.hip", "mlp_x3_fwd.hip", "mlp_x3_bwd.hip", "mlp_x3_dw.hip", "composite.hip", "sample_pdf.hip", "select_raygen.hip", "optim.hip", "camera.hip"]
-HEADERS = ["mcnerf_common.h", "mcnerf_kernels.h", "mcnerf_wave.h", "mcnerf_16.h", "mcnerf_x3.h", os.path.join("..", "..", "include", "mcnerf.h")]
+HEADERS = ["mcnerf_common.h", "mcnerf_kernels.h", "mcnerf_wave.h", "mcnerf_16.h", "mcnerf_x3.h", "mcnerf_launch.h", os.path.join("..", "..", "include", "mcnerf.h")]
 # the f16x3 chains: a layer body is ~400 MFMAs with its epilogue slices, fully unrolled (beyond hipcc's default pragma-unroll budget);
 # their 256-wide instantiations run one wave per SIMD with 512 registers, where hipcc would otherwise put the MFMA
 # accumulators in AGPRs (every epilogue read then costs a v_accvgpr_read behind a full MFMA drain)
@@ -28,12 +28,9 @@ def _newer(a, b):
     return (not os.path.exists(b)) or os.path.getmtime(a) > os.path.getmtime(b)
 
 
-def build(force=False, verbose=True, extra_flags=(), tag=""):
-    """tag / extra_flags build a VARIANT (libmcnerf_<tag>.so with extra -D flags) for kernel ablations; the
-    product library is the untagged one."""
+def build(force=False, verbose=True):
     hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
-    objdir = os.path.join(HERE, "build" + ("_" + tag if tag else ""))
-    out = os.path.join(HERE, f"libmcnerf_{tag}.so") if tag else OUT
+    objdir = os.path.join(HERE, "build")
     os.makedirs(objdir, exist_ok=True)
     hdrs = [os.path.normpath(os.path.join(CSRC, h)) for h in HEADERS]
     jobs = []
@@ -44,7 +41,7 @@ def build(force=False, verbose=True, extra_flags=(), tag=""):
 
     def cc(job):
         src, obj = job
-        cmd = [hipcc] + FLAGS + FILE_FLAGS.get(os.path.basename(src), []) + list(extra_flags) + ["-c", src, "-o", obj]
+        cmd = [hipcc] + FLAGS + FILE_FLAGS.get(os.path.basename(src), []) + ["-c", src, "-o", obj]
         r = subprocess.run(cmd, capture_output=True, text=True)
         return src, r.returncode, r.stdout + r.stderr
 
@@ -57,16 +54,15 @@ def build(force=False, verbose=True, extra_flags=(), tag=""):
             if verbose:
                 print(f"[mc_nerf_amd.build] compiled {os.path.basename(src)}")
     objs = [os.path.join(objdir, s.replace(".hip", ".o")) for s in SOURCES]
-    if jobs or not os.path.exists(out):
-        cmd = [hipcc, "--offload-arch=gfx950", "-shared", "-fPIC", "-o", out] + objs
+    if jobs or not os.path.exists(OUT):
+        cmd = [hipcc, "--offload-arch=gfx950", "-shared", "-fPIC", "-o", OUT] + objs
         r = subprocess.run(cmd, capture_output=True, text=True)
         if r.returncode != 0:
             raise RuntimeError("link failed\n" + r.stdout + r.stderr)
         if verbose:
-            print(f"[mc_nerf_amd.build] linked {out}")
-    return out
+            print(f"[mc_nerf_amd.build] linked {OUT}")
+    return OUT
 
 
 if __name__ == "__main__":
-    tag = next((a.split("=", 1)[1] for a in sys.argv if a.startswith("--tag=")), "")
-    build(force="--force" in sys.argv, extra_flags=[a for a in sys.argv[1:] if a.startswith("-") and not a.startswith("--")], tag=tag)
+    build(force="--force" in sys.argv)

@@ -4,7 +4,6 @@
 #include "mcnerf_kernels.h"
 #include "mcnerf_16.h"
 #include "mcnerf_x3.h"
-#define MCN_ACT_STRIDE(capacity, width) ((size_t)(capacity) * (width))
 #include <stdio.h>
 #include <string.h>
 
@@ -33,6 +32,29 @@ static bool net16_ok(int depth, int width, int skip) {
 // the depth layout of the sample-evaluating entry points: one grid (0) or one row per ray (S)
 static bool z_ok(int z_stride, int S) { return z_stride == 0 || z_stride == S; }
 #define REQ(cond, name) do { if (!(cond)) return fail(name, "invalid argument: " #cond); } while (0)
+// floats between the layers of the exact-fp32 workspaces
+static inline size_t act_stride(long long capacity, int width) { return (size_t)capacity * width; }
+
+// The per-sample part common to McnMlpFwdArgs / McnMlpBwdArgs / Mcn16FwdArgs / Mcn16BwdArgs, validated and filled: the net, rays, depth
+// rows, jitter, BARF weights, the (ray, sample) list and the counts.  What an entry point has beyond these it checks itself.
+template <class Args>
+static int fill_samples(const char* name, Args& a, int depth, int width, int skip, const float* params,
+                        const float* rays_o, const float* rays_d, const float* zgrid, int z_stride, const float* jitter,
+                        const float* barf_w, const int32_t* idx, const int32_t* count, int max_rows, int n_rays, int S) {
+    REQ(params && rays_o && rays_d && zgrid && barf_w && n_rays >= 0 && S > 0, name);
+    REQ((idx == nullptr) == (count == nullptr), name);
+    REQ(z_ok(z_stride, S) && (long long)n_rays * S < (1ll << 31), name);
+    a.lay = mcn_make_layout(depth, width, skip);
+    a.params = params; a.rays_o = rays_o; a.rays_d = rays_d; a.zgrid = zgrid; a.z_stride = z_stride; a.jitter = jitter;
+    a.barf_w = barf_w; a.idx = (const int2*)idx; a.count = count; a.max_rows = max_rows; a.n_rays = n_rays; a.S = S;
+    return 0;
+}
+// stand-alone CorseFine_NeRF (the apply* entry points): n rows of caller-supplied encodings, one sample per "ray" at depth z[0]; positions
+// are not used, so every other per-ray pointer is `dirs`
+template <class Args>
+static int fill_rows(const char* name, Args& a, int depth, int width, int skip, const float* params, const float* dirs, const float* z, int n) {
+    return fill_samples(name, a, depth, width, skip, params, dirs, dirs, z, 0, nullptr, dirs, nullptr, nullptr, 0, n, 1);
+}
 
 extern "C" {
 
@@ -84,21 +106,16 @@ int mcnerf_mlp_fwd(int depth, int width, int skip, const float* params, const fl
                    int n_rays, int S, float* out,
                    float* act_save, long long capacity, float* enc_save, float* sh_save, uint32_t* mask_save, void* stream) {
     REQ(net_ok(depth, width, skip), "mcnerf_mlp_fwd");
-    REQ(params && packed && rays_o && rays_d && zgrid && barf_w && out && n_rays >= 0 && S > 0, "mcnerf_mlp_fwd");
-    REQ((idx == nullptr) == (count == nullptr), "mcnerf_mlp_fwd");
+    McnMlpFwdArgs a{};
+    if (int rc = fill_samples("mcnerf_mlp_fwd", a, depth, width, skip, params, rays_o, rays_d, zgrid, z_stride, jitter, barf_w, idx, count, max_rows, n_rays, S)) return rc;
+    REQ(packed && out, "mcnerf_mlp_fwd");
     REQ(!idx || max_rows >= 0, "mcnerf_mlp_fwd");
-    REQ((long long)n_rays * S < (1ll << 31), "mcnerf_mlp_fwd");
-    REQ(z_ok(z_stride, S), "mcnerf_mlp_fwd");
     if (act_save) {
         REQ(enc_save && sh_save && mask_save, "mcnerf_mlp_fwd");
         REQ(capacity >= (idx ? (long long)max_rows : (long long)n_rays * S), "mcnerf_mlp_fwd");
     }
-    McnMlpFwdArgs a;
-    a.lay = mcn_make_layout(depth, width, skip);
-    a.params = params; a.packed = packed; a.rays_o = rays_o; a.rays_d = rays_d; a.zgrid = zgrid; a.jitter = jitter;
-    a.barf_w = barf_w; a.idx = (const int2*)idx; a.count = count; a.max_rows = max_rows; a.n_rays = n_rays; a.S = S;
-    a.out = out; a.act_save = act_save; a.act_stride = MCN_ACT_STRIDE(capacity, width); a.enc_save = enc_save; a.sh_save = sh_save; a.mask_save = mask_save;
-    a.z_stride = z_stride;
+    a.packed = packed; a.out = out;
+    a.act_save = act_save; a.act_stride = act_stride(capacity, width); a.enc_save = enc_save; a.sh_save = sh_save; a.mask_save = mask_save;
     return check("mcnerf_mlp_fwd", mcn_launch_mlp_fwd(a, (hipStream_t)stream));
 }
 
@@ -130,12 +147,9 @@ int mcnerf_encode(const float* x, const float* barf_w, int n, int n_freqs, float
 int mcnerf_mlp_apply(int depth, int width, int skip, const float* params, const float* packed, const float* x_enc,
                      const float* dirs, int n, float* out, void* stream) {
     REQ(net_ok(depth, width, skip) && params && packed && x_enc && dirs && out && n >= 0, "mcnerf_mlp_apply");
-    McnMlpFwdArgs a;
-    a.lay = mcn_make_layout(depth, width, skip);
-    a.params = params; a.packed = packed; a.rays_o = dirs; a.rays_d = dirs; a.zgrid = dirs; a.jitter = nullptr;      // positions are not used:
-    a.barf_w = dirs; a.idx = nullptr; a.count = nullptr; a.max_rows = 0; a.n_rays = n; a.S = 1;                       // the encodings come from x_enc
-    a.out = out; a.act_save = nullptr; a.act_stride = 0; a.enc_save = nullptr; a.sh_save = nullptr; a.mask_save = nullptr;
-    a.enc_in = x_enc;
+    McnMlpFwdArgs a{};
+    if (int rc = fill_rows("mcnerf_mlp_apply", a, depth, width, skip, params, dirs, dirs, n)) return rc;
+    a.packed = packed; a.out = out; a.enc_in = x_enc;
     return check("mcnerf_mlp_apply", mcn_launch_mlp_fwd(a, (hipStream_t)stream));
 }
 
@@ -149,12 +163,10 @@ int mcnerf_mlp_apply_save(int depth, int width, int skip, const float* params, c
                           float* sh_save, uint32_t* mask_save, void* stream) {
     REQ(net_ok(depth, width, skip) && params && packed && x_enc && dirs && out && n >= 0, "mcnerf_mlp_apply_save");
     REQ(act_save && enc_save && sh_save && mask_save && capacity >= n, "mcnerf_mlp_apply_save");
-    McnMlpFwdArgs a;
-    a.lay = mcn_make_layout(depth, width, skip);
-    a.params = params; a.packed = packed; a.rays_o = dirs; a.rays_d = dirs; a.zgrid = dirs; a.jitter = nullptr;
-    a.barf_w = dirs; a.idx = nullptr; a.count = nullptr; a.max_rows = 0; a.n_rays = n; a.S = 1;
-    a.out = out; a.act_save = act_save; a.act_stride = MCN_ACT_STRIDE(capacity, width); a.enc_save = enc_save; a.sh_save = sh_save; a.mask_save = mask_save;
-    a.enc_in = x_enc;
+    McnMlpFwdArgs a{};
+    if (int rc = fill_rows("mcnerf_mlp_apply_save", a, depth, width, skip, params, dirs, dirs, n)) return rc;
+    a.packed = packed; a.out = out; a.enc_in = x_enc;
+    a.act_save = act_save; a.act_stride = act_stride(capacity, width); a.enc_save = enc_save; a.sh_save = sh_save; a.mask_save = mask_save;
     return check("mcnerf_mlp_apply_save", mcn_launch_mlp_fwd(a, (hipStream_t)stream));
 }
 int mcnerf_mlp_apply_bwd(int depth, int width, int skip, const float* params, const float* packed, const float* dirs, const float* zero,
@@ -163,13 +175,11 @@ int mcnerf_mlp_apply_bwd(int depth, int width, int skip, const float* params, co
                          float* d_x_enc, float* d_dirs, void* stream) {
     REQ(net_ok(depth, width, skip) && params && packed && dirs && zero && out && d_out && n >= 0, "mcnerf_mlp_apply_bwd");
     REQ(mask_save && enc_save && sh_save && dy_save && dsh_save && d_x_enc && d_dirs && capacity >= n, "mcnerf_mlp_apply_bwd");
-    McnMlpBwdArgs a;
-    a.lay = mcn_make_layout(depth, width, skip);
-    a.params = params; a.packed = packed; a.rays_o = dirs; a.rays_d = dirs; a.zgrid = zero; a.jitter = nullptr;      // one sample per "ray" at z = 0
-    a.barf_w = dirs; a.idx = nullptr; a.count = nullptr; a.max_rows = 0; a.n_rays = n; a.S = 1;
-    a.out = out; a.d_out = d_out; a.mask_save = mask_save; a.act_stride = MCN_ACT_STRIDE(capacity, width);
+    McnMlpBwdArgs a{};
+    if (int rc = fill_rows("mcnerf_mlp_apply_bwd", a, depth, width, skip, params, dirs, zero, n)) return rc;      // (z = 0)
+    a.packed = packed; a.out = out; a.d_out = d_out; a.mask_save = mask_save; a.act_stride = act_stride(capacity, width);
     a.enc_save = enc_save; a.sh_save = sh_save; a.dy_save = dy_save; a.dsh_save = dsh_save;
-    a.d_rays_o = nullptr; a.d_rays_d = d_dirs; a.gmax_bits = nullptr; a.d_enc_out = d_x_enc;
+    a.d_rays_d = d_dirs; a.d_enc_out = d_x_enc;
     return check("mcnerf_mlp_apply_bwd", mcn_launch_mlp_bwd(a, (hipStream_t)stream));
 }
 
@@ -181,18 +191,14 @@ int mcnerf_mlp_bwd(int depth, int width, int skip, const float* params, const fl
                    const uint32_t* mask_save, long long capacity, const float* enc_save, const float* sh_save,
                    float* dy_save, float* dsh_save, float* d_rays_o, float* d_rays_d, void* stream) {
     REQ(net_ok(depth, width, skip), "mcnerf_mlp_bwd");
-    REQ(params && packed && rays_o && rays_d && zgrid && barf_w && out && d_out && n_rays >= 0 && S > 0, "mcnerf_mlp_bwd");
+    McnMlpBwdArgs a{};
+    if (int rc = fill_samples("mcnerf_mlp_bwd", a, depth, width, skip, params, rays_o, rays_d, zgrid, z_stride, jitter, barf_w, idx, count, max_rows, n_rays, S)) return rc;
+    REQ(packed && out && d_out, "mcnerf_mlp_bwd");
     REQ(mask_save && enc_save && sh_save && dy_save && dsh_save, "mcnerf_mlp_bwd");
-    REQ((idx == nullptr) == (count == nullptr), "mcnerf_mlp_bwd");
     REQ(capacity >= (idx ? (long long)max_rows : (long long)n_rays * S), "mcnerf_mlp_bwd");
-    REQ(z_ok(z_stride, S) && (long long)n_rays * S < (1ll << 31), "mcnerf_mlp_bwd");
-    McnMlpBwdArgs a;
-    a.lay = mcn_make_layout(depth, width, skip);
-    a.params = params; a.packed = packed; a.rays_o = rays_o; a.rays_d = rays_d; a.zgrid = zgrid; a.jitter = jitter;
-    a.barf_w = barf_w; a.idx = (const int2*)idx; a.count = count; a.max_rows = max_rows; a.n_rays = n_rays; a.S = S;
-    a.out = out; a.d_out = d_out; a.mask_save = mask_save; a.act_stride = MCN_ACT_STRIDE(capacity, width);
+    a.packed = packed; a.out = out; a.d_out = d_out; a.mask_save = mask_save; a.act_stride = act_stride(capacity, width);
     a.enc_save = enc_save; a.sh_save = sh_save; a.dy_save = dy_save; a.dsh_save = dsh_save;
-    a.d_rays_o = d_rays_o; a.d_rays_d = d_rays_d; a.gmax_bits = nullptr; a.z_stride = z_stride;
+    a.d_rays_o = d_rays_o; a.d_rays_d = d_rays_d;
     return check("mcnerf_mlp_bwd", mcn_launch_mlp_bwd(a, (hipStream_t)stream));
 }
 
@@ -202,10 +208,10 @@ int mcnerf_mlp_dw(int depth, int width, int skip, const int32_t* count, int rows
                   long long capacity, float* grads, void* stream) {
     REQ(net_ok(depth, width, skip), "mcnerf_mlp_dw");
     REQ(act_save && enc_save && dy_save && dsh_save && grads && rows >= 0 && capacity >= rows, "mcnerf_mlp_dw");
-    McnDwArgs a;
+    McnDwArgs a{};
     a.lay = mcn_make_layout(depth, width, skip);
     a.count = count; a.rows = rows; a.act_save = act_save; a.enc_save = enc_save; a.dy_save = dy_save;
-    a.dsh_save = dsh_save; a.act_stride = MCN_ACT_STRIDE(capacity, width); a.grads = grads; a.split16 = false; a.gmax_bits = nullptr;
+    a.dsh_save = dsh_save; a.act_stride = act_stride(capacity, width); a.grads = grads;
     return check("mcnerf_mlp_dw", mcn_launch_dw(a, (hipStream_t)stream));
 }
 
@@ -213,18 +219,18 @@ int mcnerf_mlp_dw(int depth, int width, int skip, const int32_t* count, int rows
 // ---- register-chain modes: single-pass 16-bit (mcnerf_16.h; dtype 0 = f16, 1 = bf16), split-f16 "f16x3" (mcnerf_x3.h; dtype 2), and
 //      dtype 3 "f16x3h": the split-f16 forward / backward chains saving only the hi plane of every operand (16-bit workspace layout),
 //      the weight gradient by the single-pass f16 kernel on those planes
+//      (what the launchers ask about a dtype: mcn16_is_bf16 / mcn16_x3_chain / mcn16_hi_planes_only, mcnerf_16.h)
 static bool dtype_ok(int dtype) { return dtype >= 0 && dtype <= 3; }
-static bool x3_chain(int dtype) { return dtype == 2 || dtype == 3; }
 long long mcnerf_packed_bytes_16(int depth, int width, int skip, int dtype, int backward) {
     if (!net16_ok(depth, width, skip) || !dtype_ok(dtype)) return -1;
     const McnLayout L = mcn_make_layout(depth, width, skip);
-    if (x3_chain(dtype)) return (long long)(backward ? mcnx3_bwd_stream(L) : mcnx3_fwd_stream(L)).total_frags * 2048;
+    if (mcn16_x3_chain(dtype)) return (long long)(backward ? mcnx3_bwd_stream(L) : mcnx3_fwd_stream(L)).total_frags * 2048;
     return (long long)(backward ? mcn16_bwd_stream(L) : mcn16_fwd_stream(L)).total_frags * 1024;
 }
 int mcnerf_pack_weights_16(int depth, int width, int skip, const float* params, void* packed_fwd, void* packed_bwd,
                            int dtype, uint32_t* range_flags, void* stream) {
     REQ(net16_ok(depth, width, skip) && params && packed_fwd && packed_bwd && dtype_ok(dtype), "mcnerf_pack_weights_16");
-    if (x3_chain(dtype)) return check("mcnerf_pack_weights_16", mcnx3_launch_pack(mcn_make_layout(depth, width, skip), params, packed_fwd, packed_bwd, range_flags, (hipStream_t)stream));
+    if (mcn16_x3_chain(dtype)) return check("mcnerf_pack_weights_16", mcnx3_launch_pack(mcn_make_layout(depth, width, skip), params, packed_fwd, packed_bwd, range_flags, (hipStream_t)stream));
     return check("mcnerf_pack_weights_16", mcn16_launch_pack(mcn_make_layout(depth, width, skip), params, packed_fwd, packed_bwd, dtype, range_flags, (hipStream_t)stream));
 }
 static size_t slot_bytes_of(int dtype, long long capacity, int width) { return dtype == 2 ? mcnx3_slot_bytes(capacity, width) : mcn16_slot_bytes(capacity, width); }
@@ -236,7 +242,7 @@ long long mcnerf_ws_bytes_16(int depth, int width, int dtype, long long capacity
         case 1: return (long long)(x3 ? mcnx3_enc_bytes(capacity) : mcn16_enc_bytes(capacity));
         case 2: return (long long)(depth + 2) * (long long)mcn16_mask_slot_bytes(capacity, width);
         case 3: return (long long)(x3 ? mcnx3_dsh_bytes(capacity) : mcn16_dsh_bytes(capacity));
-        case 4: return (long long)(x3_chain(dtype) ? mcnx3_sh_bytes(capacity) : mcn16_dsh_bytes(capacity));      // (the chains' fp32 sh.2 tile)
+        case 4: return (long long)(mcn16_x3_chain(dtype) ? mcnx3_sh_bytes(capacity) : mcn16_dsh_bytes(capacity));      // (the chains' fp32 sh.2 tile)
     }
     return -1;
 }
@@ -246,22 +252,17 @@ int mcnerf_mlp_fwd_16(int depth, int width, int skip, int dtype, const float* pa
                       int n_rays, int S, float* out,
                       void* act_ws, long long capacity, void* enc_ws, uint32_t* mask_ws, void* sh_ws, void* stream) {
     REQ(net16_ok(depth, width, skip) && dtype_ok(dtype), "mcnerf_mlp_fwd_16");
-    REQ(params && packed_fwd && rays_o && rays_d && zgrid && barf_w && out && n_rays >= 0 && S > 0, "mcnerf_mlp_fwd_16");
-    REQ((idx == nullptr) == (count == nullptr), "mcnerf_mlp_fwd_16");
+    Mcn16FwdArgs a{};
+    if (int rc = fill_samples("mcnerf_mlp_fwd_16", a, depth, width, skip, params, rays_o, rays_d, zgrid, z_stride, jitter, barf_w, idx, count, max_rows, n_rays, S)) return rc;
+    REQ(packed_fwd && out, "mcnerf_mlp_fwd_16");
     REQ(!idx || max_rows >= 0, "mcnerf_mlp_fwd_16");
-    REQ((long long)n_rays * S < (1ll << 31), "mcnerf_mlp_fwd_16");
-    REQ(z_ok(z_stride, S), "mcnerf_mlp_fwd_16");
     REQ((act_ws == nullptr) == (enc_ws == nullptr) && (act_ws == nullptr) == (mask_ws == nullptr) && (act_ws == nullptr) == (sh_ws == nullptr), "mcnerf_mlp_fwd_16");
     if (act_ws) REQ(capacity >= (idx ? (long long)max_rows : (long long)n_rays * S), "mcnerf_mlp_fwd_16");
-    Mcn16FwdArgs a;
-    a.lay = mcn_make_layout(depth, width, skip);
-    a.params = params; a.packed = packed_fwd; a.bf16 = dtype;
-    a.stream_slabs = x3_chain(dtype) ? mcnx3_fwd_stream(a.lay).total_frags / MCNX3_SLABF : mcn16_fwd_stream(a.lay).total_frags / MCN16_SLAB;
-    a.rays_o = rays_o; a.rays_d = rays_d; a.zgrid = zgrid; a.jitter = jitter; a.barf_w = barf_w;
-    a.idx = (const int2*)idx; a.count = count; a.max_rows = max_rows; a.n_rays = n_rays; a.S = S; a.out = out;
-    a.act_ws = act_ws; a.slot_bytes = slot_bytes_of(dtype, capacity, width); a.enc_ws = enc_ws;
-    a.mask_ws = mask_ws; a.mask_slot_words = mcn16_mask_slot_bytes(capacity, width) / 4; a.sh_ws = sh_ws; a.z_stride = z_stride;
-    return check("mcnerf_mlp_fwd_16", x3_chain(dtype) ? mcnx3_launch_fwd(a, (hipStream_t)stream) : mcn16_launch_fwd(a, (hipStream_t)stream));
+    a.packed = packed_fwd; a.dtype = dtype;
+    a.stream_slabs = mcn16_x3_chain(dtype) ? mcnx3_fwd_stream(a.lay).total_frags / MCNX3_SLABF : mcn16_fwd_stream(a.lay).total_frags / MCN16_SLAB;
+    a.out = out; a.act_ws = act_ws; a.slot_bytes = slot_bytes_of(dtype, capacity, width); a.enc_ws = enc_ws;
+    a.mask_ws = mask_ws; a.mask_slot_words = mcn16_mask_slot_bytes(capacity, width) / 4; a.sh_ws = sh_ws;
+    return check("mcnerf_mlp_fwd_16", mcn16_x3_chain(dtype) ? mcnx3_launch_fwd(a, (hipStream_t)stream) : mcn16_launch_fwd(a, (hipStream_t)stream));
 }
 int mcnerf_mlp_bwd_16(int depth, int width, int skip, int dtype, const float* params, const void* packed_bwd,
                       const float* rays_o, const float* rays_d, const float* zgrid, int z_stride, const float* jitter,
@@ -270,32 +271,28 @@ int mcnerf_mlp_bwd_16(int depth, int width, int skip, int dtype, const float* pa
                       const uint32_t* mask_ws, long long capacity, const void* enc_ws, const void* sh_ws,
                       void* dy_ws, void* dsh_ws, float* d_rays_o, float* d_rays_d, const uint32_t* gmax_bits, void* stream) {
     REQ(net16_ok(depth, width, skip) && dtype_ok(dtype), "mcnerf_mlp_bwd_16");
-    REQ(params && packed_bwd && gmax_bits && rays_o && rays_d && zgrid && barf_w && out && d_out && n_rays >= 0 && S > 0, "mcnerf_mlp_bwd_16");
+    Mcn16BwdArgs a{};
+    if (int rc = fill_samples("mcnerf_mlp_bwd_16", a, depth, width, skip, params, rays_o, rays_d, zgrid, z_stride, jitter, barf_w, idx, count, max_rows, n_rays, S)) return rc;
+    REQ(packed_bwd && gmax_bits && out && d_out, "mcnerf_mlp_bwd_16");
     REQ(mask_ws && enc_ws && sh_ws && dy_ws && dsh_ws, "mcnerf_mlp_bwd_16");
-    REQ((idx == nullptr) == (count == nullptr), "mcnerf_mlp_bwd_16");
     REQ(capacity >= (idx ? (long long)max_rows : (long long)n_rays * S), "mcnerf_mlp_bwd_16");
-    REQ(z_ok(z_stride, S) && (long long)n_rays * S < (1ll << 31), "mcnerf_mlp_bwd_16");
-    Mcn16BwdArgs a;
-    a.lay = mcn_make_layout(depth, width, skip);
-    a.params = params; a.packed = packed_bwd; a.bf16 = dtype;
-    a.stream_slabs = x3_chain(dtype) ? mcnx3_bwd_stream(a.lay).total_frags / MCNX3_SLABF : mcn16_bwd_stream(a.lay).total_frags / MCN16_SLAB;
-    a.rays_o = rays_o; a.rays_d = rays_d; a.zgrid = zgrid; a.jitter = jitter; a.barf_w = barf_w;
-    a.idx = (const int2*)idx; a.count = count; a.max_rows = max_rows; a.n_rays = n_rays; a.S = S;
+    a.packed = packed_bwd; a.dtype = dtype;
+    a.stream_slabs = mcn16_x3_chain(dtype) ? mcnx3_bwd_stream(a.lay).total_frags / MCNX3_SLABF : mcn16_bwd_stream(a.lay).total_frags / MCN16_SLAB;
     a.out = out; a.d_out = d_out; a.mask_ws = mask_ws; a.mask_slot_words = mcn16_mask_slot_bytes(capacity, width) / 4;
     a.enc_ws = enc_ws; a.sh_ws = sh_ws; a.dy_ws = dy_ws; a.slot_bytes = slot_bytes_of(dtype, capacity, width); a.dsh_ws = dsh_ws;
-    a.d_rays_o = d_rays_o; a.d_rays_d = d_rays_d; a.gmax_bits = gmax_bits; a.z_stride = z_stride;
-    return check("mcnerf_mlp_bwd_16", x3_chain(dtype) ? mcnx3_launch_bwd(a, (hipStream_t)stream) : mcn16_launch_bwd(a, (hipStream_t)stream));
+    a.d_rays_o = d_rays_o; a.d_rays_d = d_rays_d; a.gmax_bits = gmax_bits;
+    return check("mcnerf_mlp_bwd_16", mcn16_x3_chain(dtype) ? mcnx3_launch_bwd(a, (hipStream_t)stream) : mcn16_launch_bwd(a, (hipStream_t)stream));
 }
 int mcnerf_mlp_dw_16(int depth, int width, int skip, int dtype, const int32_t* count, int rows,
                      const void* act_ws, const void* enc_ws, const void* dy_ws, const void* dsh_ws,
                      long long capacity, float* grads, const uint32_t* gmax_bits, void* stream) {
     REQ(net16_ok(depth, width, skip) && dtype_ok(dtype), "mcnerf_mlp_dw_16");
     REQ(act_ws && enc_ws && dy_ws && dsh_ws && grads && gmax_bits && rows >= 0 && capacity >= rows, "mcnerf_mlp_dw_16");
-    Mcn16DwArgs a;
+    Mcn16DwArgs a{};
     a.lay = mcn_make_layout(depth, width, skip);
-    a.bf16 = dtype == 3 ? 0 : dtype; a.count = count; a.rows = rows; a.act_ws = act_ws; a.enc_ws = enc_ws; a.dy_ws = dy_ws; a.dsh_ws = dsh_ws;
+    a.dtype = dtype; a.count = count; a.rows = rows; a.act_ws = act_ws; a.enc_ws = enc_ws; a.dy_ws = dy_ws; a.dsh_ws = dsh_ws;
     a.slot_bytes = slot_bytes_of(dtype, capacity, width); a.grads = grads; a.gmax_bits = gmax_bits;
-    a.x_scale = dtype == 3 ? MCNX3_SX : 1.f;           // (dtype 3: f16 hi planes of the split-f16 chains, activations x 2^3)
+    a.x_scale = mcn16_hi_planes_only(dtype) ? MCNX3_SX : 1.f;       // (f16 hi planes of the split-f16 chains: activations x 2^3)
     return check("mcnerf_mlp_dw_16", dtype == 2 ? mcnx3_launch_dw(a, (hipStream_t)stream) : mcn16_launch_dw(a, (hipStream_t)stream));
 }
 

@@ -96,12 +96,17 @@ static inline size_t mcn16_mask_slot_bytes(long long capacity, int width) { retu
 static inline size_t mcn16_enc_bytes(long long capacity) { return (size_t)mcn16_cap_tiles(capacity) * MCN16_ENCKS * 1024; }
 static inline size_t mcn16_dsh_bytes(long long capacity) { return (size_t)mcn16_cap_tiles(capacity) * 2 * 1024; }
 
+// the ABI's dtype 0 .. 3 of the register-chain entry points, as the launchers ask about it
+static inline bool mcn16_is_bf16(int dtype) { return dtype == 1; }                 // 16-bit kernels: bf16 rather than f16 operands
+static inline bool mcn16_x3_chain(int dtype) { return dtype == 2 || dtype == 3; }  // forward / backward by the split-f16 chains
+static inline bool mcn16_hi_planes_only(int dtype) { return dtype == 3; }          // ... which save the hi plane of every operand alone
+
 struct Mcn16FwdArgs {
     McnLayout lay;
     const float* params;        // flat fp32 parameters (biases, sigma.2)
     const void* packed;         // forward stream (mcn16_fwd_stream order), 16-bit
     int stream_slabs;           // total_frags / 16
-    int bf16;                   // 0 = f16, 1 = bf16; the split-f16 launchers: 2 = (hi, lo) workspaces, 3 = hi planes only (16-bit layout)
+    int dtype;                  // the ABI's dtype: 0 = f16, 1 = bf16; the split-f16 launchers: 2 = (hi, lo) workspaces, 3 = hi planes only (16-bit layout)
     const float* rays_o; const float* rays_d; const float* zgrid; const float* jitter; const float* barf_w;
     const int2* idx; const int* count; int max_rows; int n_rays, S;
     float* out;                 // [n_rays,S,4]
@@ -119,7 +124,7 @@ struct Mcn16BwdArgs {
     const float* params;
     const void* packed;         // backward stream (mcn16_bwd_stream order)
     int stream_slabs;
-    int bf16;
+    int dtype;
     const float* rays_o; const float* rays_d; const float* zgrid; const float* jitter; const float* barf_w;
     const int2* idx; const int* count; int max_rows; int n_rays, S;
     const float* out; const float* d_out;
@@ -136,7 +141,7 @@ hipError_t mcn16_launch_bwd(const Mcn16BwdArgs& a, hipStream_t st);
 
 struct Mcn16DwArgs {
     McnLayout lay;
-    int bf16;
+    int dtype;
     const int* count; int rows;
     const void* act_ws; const void* enc_ws; const void* dy_ws; const void* dsh_ws;
     size_t slot_bytes;
@@ -145,6 +150,74 @@ struct Mcn16DwArgs {
     float x_scale;              // scale of the X planes (0 / 1: none; MCNX3_SX for the hi planes of the split-f16 chains, dtype 3)
 };
 hipError_t mcn16_launch_dw(const Mcn16DwArgs& a, hipStream_t st);
+
+// One segment of the weight-gradient job (mlp16_dw.hip; mlp_x3_dw.hip reads the same fields over (hi, lo) plane pairs).
+struct Dw16Seg {
+    const char* dY; int ksn;      // fragment-major [tile][ksn][64][8]: N = 16 ksn columns
+    const char* X;  int ksk;      // fragment-major [tile][ksk][64][8]: K = 16 ksk columns
+    const char* X2; int ksk2;     // optional second input block, K2 = 16 ksk2 more columns (the skip layer: [hidden | encoded] in ONE
+                                  // pass, so its dY is read once); null / 0 otherwise
+    int n_lo, n_real;             // outputs n_lo <= n < n_real are real (row n - n_lo of dW)
+    int col, k_real;              // input k < K of X is real for k < k_real and lands in column col + k of the dW row
+    int col2, k_real2;            // input K + k of X2: column col2 + k, real for k < k_real2
+    float* dW; int ldw;
+    float* db;
+    int kmap, kmap2, nmap;        // index maps (mcnerf_common.h; 0 = none): encoded input columns of X / X2 through mcn_enc_col(k, F = kmap / kmap2),
+                                  // sh.2 output rows through mcn_sh_row(n, nmap - 16): gradients of channels / rows the net does not have are dropped
+};
+#define MCN16_DW_MAXSEG 15
+
+// The D + 4 .. D + 5 segments of one net into job.n / job.shape / job.seg (Job = Dw16Job or DwX3Job); false if they do not fit.
+// shape: 0: W x W   1: W x 64 (encoded-input columns)   2: 32 x W (sh.2 / sigma.2 rows)   3: W x (W + 64) (merged skip layer)
+template <class Job>
+static inline bool mcn16_dw_job(const Mcn16DwArgs& a, Job& job) {
+    const McnLayout& L = a.lay;
+    const int W = L.width, D = L.depth, KS = W / 16;
+    const int ME = L.nfreq == MCN_NFREQ ? 0 : L.nfreq, MS = L.sh_deg == 2 ? 0 : 16 + L.sh_deg;      // index maps (Dw16Seg)
+    auto act = [&](int slot) { return reinterpret_cast<const char*>(a.act_ws) + (size_t)slot * a.slot_bytes; };
+    auto dy = [&](int slot) { return reinterpret_cast<const char*>(a.dy_ws) + (size_t)slot * a.slot_bytes; };
+    const char* dsh = reinterpret_cast<const char*>(a.dsh_ws);
+    float* const g = a.grads;
+    job.n = 0;
+    if (D + 5 > MCN16_DW_MAXSEG) return false;
+    // a segment is added with its outputs (rows n_lo .. n_real of the KSN k-steps of dY -> dW / db); hidden() / encoded() then name
+    // its inputs: the first fills X, a second X2
+    auto add = [&](int shape, const char* dY, int ksn, int n_lo, int n_real, float* dW, int ldw, float* db, int nmap = 0) -> Dw16Seg& {
+        Dw16Seg& s = job.seg[job.n];
+        job.shape[job.n++] = shape;
+        s = Dw16Seg{};
+        s.dY = dY; s.ksn = ksn; s.n_lo = n_lo; s.n_real = n_real; s.dW = dW; s.ldw = ldw; s.db = db; s.nmap = nmap;
+        return s;
+    };
+    auto input = [](Dw16Seg& s, const char* x, int ks, int col, int k_real, int kmap) {
+        if (!s.X) { s.X = x; s.ksk = ks; s.col = col; s.k_real = k_real; s.kmap = kmap; }
+        else { s.X2 = x; s.ksk2 = ks; s.col2 = col; s.k_real2 = k_real; s.kmap2 = kmap; }
+    };
+    auto hidden = [&](Dw16Seg& s, int slot, int col) { input(s, act(slot), KS, col, W, 0); };        // the W activations of `slot` -> columns col ..
+    auto encoded = [&](Dw16Seg& s) { input(s, reinterpret_cast<const char*>(a.enc_ws), MCN16_ENCKS, 0, MCN_ENC, ME); };   // -> columns 0 .. 62
+    const bool merged = (W == 256 || W == 128);       // (Dw16SkipMerged / DwX3SkipMerged)
+    for (int l = 0; l < D; ++l) {
+        const int ldw = mcn_layer_in(L, l);
+        float* dWl = g + L.pW[l];
+        float* dbl = g + L.pB[l];
+        if (l == 0) encoded(add(1, dy(l), KS, 0, W, dWl, ldw, dbl));
+        else if (l == L.skip && merged) {             // [hidden | encoded] in one pass: hidden k -> column 63 + k, encoded k -> column k
+            Dw16Seg& s = add(3, dy(l), KS, 0, W, dWl, ldw, dbl);
+            hidden(s, l - 1, L.nenc);
+            encoded(s);
+        } else if (l == L.skip) {                     // ... in two: the bias gradient with the first
+            encoded(add(1, dy(l), KS, 0, W, dWl, ldw, dbl));
+            hidden(add(0, dy(l), KS, 0, W, dWl, ldw, nullptr), l - 1, L.nenc);
+        } else hidden(add(0, dy(l), KS, 0, W, dWl, ldw, dbl), l - 1, 0);
+    }
+    // sigma.0 and sh.0 read the last trunk activation; sh.2 reads the sh hidden layer
+    hidden(add(0, dy(D), KS, 0, W, g + L.pWs1, W, g + L.pBs1), D - 1, 0);
+    hidden(add(0, dy(D + 1), KS, 0, W, g + L.pWc1, W, g + L.pBc1), D - 1, 0);
+    hidden(add(2, dsh, 2, 0, MCN_NSH, g + L.pWc2, W, g + L.pBc2, MS), D + 1, 0);
+    // sigma.2 (1 x W): d sigma sits in column 27 of dsh, its input is the sigma hidden layer
+    hidden(add(2, dsh, 2, MCN_NSH, MCN_NSH + 1, g + L.pWs2, W, g + L.pBs2), D, 0);
+    return true;
+}
 hipError_t mcn16_launch_pack(const McnLayout& L, const float* params, void* packed_fwd, void* packed_bwd, int bf16, unsigned* range_flags, hipStream_t st);
 
 #ifdef __HIPCC__

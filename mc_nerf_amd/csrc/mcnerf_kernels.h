@@ -58,7 +58,7 @@ struct McnMlpBwdArgs {
     float* dsh_save;          // [capacity][32] gradient of the sh.2 outputs (cols 0..26) and of sigma_raw (col 27)
     float* d_rays_o;          // [n_rays,3] accumulated with atomics (may be null)
     float* d_rays_d;          // [n_rays,3]
-    const unsigned int* gmax_bits;   // split-f16 mode only: float bits of max|d_out| over the launch (device scalar)
+    const unsigned int* gmax_bits;   // unused (null); stays: the struct is a kernel parameter, its layout part of the kernel
     float* d_enc_out = nullptr;      // stand-alone CorseFine_NeRF backward: the encoded-input gradient [rows][63] is the result
                                      // (no positional-encoding backward; d_rays_d then receives the SH view-direction term alone)
     int z_stride = 0;         // as McnMlpFwdArgs::z_stride
@@ -75,8 +75,6 @@ struct McnDwArgs {
     const float* dsh_save;
     size_t act_stride;
     float* grads;             // flat gradient buffer (same layout as params), accumulated with atomics
-    bool split16;             // (unused: the split-f16 mode lives in mlp_x3_dw.hip)
-    const unsigned int* gmax_bits;   // split-f16 mode: float bits of max|d_out| (gradient scale), device scalar
 };
 hipError_t mcn_launch_dw(const McnDwArgs& a, hipStream_t st);
 

@@ -9,6 +9,7 @@
 // per-launch power of two SG (f16 range; derived from max|d_out| as in the split-f16 mode).
 // Replaces autograd through model/net_block.py:22-33, 67-78 and model/mc_nerf.py:602, 635, 690-691.
 #include "mcnerf_16.h"
+#include "mcnerf_launch.h"
 
 
 template <int W>
@@ -429,29 +430,10 @@ __global__ __launch_bounds__(64 * MCN16_WAVES, 2) void mlp16_bwd_kernel(Mcn16Bwd
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
 }
 
-template <int W>
-static hipError_t launch_bwd16(const Mcn16BwdArgs& a, long long max_rows, hipStream_t st) {
-    using SM = Bwd16Smem<W>;
-    int dev = 0, cus = 256;
-    hipDeviceProp_t prop;
-    if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess && prop.multiProcessorCount > 0) cus = prop.multiProcessorCount;
-    long long passes = (max_rows + MCN16_ROWS - 1) / MCN16_ROWS;
-    if (passes <= 0) return hipSuccess;
-    const int grid = (int)(passes < cus ? passes : cus);
-    void (*kern)(Mcn16BwdArgs) = a.bf16 ? mlp16_bwd_kernel<W, true> : mlp16_bwd_kernel<W, false>;
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, SM::total);
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(64 * MCN16_WAVES), SM::total, st, a);
-    return hipGetLastError();
-}
-
 hipError_t mcn16_launch_bwd(const Mcn16BwdArgs& a, hipStream_t st) {
-    const long long max_rows = a.count ? (long long)a.max_rows : (long long)a.n_rays * a.S;
-    switch (a.lay.width) {
-        case 256: return launch_bwd16<256>(a, max_rows, st);
-        case 128: return launch_bwd16<128>(a, max_rows, st);
-        case 64:  return launch_bwd16<64>(a, max_rows, st);
-        case 32:  return launch_bwd16<32>(a, max_rows, st);
-    }
-    return hipErrorInvalidValue;
+    return mcn_for_width(a.lay.width, [&](auto w) {
+        constexpr int W = decltype(w)::value;
+        void (*kern)(Mcn16BwdArgs) = mcn16_is_bf16(a.dtype) ? mlp16_bwd_kernel<W, true> : mlp16_bwd_kernel<W, false>;
+        return mcn_launch(kern, mcn_persistent_grid(mcn_passes(mcn_max_rows(a), MCN16_ROWS)), 64 * MCN16_WAVES, Bwd16Smem<W>::total, st, a);
+    });
 }

@@ -17,20 +17,7 @@
 // (s, hh, m .. m+3) of two fragments s.  The DMA places chunk (hh, m) of fragment s at position
 // 32 hh + (m ^ 4 (2 (s & 1) + hh)), which spreads the 16 chunks of one 32-lane half over all 64 banks.
 #include "mcnerf_16.h"
-
-struct Dw16Seg {
-    const char* dY; int ksn;      // fragment-major [tile][ksn][64][8]: N = 16 ksn columns
-    const char* X;  int ksk;      // fragment-major [tile][ksk][64][8]: K = 16 ksk columns
-    const char* X2; int ksk2;     // optional second input block, K2 = 16 ksk2 more columns (the skip layer: [hidden | encoded] in ONE
-                                  // pass, so its dY is read once); null / 0 otherwise
-    int n_lo, n_real;             // outputs n_lo <= n < n_real are real (row n - n_lo of dW)
-    int col, k_real;              // input k < K of X is real for k < k_real and lands in column col + k of the dW row
-    int col2, k_real2;            // input K + k of X2: column col2 + k, real for k < k_real2
-    float* dW; int ldw;
-    float* db;
-    int kmap, kmap2, nmap;        // index maps (mcnerf_common.h; 0 = none): encoded input columns of X / X2 through mcn_enc_col(k, F = kmap / kmap2),
-                                  // sh.2 output rows through mcn_sh_row(n, nmap - 16): gradients of channels / rows the net does not have are dropped
-};
+#include "mcnerf_launch.h"
 
 constexpr int dw16_pick(int N, int K, bool want_vn) {
     int bestG = 0, bestVN = 1, bestKT = 1;
@@ -241,12 +228,11 @@ __device__ __forceinline__ void dw16_run(const Dw16Seg& sg, const int t0, const 
 }
 
 // ---- one launch per net ---------------------------------------------------------------------------------------------
-#define DW16_MAXSEG 15
 struct Dw16Job {
     int n;
     float x_scale;                // power-of-two scale of the X planes (1; MCNX3_SX when the planes are the split-f16 chains' hi planes)
-    int shape[DW16_MAXSEG];       // 0: W x W   1: W x 64 (encoded-input columns)   2: 32 x W (sh.2 / sigma.2 rows)   3: W x (W + 64) (skip layer)
-    Dw16Seg seg[DW16_MAXSEG];
+    int shape[MCN16_DW_MAXSEG];       // 0: W x W   1: W x 64 (encoded-input columns)   2: 32 x W (sh.2 / sigma.2 rows)   3: W x (W + 64) (skip layer)
+    Dw16Seg seg[MCN16_DW_MAXSEG];
 };
 
 // the skip layer as ONE segment over [hidden | encoded] inputs (its dY read once): wide nets, where the W x (W + 64) block
@@ -282,74 +268,15 @@ __global__ __launch_bounds__(64 * MCN16_WAVES) void dw16_stream_kernel(Dw16Job j
     }
 }
 
-static int dw16_num_cus() {
-    static int cus = 0;
-    if (!cus) {
-        int dev = 0;
-        hipDeviceProp_t prop;
-        if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess) cus = prop.multiProcessorCount;
-        if (cus <= 0) cus = 256;
-    }
-    return cus;
-}
-
-template <int W>
-static hipError_t dw16_launch_job(const Dw16Job& job, const int* count, int rows_cap, int bf16, const unsigned* gmax_bits, hipStream_t st) {
-    if (rows_cap <= 0) return hipSuccess;
-    const long long ntiles = (rows_cap + 31) / 32;
-    long long grid = dw16_num_cus();
-    if (grid > ntiles * job.n) grid = ntiles * job.n;
-    const int pmax = Dw16SkipMerged<W>::value ? 2 * W / 16 + MCN16_ENCKS : (2 * W / 16 > W / 16 + MCN16_ENCKS ? 2 * W / 16 : W / 16 + MCN16_ENCKS);
-    const size_t lds = (size_t)DW16_STAGES * pmax * 1024;
-    void (*kern)(Dw16Job, const int*, int, const unsigned*) = bf16 ? dw16_stream_kernel<W, true> : dw16_stream_kernel<W, false>;
-    static bool attr_set[2] = {false, false};                          // (per width instantiation and precision)
-    if (lds > 64 * 1024 && !attr_set[bf16 ? 1 : 0]) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) return e;
-        attr_set[bf16 ? 1 : 0] = true;
-    }
-    hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(64 * MCN16_WAVES), lds, st, job, count, rows_cap, gmax_bits);
-    return hipGetLastError();
-}
-
 hipError_t mcn16_launch_dw(const Mcn16DwArgs& a, hipStream_t st) {
-    const McnLayout& L = a.lay;
-    const int W = L.width, D = L.depth, KS = W / 16;
-    const int ME = L.nfreq == MCN_NFREQ ? 0 : L.nfreq, MS = L.sh_deg == 2 ? 0 : 16 + L.sh_deg;      // index maps (Dw16Seg)
-    auto act = [&](int slot) { return reinterpret_cast<const char*>(a.act_ws) + (size_t)slot * a.slot_bytes; };
-    auto dy = [&](int slot) { return reinterpret_cast<const char*>(a.dy_ws) + (size_t)slot * a.slot_bytes; };
-    const char* enc = reinterpret_cast<const char*>(a.enc_ws);
-    const char* dsh = reinterpret_cast<const char*>(a.dsh_ws);
-    Dw16Job job;
-    job.n = 0;
+    Dw16Job job{};
+    if (!mcn16_dw_job(a, job)) return hipErrorInvalidValue;
     job.x_scale = a.x_scale > 0.f ? a.x_scale : 1.f;
-    auto add = [&](int shape, const Dw16Seg& s) { job.shape[job.n] = shape; job.seg[job.n] = s; ++job.n; };
-    if (D + 5 > DW16_MAXSEG) return hipErrorInvalidValue;
-    const bool merged = (W == 256 || W == 128);       // (Dw16SkipMerged)
-    for (int l = 0; l < D; ++l) {
-        const int ldw = mcn_layer_in(L, l);
-        float* dWl = a.grads + L.pW[l];
-        float* dbl = a.grads + L.pB[l];
-        if (l == 0)                       // encoded-input columns only
-            add(1, Dw16Seg{dy(l), KS, enc, MCN16_ENCKS, nullptr, 0, 0, W, 0, MCN_ENC, 0, 0, dWl, ldw, dbl, ME, 0, 0});
-        else if (l == L.skip && merged)   // [hidden | encoded] in one pass: hidden k -> column 63 + k, encoded k -> column k
-            add(3, Dw16Seg{dy(l), KS, act(l - 1), KS, enc, MCN16_ENCKS, 0, W, L.nenc, W, 0, MCN_ENC, dWl, ldw, dbl, 0, ME, 0});
-        else if (l == L.skip) {
-            add(1, Dw16Seg{dy(l), KS, enc, MCN16_ENCKS, nullptr, 0, 0, W, 0, MCN_ENC, 0, 0, dWl, ldw, dbl, ME, 0, 0});
-            add(0, Dw16Seg{dy(l), KS, act(l - 1), KS, nullptr, 0, 0, W, L.nenc, W, 0, 0, dWl, ldw, nullptr, 0, 0, 0});
-        } else
-            add(0, Dw16Seg{dy(l), KS, act(l - 1), KS, nullptr, 0, 0, W, 0, W, 0, 0, dWl, ldw, dbl, 0, 0, 0});
-    }
-    add(0, Dw16Seg{dy(D), KS, act(D - 1), KS, nullptr, 0, 0, W, 0, W, 0, 0, a.grads + L.pWs1, W, a.grads + L.pBs1, 0, 0, 0});
-    add(0, Dw16Seg{dy(D + 1), KS, act(D - 1), KS, nullptr, 0, 0, W, 0, W, 0, 0, a.grads + L.pWc1, W, a.grads + L.pBc1, 0, 0, 0});
-    add(2, Dw16Seg{dsh, 2, act(D + 1), KS, nullptr, 0, 0, MCN_NSH, 0, W, 0, 0, a.grads + L.pWc2, W, a.grads + L.pBc2, 0, 0, MS});
-    // sigma.2 (1 x W): d sigma sits in column 27 of dsh, its input is the sigma hidden layer
-    add(2, Dw16Seg{dsh, 2, act(D), KS, nullptr, 0, MCN_NSH, MCN_NSH + 1, 0, W, 0, 0, a.grads + L.pWs2, W, a.grads + L.pBs2, 0, 0, 0});
-    switch (W) {
-        case 256: return dw16_launch_job<256>(job, a.count, a.rows, a.bf16, a.gmax_bits, st);
-        case 128: return dw16_launch_job<128>(job, a.count, a.rows, a.bf16, a.gmax_bits, st);
-        case 64:  return dw16_launch_job<64>(job, a.count, a.rows, a.bf16, a.gmax_bits, st);
-        case 32:  return dw16_launch_job<32>(job, a.count, a.rows, a.bf16, a.gmax_bits, st);
-        default:  return hipErrorInvalidValue;
-    }
+    const long long ntiles = mcn_passes(a.rows, 32);
+    return mcn_for_width(a.lay.width, [&](auto w) {
+        constexpr int W = decltype(w)::value;
+        constexpr int pmax = Dw16SkipMerged<W>::value ? 2 * W / 16 + MCN16_ENCKS : (2 * W / 16 > W / 16 + MCN16_ENCKS ? 2 * W / 16 : W / 16 + MCN16_ENCKS);
+        void (*kern)(Dw16Job, const int*, int, const unsigned*) = mcn16_is_bf16(a.dtype) ? dw16_stream_kernel<W, true> : dw16_stream_kernel<W, false>;
+        return mcn_launch(kern, mcn_persistent_grid(ntiles * job.n), 64 * MCN16_WAVES, (size_t)DW16_STAGES * pmax * 1024, st, job, a.count, a.rows, a.gmax_bits);
+    });
 }

@@ -5,6 +5,7 @@
 // CorseFine_NeRF.forward (model/net_block.py:67-78), eval_sh (model/net_utils.py:103-191) and the gather / scatter of
 // NeRF_Model.inference (model/mc_nerf.py:688-701).
 #include "mcnerf_16.h"
+#include "mcnerf_launch.h"
 
 template <int W>
 struct Fwd16Smem {
@@ -291,31 +292,12 @@ __global__ __launch_bounds__(64 * MCN16_WAVES, 2) void mlp16_fwd_kernel(Mcn16Fwd
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");       // ring pieces still in flight must land before the LDS is released
 }
 
-template <int W>
-static hipError_t launch_fwd16(const Mcn16FwdArgs& a, long long max_rows, hipStream_t st) {
-    using SM = Fwd16Smem<W>;
-    int dev = 0, cus = 256;
-    hipDeviceProp_t prop;
-    if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess && prop.multiProcessorCount > 0) cus = prop.multiProcessorCount;
-    long long passes = (max_rows + MCN16_ROWS - 1) / MCN16_ROWS;
-    if (passes <= 0) return hipSuccess;
-    const int grid = (int)(passes < cus ? passes : cus);
-    const bool save = a.act_ws != nullptr;
-    void (*kern)(Mcn16FwdArgs) = a.bf16 ? (save ? mlp16_fwd_kernel<W, true, true> : mlp16_fwd_kernel<W, false, true>)
-                                        : (save ? mlp16_fwd_kernel<W, true, false> : mlp16_fwd_kernel<W, false, false>);
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, SM::total);
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(64 * MCN16_WAVES), SM::total, st, a);
-    return hipGetLastError();
-}
-
 hipError_t mcn16_launch_fwd(const Mcn16FwdArgs& a, hipStream_t st) {
-    const long long max_rows = a.count ? (long long)a.max_rows : (long long)a.n_rays * a.S;
-    switch (a.lay.width) {
-        case 256: return launch_fwd16<256>(a, max_rows, st);
-        case 128: return launch_fwd16<128>(a, max_rows, st);
-        case 64:  return launch_fwd16<64>(a, max_rows, st);
-        case 32:  return launch_fwd16<32>(a, max_rows, st);
-    }
-    return hipErrorInvalidValue;
+    return mcn_for_width(a.lay.width, [&](auto w) {
+        constexpr int W = decltype(w)::value;
+        const bool save = a.act_ws != nullptr;
+        void (*kern)(Mcn16FwdArgs) = mcn16_is_bf16(a.dtype) ? (save ? mlp16_fwd_kernel<W, true, true> : mlp16_fwd_kernel<W, false, true>)
+                                                            : (save ? mlp16_fwd_kernel<W, true, false> : mlp16_fwd_kernel<W, false, false>);
+        return mcn_launch(kern, mcn_persistent_grid(mcn_passes(mcn_max_rows(a), MCN16_ROWS)), 64 * MCN16_WAVES, Fwd16Smem<W>::total, st, a);
+    });
 }

@@ -10,6 +10,7 @@
 // Every dY is also written to dy_save: it is the A operand of the weight-gradient kernel (mlp_dw.hip).
 #include "mcnerf_common.h"
 #include "mcnerf_kernels.h"
+#include "mcnerf_launch.h"
 
 template <int WIDTH>
 struct BwdSmem {
@@ -326,25 +327,9 @@ __global__ __launch_bounds__(McnGeom<WIDTH>::WN * McnGeom<WIDTH>::WM * 64, 2) vo
     }
 }
 
-template <int WIDTH>
-static hipError_t launch_bwd(const McnMlpBwdArgs& a, long long max_rows, hipStream_t st) {
-    using SM = BwdSmem<WIDTH>;
-    const int grid = (int)((max_rows + SM::MT - 1) / SM::MT);
-    if (grid <= 0) return hipSuccess;
-    auto kern = mlp_bwd_kernel<WIDTH>;
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)SM::bytes);
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(SM::NT), SM::bytes, st, a);
-    return hipGetLastError();
-}
-
 hipError_t mcn_launch_mlp_bwd(const McnMlpBwdArgs& a, hipStream_t st) {
-    const long long max_rows = a.count ? (long long)a.max_rows : (long long)a.n_rays * a.S;
-    switch (a.lay.width) {
-        case 256: return launch_bwd<256>(a, max_rows, st);
-        case 128: return launch_bwd<128>(a, max_rows, st);
-        case 64:  return launch_bwd<64>(a, max_rows, st);
-        case 32:  return launch_bwd<32>(a, max_rows, st);
-    }
-    return hipErrorInvalidValue;
+    return mcn_for_width(a.lay.width, [&](auto w) {
+        using SM = BwdSmem<decltype(w)::value>;
+        return mcn_launch(mlp_bwd_kernel<decltype(w)::value>, mcn_passes(mcn_max_rows(a), SM::MT), SM::NT, SM::bytes, st, a);
+    });
 }

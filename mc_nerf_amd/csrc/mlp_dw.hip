@@ -7,6 +7,7 @@
 // float-atomic pass at the end (>= 512 FLOP per atomic byte, far above the atomic roofline).
 // (Design notes at the kernel.)
 #include "mcnerf_kernels.h"
+#include "mcnerf_launch.h"
 
 struct DwSeg {
     const float* dY; int ldy;     // [rows][ldy], columns nbase.. are the outputs
@@ -183,55 +184,23 @@ __global__ __launch_bounds__(512) void dw_kernel(DwSeg s, const int* count, int 
     }
 }
 
-static int dw_num_cus() {
-    static int cus = 0;
-    if (!cus) {
-        int dev = 0;
-        hipDeviceProp_t prop;
-        if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess) cus = prop.multiProcessorCount;
-        if (cus <= 0) cus = 256;
-    }
-    return cus;
-}
-
-template <class Kern, class... Args>
-static hipError_t dw_launch(Kern kern, int grid, int threads, size_t lds, hipStream_t st, Args... args) {
-    if (lds > 64 * 1024) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) return e;
-    }
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(threads), lds, st, args...);
-    return hipGetLastError();
-}
-
-// one segment: exact-fp32 kernel, or the split-f16 kernel for its shape (256 x 256: first formulation, see above)
-template <int NN, int KK>
-static hipError_t launch_seg_t(const DwSeg& s, const int* count, int rows_cap, int grid, size_t lds, hipStream_t st,
-                               const unsigned int* gmax_bits, bool split16) {
-    (void)gmax_bits; (void)split16;
-    return dw_launch(dw_kernel<NN, KK>, grid, 512, lds, st, s, count, rows_cap);
-}
-
-static hipError_t launch_seg(const DwSeg& s, const int* count, int rows_cap, hipStream_t st, const unsigned int* gmax_bits = nullptr, bool split16 = false) {
-    if (rows_cap <= 0) return hipSuccess;
-    int grid = dw_num_cus();                                   // persistent: one workgroup per CU
-    const int max_wgs = (rows_cap + DW_SLAB_ROWS - 1) / DW_SLAB_ROWS;
-    if (grid > max_wgs) grid = max_wgs;
+// one segment: persistent, one workgroup per CU while there is a slab of rows for each
+static hipError_t launch_seg(const DwSeg& s, const int* count, int rows_cap, hipStream_t st) {
+    const int grid = mcn_persistent_grid(mcn_passes(rows_cap, DW_SLAB_ROWS));
     const size_t lds = (size_t)3 * DW_SLAB_ROWS * (s.N + s.K) * sizeof(float);
-#define DW_LAUNCH(NN, KK) return launch_seg_t<NN, KK>(s, count, rows_cap, grid, lds, st, gmax_bits, split16)
+    auto launch = [&](auto kern) { return mcn_launch(kern, grid, 512, lds, st, s, count, rows_cap); };
     switch (s.N * 1000 + s.K) {
-        case 256256: DW_LAUNCH(256, 256);
-        case 256064: DW_LAUNCH(256, 64);
-        case 32256:  DW_LAUNCH(32, 256);
-        case 128128: DW_LAUNCH(128, 128);
-        case 128064: DW_LAUNCH(128, 64);
-        case 32128:  DW_LAUNCH(32, 128);
-        case 64064:  DW_LAUNCH(64, 64);
-        case 32064:  DW_LAUNCH(32, 64);
-        case 32032:  DW_LAUNCH(32, 32);
-        default: return hipErrorInvalidValue;
+        case 256256: return launch(dw_kernel<256, 256>);
+        case 256064: return launch(dw_kernel<256, 64>);
+        case 32256:  return launch(dw_kernel<32, 256>);
+        case 128128: return launch(dw_kernel<128, 128>);
+        case 128064: return launch(dw_kernel<128, 64>);
+        case 32128:  return launch(dw_kernel<32, 128>);
+        case 64064:  return launch(dw_kernel<64, 64>);
+        case 32064:  return launch(dw_kernel<32, 64>);
+        case 32032:  return launch(dw_kernel<32, 32>);
     }
-#undef DW_LAUNCH
+    return hipErrorInvalidValue;
 }
 
 hipError_t mcn_launch_dw(const McnDwArgs& a, hipStream_t st) {
@@ -246,30 +215,30 @@ hipError_t mcn_launch_dw(const McnDwArgs& a, hipStream_t st) {
         const bool takes_enc = l == 0 || ((L.skip_mask >> l) & 1u);
         if (takes_enc) {                  // encoded-input columns
             DwSeg s = {dy(l), W, a.enc_save, MCN_ENCP, W, 0, W, MCN_ENCP, L.nenc, a.grads + L.pW[l], ldw, a.grads + L.pB[l]};
-            if ((e = launch_seg(s, a.count, a.rows, st, a.gmax_bits, a.split16)) != hipSuccess) return e;
+            if ((e = launch_seg(s, a.count, a.rows, st)) != hipSuccess) return e;
         }
         if (l > 0) {                      // hidden-input columns (after the 63 encoded ones at the skip layer)
             DwSeg s = {dy(l), W, act(l - 1), W, W, 0, W, W, W, a.grads + L.pW[l] + (takes_enc ? L.nenc : 0), ldw,
                        takes_enc ? nullptr : a.grads + L.pB[l]};
-            if ((e = launch_seg(s, a.count, a.rows, st, a.gmax_bits, a.split16)) != hipSuccess) return e;
+            if ((e = launch_seg(s, a.count, a.rows, st)) != hipSuccess) return e;
         }
     }
     {   // sigma.0 and sh.0 read the last trunk activation; sh.2 reads the sh hidden layer
         DwSeg s1 = {dy(D), W, act(D - 1), W, W, 0, W, W, W, a.grads + L.pWs1, W, a.grads + L.pBs1};
-        if ((e = launch_seg(s1, a.count, a.rows, st, a.gmax_bits, a.split16)) != hipSuccess) return e;
+        if ((e = launch_seg(s1, a.count, a.rows, st)) != hipSuccess) return e;
         DwSeg c1 = {dy(D + 1), W, act(D - 1), W, W, 0, W, W, W, a.grads + L.pWc1, W, a.grads + L.pBc1};
-        if ((e = launch_seg(c1, a.count, a.rows, st, a.gmax_bits, a.split16)) != hipSuccess) return e;
+        if ((e = launch_seg(c1, a.count, a.rows, st)) != hipSuccess) return e;
         // sh.2: nsh = 3 (deg + 1)^2 outputs in rows of nshp floats (32, or 64 at degree 3: two 32-column halves of the same rows)
         const int NP_ = L.nshp, NS_ = L.nsh;
         for (int half = 0; half * 32 < NP_; ++half) {
             const int real = NS_ - 32 * half < 32 ? NS_ - 32 * half : 32;
             if (real <= 0) break;
             DwSeg c2 = {a.dsh_save + 32 * half, NP_, act(D + 1), W, 32, 0, real, W, W, a.grads + L.pWc2 + (size_t)32 * half * W, W, a.grads + L.pBc2 + 32 * half};
-            if ((e = launch_seg(c2, a.count, a.rows, st, a.gmax_bits, a.split16)) != hipSuccess) return e;
+            if ((e = launch_seg(c2, a.count, a.rows, st)) != hipSuccess) return e;
         }
         // sigma.2 (1 x W): d sigma sits in the spare column nsh of dsh_save (27 at degree 2), its input is the sigma hidden layer
         DwSeg s2 = {a.dsh_save + 32 * (NS_ / 32), NP_, act(D), W, 32, NS_ % 32, NS_ % 32 + 1, W, W, a.grads + L.pWs2, W, a.grads + L.pBs2};
-        if ((e = launch_seg(s2, a.count, a.rows, st, a.gmax_bits, a.split16)) != hipSuccess) return e;
+        if ((e = launch_seg(s2, a.count, a.rows, st)) != hipSuccess) return e;
     }
     return hipSuccess;
 }

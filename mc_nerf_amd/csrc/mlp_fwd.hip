@@ -11,6 +11,7 @@
 // (bias + ReLU) is written back in place after a barrier.
 #include "mcnerf_common.h"
 #include "mcnerf_kernels.h"
+#include "mcnerf_launch.h"
 
 template <int WIDTH>
 struct FwdSmem {
@@ -328,36 +329,16 @@ __global__ __launch_bounds__(McnGeom<WIDTH>::WN * McnGeom<WIDTH>::WM * 64, 2) vo
     }
 }
 
-template <int WIDTH>
-static hipError_t launch_fwd(const McnMlpFwdArgs& a, long long max_rows, hipStream_t st) {
-    using SM = FwdSmem<WIDTH>;
-    const int grid = (int)((max_rows + SM::MT - 1) / SM::MT);
-    if (grid <= 0) return hipSuccess;
-    const bool save = a.act_save != nullptr;
-    auto kern = save ? mlp_fwd_kernel<WIDTH, true> : mlp_fwd_kernel<WIDTH, false>;
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)SM::bytes);
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(SM::NT), SM::bytes, st, a);
-    return hipGetLastError();
-}
-
 hipError_t mcn_launch_mlp_fwd(const McnMlpFwdArgs& a, hipStream_t st) {
-    const long long max_rows = a.count ? (long long)a.max_rows : (long long)a.n_rays * a.S;
-    switch (a.lay.width) {
-        case 256: return launch_fwd<256>(a, max_rows, st);
-        case 128: return launch_fwd<128>(a, max_rows, st);
-        case 64:  return launch_fwd<64>(a, max_rows, st);
-        case 32:  return launch_fwd<32>(a, max_rows, st);
-    }
-    return hipErrorInvalidValue;
+    return mcn_for_width(a.lay.width, [&](auto w) {
+        using SM = FwdSmem<decltype(w)::value>;
+        auto kern = a.act_save ? mlp_fwd_kernel<decltype(w)::value, true> : mlp_fwd_kernel<decltype(w)::value, false>;
+        return mcn_launch(kern, mcn_passes(mcn_max_rows(a), SM::MT), SM::NT, SM::bytes, st, a);
+    });
 }
 
 int mcn_mlp_tile_rows(int width) {
-    switch (width) {
-        case 256: return FwdSmem<256>::MT;
-        case 128: return FwdSmem<128>::MT;
-        case 64:  return FwdSmem<64>::MT;
-        case 32:  return FwdSmem<32>::MT;
-    }
-    return 0;
+    int rows = 0;
+    (void)mcn_for_width(width, [&](auto w) { rows = FwdSmem<decltype(w)::value>::MT; return hipSuccess; });
+    return rows;
 }

@@ -10,6 +10,7 @@
 // mlp_x3_dw.hip), scaled by the per-launch power of two SG (f16 range; derived from max|d_out|).
 // Replaces autograd through model/net_block.py:22-33, 67-78 and model/mc_nerf.py:602, 635, 690-691.
 #include "mcnerf_x3.h"
+#include "mcnerf_launch.h"
 
 #define MCNX3_BWD_PREF_MINW 256
 #include <cstdlib>
@@ -541,30 +542,10 @@ __global__ __launch_bounds__(64 * mcnx3_waves(W), mcnx3_waves(W) / 4) void mlp_x
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
 }
 
-template <int W>
-static hipError_t launch_bwd_x3(const Mcn16BwdArgs& a, long long max_rows, hipStream_t st) {
-    using SM = BwdX3Smem<W>;
-    constexpr int WAVES = mcnx3_waves(W), ROWS = 32 * WAVES;
-    int dev = 0, cus = 256;
-    hipDeviceProp_t prop;
-    if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess && prop.multiProcessorCount > 0) cus = prop.multiProcessorCount;
-    long long passes = (max_rows + ROWS - 1) / ROWS;
-    if (passes <= 0) return hipSuccess;
-    int grid = (int)(passes < cus ? passes : cus);
-    void (*kern)(Mcn16BwdArgs) = a.bf16 == 3 ? mlp_x3_bwd_kernel<W, true> : mlp_x3_bwd_kernel<W, false>;
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, SM::total);
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(64 * WAVES), SM::total, st, a);
-    return hipGetLastError();
-}
-
 hipError_t mcnx3_launch_bwd(const Mcn16BwdArgs& a, hipStream_t st) {
-    const long long max_rows = a.count ? (long long)a.max_rows : (long long)a.n_rays * a.S;
-    switch (a.lay.width) {
-        case 256: return launch_bwd_x3<256>(a, max_rows, st);
-        case 128: return launch_bwd_x3<128>(a, max_rows, st);
-        case 64:  return launch_bwd_x3<64>(a, max_rows, st);
-        case 32:  return launch_bwd_x3<32>(a, max_rows, st);
-    }
-    return hipErrorInvalidValue;
+    return mcn_for_width(a.lay.width, [&](auto w) {
+        constexpr int W = decltype(w)::value, WAVES = mcnx3_waves(W);
+        void (*kern)(Mcn16BwdArgs) = mcn16_hi_planes_only(a.dtype) ? mlp_x3_bwd_kernel<W, true> : mlp_x3_bwd_kernel<W, false>;
+        return mcn_launch(kern, mcn_persistent_grid(mcn_passes(mcn_max_rows(a), 32 * WAVES)), 64 * WAVES, BwdX3Smem<W>::total, st, a);
+    });
 }

@@ -10,20 +10,10 @@
 // piece leaves a segment).  A tile is now 2 (N + K) / 16 pieces of 1 KiB, which leaves room for only 2 tile slots in the
 // CU's 160 KiB at 256 x 256 -- so the slots are filled, consumed and freed by QUARTERS (dwx3_run).
 #include "mcnerf_x3.h"
+#include "mcnerf_launch.h"
 #include <cstdlib>
 
-struct DwX3Seg {
-    const char* dY; int ksn;      // fragment-major [tile][part][ksn][64][8]: N = 16 ksn columns
-    const char* X;  int ksk;      // fragment-major [tile][part][ksk][64][8]: K = 16 ksk columns
-    const char* X2; int ksk2;     // optional second input block (the skip layer: [hidden | encoded] in ONE pass); null / 0 otherwise
-    int n_lo, n_real;             // outputs n_lo <= n < n_real are real (row n - n_lo of dW)
-    int col, k_real;              // input k < K of X is real for k < k_real and lands in column col + k of the dW row
-    int col2, k_real2;            // input K + k of X2: column col2 + k, real for k < k_real2
-    float* dW; int ldw;
-    float* db;
-    int kmap, kmap2, nmap;        // index maps (mcnerf_common.h; 0 = none): encoded input columns of X / X2 through mcn_enc_col(k, F = kmap / kmap2),
-                                  // sh.2 output rows through mcn_sh_row(n, nmap - 16): gradients of channels / rows the net does not have are dropped
-};
+using DwX3Seg = Dw16Seg;          // (the same fields; every operand is a (hi, lo) pair of planes: [tile][part][k-step][64][8])
 
 constexpr int dwx3_pick(int N, int K, bool want_vn) {
     int bestG = 0, bestVN = 1, bestKT = 1;
@@ -283,11 +273,10 @@ __device__ __forceinline__ void dwx3_run(const DwX3Seg& sg, const int t0, const 
 }
 
 // ---- one launch per net ---------------------------------------------------------------------------------------------
-#define DWX3_MAXSEG 15
 struct DwX3Job {
     int n;
-    int shape[DWX3_MAXSEG];       // 0: W x W   1: W x 64 (encoded-input columns)   2: 32 x W (sh.2 / sigma.2 rows)   3: W x (W + 64) (skip layer)
-    DwX3Seg seg[DWX3_MAXSEG];
+    int shape[MCN16_DW_MAXSEG];       // 0: W x W   1: W x 64 (encoded-input columns)   2: 32 x W (sh.2 / sigma.2 rows)   3: W x (W + 64) (skip layer)
+    DwX3Seg seg[MCN16_DW_MAXSEG];
 };
 template <int W> struct DwX3SkipMerged { static constexpr bool value = (W == 256) || (W == 128); };
 
@@ -318,78 +307,17 @@ __global__ __launch_bounds__(64 * MCN16_WAVES) void dwx3_stream_kernel(DwX3Job j
     }
 }
 
-static int dwx3_num_cus() {
-    static int cus = 0;
-    if (!cus) {
-        int dev = 0;
-        hipDeviceProp_t prop;
-        if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess) cus = prop.multiProcessorCount;
-        if (cus <= 0) cus = 256;
-    }
-    return cus;
-}
-
-template <int W>
-static hipError_t dwx3_launch_job(const DwX3Job& job, const int* count, int rows_cap, const unsigned* gmax_bits, hipStream_t st) {
-    if (rows_cap <= 0) return hipSuccess;
-    const long long ntiles = (rows_cap + 31) / 32;
-    long long grid = dwx3_num_cus();
-    if (grid > ntiles * job.n) grid = ntiles * job.n;
-    // LDS: the largest stages x stage product over the shapes of this width
-    constexpr int KS = W / 16;
-    constexpr int p0 = 2 * (2 * KS), p1 = 2 * (KS + MCN16_ENCKS), p2 = 2 * (2 + KS), p3 = 2 * (2 * KS + MCN16_ENCKS);
-    constexpr int l0 = dwx3_slots(p0) * p0, l1 = dwx3_slots(p1) * p1, l2 = dwx3_slots(p2) * p2, l3 = DwX3SkipMerged<W>::value ? dwx3_slots(p3) * p3 : 0;
-    constexpr int lmax = (l0 > l1 ? l0 : l1) > (l2 > l3 ? l2 : l3) ? (l0 > l1 ? l0 : l1) : (l2 > l3 ? l2 : l3);
-    static_assert(lmax <= 160, "ring exceeds the CU's LDS");
-    const size_t lds = (size_t)lmax * 1024;
-    void (*kern)(DwX3Job, const int*, int, const unsigned*) = dwx3_stream_kernel<W>;
-    static bool attr_set = false;                                      // (per width instantiation)
-    if (lds > 64 * 1024 && !attr_set) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) return e;
-        attr_set = true;
-    }
-    hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(64 * MCN16_WAVES), lds, st, job, count, rows_cap, gmax_bits);
-    return hipGetLastError();
-}
-
 hipError_t mcnx3_launch_dw(const Mcn16DwArgs& a, hipStream_t st) {
-    const McnLayout& L = a.lay;
-    const int W = L.width, D = L.depth, KS = W / 16;
-    const int ME = L.nfreq == MCN_NFREQ ? 0 : L.nfreq, MS = L.sh_deg == 2 ? 0 : 16 + L.sh_deg;      // index maps (DwX3Seg)
-    auto act = [&](int slot) { return reinterpret_cast<const char*>(a.act_ws) + (size_t)slot * a.slot_bytes; };
-    auto dy = [&](int slot) { return reinterpret_cast<const char*>(a.dy_ws) + (size_t)slot * a.slot_bytes; };
-    const char* enc = reinterpret_cast<const char*>(a.enc_ws);
-    const char* dsh = reinterpret_cast<const char*>(a.dsh_ws);
-    DwX3Job job;
-    job.n = 0;
-    auto add = [&](int shape, const DwX3Seg& s) { job.shape[job.n] = shape; job.seg[job.n] = s; ++job.n; };
-    if (D + 5 > DWX3_MAXSEG) return hipErrorInvalidValue;
-    const bool merged = (W == 256 || W == 128);       // (DwX3SkipMerged)
-    for (int l = 0; l < D; ++l) {
-        const int ldw = mcn_layer_in(L, l);
-        float* dWl = a.grads + L.pW[l];
-        float* dbl = a.grads + L.pB[l];
-        if (l == 0)                       // encoded-input columns only
-            add(1, DwX3Seg{dy(l), KS, enc, MCN16_ENCKS, nullptr, 0, 0, W, 0, MCN_ENC, 0, 0, dWl, ldw, dbl, ME, 0, 0});
-        else if (l == L.skip && merged)   // [hidden | encoded] in one pass: hidden k -> column 63 + k, encoded k -> column k
-            add(3, DwX3Seg{dy(l), KS, act(l - 1), KS, enc, MCN16_ENCKS, 0, W, L.nenc, W, 0, MCN_ENC, dWl, ldw, dbl, 0, ME, 0});
-        else if (l == L.skip) {
-            add(1, DwX3Seg{dy(l), KS, enc, MCN16_ENCKS, nullptr, 0, 0, W, 0, MCN_ENC, 0, 0, dWl, ldw, dbl, ME, 0, 0});
-            add(0, DwX3Seg{dy(l), KS, act(l - 1), KS, nullptr, 0, 0, W, L.nenc, W, 0, 0, dWl, ldw, nullptr, 0, 0, 0});
-        } else
-            add(0, DwX3Seg{dy(l), KS, act(l - 1), KS, nullptr, 0, 0, W, 0, W, 0, 0, dWl, ldw, dbl, 0, 0, 0});
-    }
-    add(0, DwX3Seg{dy(D), KS, act(D - 1), KS, nullptr, 0, 0, W, 0, W, 0, 0, a.grads + L.pWs1, W, a.grads + L.pBs1, 0, 0, 0});
-    add(0, DwX3Seg{dy(D + 1), KS, act(D - 1), KS, nullptr, 0, 0, W, 0, W, 0, 0, a.grads + L.pWc1, W, a.grads + L.pBc1, 0, 0, 0});
-    add(2, DwX3Seg{dsh, 2, act(D + 1), KS, nullptr, 0, 0, MCN_NSH, 0, W, 0, 0, a.grads + L.pWc2, W, a.grads + L.pBc2, 0, 0, MS});
-    // sigma.2 (1 x W): d sigma sits in column 27 of dsh, its input is the sigma hidden layer
-    add(2, DwX3Seg{dsh, 2, act(D), KS, nullptr, 0, MCN_NSH, MCN_NSH + 1, 0, W, 0, 0, a.grads + L.pWs2, W, a.grads + L.pBs2, 0, 0, 0});
-    switch (W) {
-        case 256: return dwx3_launch_job<256>(job, a.count, a.rows, a.gmax_bits, st);
-        case 128: return dwx3_launch_job<128>(job, a.count, a.rows, a.gmax_bits, st);
-        case 64:  return dwx3_launch_job<64>(job, a.count, a.rows, a.gmax_bits, st);
-        case 32:  return dwx3_launch_job<32>(job, a.count, a.rows, a.gmax_bits, st);
-        default:  return hipErrorInvalidValue;
-    }
+    DwX3Job job{};
+    if (!mcn16_dw_job(a, job)) return hipErrorInvalidValue;
+    const long long ntiles = mcn_passes(a.rows, 32);
+    return mcn_for_width(a.lay.width, [&](auto w) {
+        constexpr int W = decltype(w)::value, KS = W / 16;
+        // LDS: the largest stages x stage product over the shapes of this width
+        constexpr int p0 = 2 * (2 * KS), p1 = 2 * (KS + MCN16_ENCKS), p2 = 2 * (2 + KS), p3 = 2 * (2 * KS + MCN16_ENCKS);
+        constexpr int l0 = dwx3_slots(p0) * p0, l1 = dwx3_slots(p1) * p1, l2 = dwx3_slots(p2) * p2, l3 = DwX3SkipMerged<W>::value ? dwx3_slots(p3) * p3 : 0;
+        constexpr int lmax = (l0 > l1 ? l0 : l1) > (l2 > l3 ? l2 : l3) ? (l0 > l1 ? l0 : l1) : (l2 > l3 ? l2 : l3);
+        static_assert(lmax <= 160, "ring exceeds the CU's LDS");
+        return mcn_launch(dwx3_stream_kernel<W>, mcn_persistent_grid(ntiles * job.n), 64 * MCN16_WAVES, (size_t)lmax * 1024, st, job, a.count, a.rows, a.gmax_bits);
+    });
 }

@@ -7,6 +7,7 @@
 // (model/net_block.py:20-35), CorseFine_NeRF.forward (model/net_block.py:67-78), eval_sh (model/net_utils.py:103-191)
 // and the gather / scatter of NeRF_Model.inference (model/mc_nerf.py:688-701).
 #include "mcnerf_x3.h"
+#include "mcnerf_launch.h"
 
 template <int W>
 struct FwdX3Smem {
@@ -388,31 +389,11 @@ __global__ __launch_bounds__(64 * mcnx3_waves(W), mcnx3_waves(W) / 4) void mlp_x
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");       // ring pieces still in flight must land before the LDS is released
 }
 
-template <int W>
-static hipError_t launch_fwd_x3(const Mcn16FwdArgs& a, long long max_rows, hipStream_t st) {
-    using SM = FwdX3Smem<W>;
-    constexpr int WAVES = mcnx3_waves(W), ROWS = 32 * WAVES;
-    int dev = 0, cus = 256;
-    hipDeviceProp_t prop;
-    if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess && prop.multiProcessorCount > 0) cus = prop.multiProcessorCount;
-    long long passes = (max_rows + ROWS - 1) / ROWS;
-    if (passes <= 0) return hipSuccess;
-    const int grid = (int)(passes < cus ? passes : cus);
-    const bool save = a.act_ws != nullptr;
-    void (*kern)(Mcn16FwdArgs) = save ? (a.bf16 == 3 ? mlp_x3_fwd_kernel<W, 2> : mlp_x3_fwd_kernel<W, 1>) : mlp_x3_fwd_kernel<W, 0>;
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, SM::total);
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(64 * WAVES), SM::total, st, a);
-    return hipGetLastError();
-}
-
 hipError_t mcnx3_launch_fwd(const Mcn16FwdArgs& a, hipStream_t st) {
-    const long long max_rows = a.count ? (long long)a.max_rows : (long long)a.n_rays * a.S;
-    switch (a.lay.width) {
-        case 256: return launch_fwd_x3<256>(a, max_rows, st);
-        case 128: return launch_fwd_x3<128>(a, max_rows, st);
-        case 64:  return launch_fwd_x3<64>(a, max_rows, st);
-        case 32:  return launch_fwd_x3<32>(a, max_rows, st);
-    }
-    return hipErrorInvalidValue;
+    return mcn_for_width(a.lay.width, [&](auto w) {
+        constexpr int W = decltype(w)::value, WAVES = mcnx3_waves(W);
+        // what the chain saves for the backward: nothing (inference), the (hi, lo) planes, or the hi planes alone
+        void (*kern)(Mcn16FwdArgs) = !a.act_ws ? mlp_x3_fwd_kernel<W, 0> : mcn16_hi_planes_only(a.dtype) ? mlp_x3_fwd_kernel<W, 2> : mlp_x3_fwd_kernel<W, 1>;
+        return mcn_launch(kern, mcn_persistent_grid(mcn_passes(mcn_max_rows(a), 32 * WAVES)), 64 * WAVES, FwdX3Smem<W>::total, st, a);
+    });
 }
