@@ -233,6 +233,38 @@ int mcnerf_select_fine(const float* w_sel, const uint32_t* wmax_bits, float thre
 int mcnerf_sample_pdf(const float* w, const float* zgrid, const float* jitter, const float* u, int N, int Sc, int I,
                       float* z_all, void* stream);
 
+/* ---- Voxel sigma cache, the coarse sampler of `coarse_sampler = "voxel"` (a sys_param key of this build; the default, "dense",
+ * evaluates the coarse net on the whole [N,Sc] grid as the reference does).  New symbols only: no existing entry point changes,
+ * MCNERF_ABI_VERSION stays 7.  The reference sketches the cache and never allocates it: query_sigma / update_sigma
+ * (model/mc_nerf.py:859-867) index a `sigma_voxels` grid that does not exist; these four entry points replace those two methods
+ * and build the (ray, sample) list + prefill that inference(..., idx_render, coarse=True) (:682-704, prefill :689-694) consumes.
+ *   vox [G,G,G] fp32: running raw (pre-softplus) coarse sigma per cell over the cube [bmin, bmax]^3; scratch [G,G,G] uint32, all
+ *   zero between calls.  Both are caller-owned device buffers like every other pointer: nothing is allocated, nothing synchronises.
+ *   2 <= G <= 1024;  s = float32(G) / float32(bmax - bmin), formed once by the caller in fp32 (there is no device division).
+ *   Cell of a point p, per axis: i = (int) min(max((p - bmin) * s, 0), G - 1) (a NaN lands in cell 0; nothing indexes outside the
+ *   grid), linear index (ix * G + iy) * G + iz.  Sample j of ray n sits at p = o + d * z, z = zgrid[j] + jitter[n] (jitter NULL = 0),
+ *   every step a separately rounded fp32 multiply or add: the cell of a sample is a pure function of its inputs.
+ *
+ * mcnerf_voxel_select: every (ray, sample) pair with vox[cell] > thresh, in torch.nonzero (row-major) order, into idx [N*Sc] (int32
+ * pairs) with the total in *count (0 is legal and leaves idx untouched); out_c [N,Sc,4] (or NULL) is pre-filled with
+ * (sigma_default, 1, 1, 1).  ray_counts / ray_offsets: int32 [N] workspaces.  No atomic decides a position. */
+int mcnerf_voxel_select(const float* vox, int G, float bmin, float s, float thresh, const float* rays_o, const float* rays_d,
+                        const float* zgrid, const float* jitter, int N, int Sc, float sigma_default, int32_t* ray_counts,
+                        int32_t* ray_offsets, int32_t* idx, int32_t* count, float* out_c, void* stream);
+/* The update rule, on the listed pairs idx[0 .. min(*count, max_rows)) (idx / count NULL: all N * Sc pairs) with the sigma of pair
+ * (n, j) read from sig_rgb[n, j, 0] (sig_rgb [N,Sc,4], the coarse net's output): for each touched cell m = max of this call's
+ * finite sigmas in it (non-finite ones are skipped), V <- (1 - beta) * V + beta * m evaluated as
+ * fadd_rn(fmul_rn(one_minus_beta, V), fmul_rn(beta, m)) with one_minus_beta = float32(1) - float32(beta) formed by the caller.
+ * Untouched cells keep their bits; the result does not depend on the order of arrival; scratch is all zero again afterwards. */
+int mcnerf_voxel_update(float* vox, uint32_t* scratch, int G, float bmin, float s, float beta, float one_minus_beta,
+                        const float* rays_o, const float* rays_d, const float* zgrid, const float* jitter, int N, int Sc,
+                        const int32_t* idx, const int32_t* count, int max_rows, const float* sig_rgb, void* stream);
+/* query_sigma (model/mc_nerf.py:859-862): out[i] = vox[cell(pts[i])], pts [M,3] -> out [M]. */
+int mcnerf_voxel_query(const float* vox, int G, float bmin, float s, const float* pts, int M, float* out, void* stream);
+/* update_sigma (model/mc_nerf.py:864-867): the update rule above on explicit points pts [M,3] with sigma [M]. */
+int mcnerf_voxel_update_points(float* vox, uint32_t* scratch, int G, float bmin, float s, float beta, float one_minus_beta,
+                               const float* pts, const float* sigma, int M, void* stream);
+
 /* The random cap of model/mc_nerf.py:630-632: idx_out[i] = idx_in[perm[i]], i < keep; *count = keep. */
 int mcnerf_cap_gather(const int32_t* idx_in, const int64_t* perm, int keep, int32_t* idx_out, int32_t* count, void* stream);
 

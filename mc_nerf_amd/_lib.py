@@ -57,6 +57,10 @@ SIGNATURES = {
     "mcnerf_composite_bwd": (_I, [_P, _P, _I, _P, _P, _P, _I, _I, _I, _P, _P, _P]),
     "mcnerf_select_fine": (_I, [_P, _P, c_float, _I, _I, _I, c_float, _P, _P, _P, _P, _P, _P]),
     "mcnerf_sample_pdf": (_I, [_P, _P, _P, _P, _I, _I, _I, _P, _P]),
+    "mcnerf_voxel_select": (_I, [_P, _I, c_float, c_float, c_float, _P, _P, _P, _P, _I, _I, c_float, _P, _P, _P, _P, _P, _P]),
+    "mcnerf_voxel_update": (_I, [_P, _P, _I, c_float, c_float, c_float, c_float, _P, _P, _P, _P, _I, _I, _P, _P, _I, _P, _P]),
+    "mcnerf_voxel_query": (_I, [_P, _I, c_float, c_float, _P, _I, _P, _P]),
+    "mcnerf_voxel_update_points": (_I, [_P, _P, _I, c_float, c_float, c_float, c_float, _P, _P, _I, _P]),
     "mcnerf_cap_gather": (_I, [_P, _P, _I, _P, _P, _P]),
     "mcnerf_cap_ws_words": (_L, []),
     "mcnerf_cap_random": (_I, [_P, _P, _I, _I, _P, _P, _P, _P, _P]),

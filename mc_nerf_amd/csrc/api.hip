@@ -2,6 +2,7 @@
 // kernel is enqueued on the caller's stream, nothing here synchronises or allocates.
 #include "../../include/mcnerf.h"
 #include "mcnerf_kernels.h"
+#include "mcnerf_voxel.h"
 #include "mcnerf_16.h"
 #include "mcnerf_x3.h"
 #include <stdio.h>
@@ -329,6 +330,36 @@ int mcnerf_sample_pdf(const float* w, const float* zgrid, const float* jitter, c
     REQ((long long)N * (Sc + I) < (1ll << 31), "mcnerf_sample_pdf");
     McnSamplePdfArgs a = {w, zgrid, jitter, u, N, Sc, I, z_all};
     return check("mcnerf_sample_pdf", mcn_launch_sample_pdf(a, (hipStream_t)stream));
+}
+// the voxel grid's geometry: 2 <= G <= 1024 cells per axis, a finite positive cells-per-unit scale
+static bool vox_ok(int G, float bmin, float s) { return G >= 2 && G <= 1024 && bmin == bmin && s > 0.f && s <= 3.0e38f; }
+int mcnerf_voxel_select(const float* vox, int G, float bmin, float s, float thresh, const float* rays_o, const float* rays_d,
+                        const float* zgrid, const float* jitter, int N, int Sc, float sigma_default, int32_t* ray_counts,
+                        int32_t* ray_offsets, int32_t* idx, int32_t* count, float* out_c, void* stream) {
+    REQ(vox && vox_ok(G, bmin, s) && rays_o && rays_d && zgrid && ray_counts && ray_offsets && idx && count && N >= 0 && Sc > 0, "mcnerf_voxel_select");
+    REQ((long long)N * Sc < (1ll << 31), "mcnerf_voxel_select");
+    McnVoxelSelectArgs a = {vox, G, bmin, s, thresh, rays_o, rays_d, zgrid, jitter, N, Sc, sigma_default, ray_counts, ray_offsets, (int2*)idx, count, out_c};
+    return check("mcnerf_voxel_select", mcn_launch_voxel_select(a, (hipStream_t)stream));
+}
+int mcnerf_voxel_update(float* vox, uint32_t* scratch, int G, float bmin, float s, float beta, float one_minus_beta,
+                        const float* rays_o, const float* rays_d, const float* zgrid, const float* jitter, int N, int Sc,
+                        const int32_t* idx, const int32_t* count, int max_rows, const float* sig_rgb, void* stream) {
+    REQ(vox && scratch && vox_ok(G, bmin, s) && rays_o && rays_d && zgrid && sig_rgb && N >= 0 && Sc > 0, "mcnerf_voxel_update");
+    REQ((idx == nullptr) == (count == nullptr) && max_rows >= 0 && (long long)N * Sc < (1ll << 31), "mcnerf_voxel_update");
+    McnVoxelUpdateArgs a = {vox, scratch, G, bmin, s, beta, one_minus_beta, nullptr, nullptr, 0, rays_o, rays_d, zgrid, jitter, N, Sc,
+                            (const int2*)idx, count, max_rows, sig_rgb};
+    return check("mcnerf_voxel_update", mcn_launch_voxel_update(a, (hipStream_t)stream));
+}
+int mcnerf_voxel_query(const float* vox, int G, float bmin, float s, const float* pts, int M, float* out, void* stream) {
+    REQ(vox && vox_ok(G, bmin, s) && pts && out && M >= 0, "mcnerf_voxel_query");
+    return check("mcnerf_voxel_query", mcn_launch_voxel_query(vox, G, bmin, s, pts, M, out, (hipStream_t)stream));
+}
+int mcnerf_voxel_update_points(float* vox, uint32_t* scratch, int G, float bmin, float s, float beta, float one_minus_beta,
+                               const float* pts, const float* sigma, int M, void* stream) {
+    REQ(vox && scratch && vox_ok(G, bmin, s) && pts && sigma && M >= 0, "mcnerf_voxel_update_points");
+    McnVoxelUpdateArgs a = {vox, scratch, G, bmin, s, beta, one_minus_beta, pts, sigma, M, nullptr, nullptr, nullptr, nullptr, 0, 0,
+                            nullptr, nullptr, 0, nullptr};
+    return check("mcnerf_voxel_update_points", mcn_launch_voxel_update(a, (hipStream_t)stream));
 }
 int mcnerf_cap_gather(const int32_t* idx_in, const int64_t* perm, int keep, int32_t* idx_out, int32_t* count, void* stream) {
     REQ(idx_in && perm && idx_out && count && keep >= 0, "mcnerf_cap_gather");

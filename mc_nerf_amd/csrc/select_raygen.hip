@@ -5,6 +5,7 @@
 //     backward: replaces MC_Model.get_rays + generate_rand_rays (model/mc_nerf.py:124-145, 213-256,
 //     327-345) for the selected pixels only.
 #include "mcnerf_kernels.h"
+#include "mcnerf_voxel.h"
 
 // ------------------------------------------------------------------ selection
 __device__ __forceinline__ float sel_threshold(const McnSelectArgs& a) {
@@ -121,6 +122,12 @@ hipError_t mcn_launch_select(const McnSelectArgs& a, hipStream_t st) {
     hipLaunchKernelGGL(select_count_kernel, g, b, 0, st, a);
     hipLaunchKernelGGL(select_scan_kernel, dim3(1), dim3(1024), 0, st, a);
     hipLaunchKernelGGL(select_write_kernel, g, b, 0, st, a);
+    return hipGetLastError();
+}
+// the scan for a caller with its own count and write kernels (voxel.hip)
+hipError_t mcn_launch_select_scan(const McnSelectArgs& a, hipStream_t st) {
+    if (a.N <= 0) return hipSuccess;
+    hipLaunchKernelGGL(select_scan_kernel, dim3(1), dim3(1024), 0, st, a);
     return hipGetLastError();
 }
 

@@ -82,9 +82,20 @@ class NeRF_Model(nn.Module):
         if self.fine_sampler == "pdf" and not (self.samples_c >= 3 and self.samples_c + self.n_importance <= ops.PDF_MAX_SAMPLES):
             raise ValueError(f"fine_sampler 'pdf' needs samples >= 3 and samples + n_importance <= {ops.PDF_MAX_SAMPLES}, "
                              f"got samples = {self.samples_c}, n_importance = {self.n_importance}")
+        # "coarse_sampler" is this build's own key too: "dense" (the reference's coarse pass on the whole [N, samples] grid; the default)
+        # or "voxel" (the coarse net on the samples in occupied cells of a [grid_nerf]^3 grid of running raw sigmas over
+        # [boader_min, boader_max]^3 -- the cache the reference sketches in query_sigma / update_sigma, :859-867, and never allocates).
+        # "voxel_beta" / "voxel_thresh" / "voxel_warmup_epoch" and the reference's grid keys are read and validated in "voxel" mode only.
+        self.coarse_sampler = sys_param.get("coarse_sampler", "dense")
+        if self.coarse_sampler not in ("dense", "voxel"):
+            raise ValueError(f"coarse_sampler must be 'dense' or 'voxel', got {self.coarse_sampler!r}")
+        self._voxels = None               # ops.VoxelGrid, allocated on first use ("voxel" mode only): not a parameter, not a buffer
+        voxel_kw = self._voxel_settings(sys_param) if self.coarse_sampler == "voxel" else {}
         self.settings = RenderSettings(self.samples_c, self.sample_scale, float(self.weight_thresh),
                                        float(self.sigma_default), bool(self.white_back), precision=self.precision,
-                                       fine_sampler=self.fine_sampler, n_importance=int(self.n_importance))
+                                       fine_sampler=self.fine_sampler, n_importance=int(self.n_importance),
+                                       coarse_sampler=self.coarse_sampler, **voxel_kw)
+        self.last_coarse_selection = None  # (idx_c, count_c) of the last pruned coarse pass; None in "dense" mode and in the warm-up
         self.last_selection = None        # (idx, count) of the last fine pass in "threshold" mode; None in "pdf" mode
         self.last_z_all = None            # the fine pass's depth rows [N, samples + n_importance] in "pdf" mode
         self.last_flat_grads = None
@@ -97,6 +108,85 @@ class NeRF_Model(nn.Module):
             self.nerf_coarse.load_state_dict(self.rewrite_nerf_ckpt(ckpt, coarse=True))
             self.nerf_fine.load_state_dict(self.rewrite_nerf_ckpt(ckpt))
             logging.info("Loading weights:{}".format(self.nerf_ckpt_name))
+            if self.coarse_sampler == "voxel":          # the grid is not in the checkpoint: built from the loaded coarse net
+                self.rebuild_voxels()
+
+    # ------------------------------------------------------------------ voxel sigma cache (:859-867)
+    def _voxel_settings(self, sys_param):
+        """Reads and validates the keys of "voxel" mode (a ValueError names the key) -> the RenderSettings fields."""
+        def number(key, default):
+            v = sys_param.get(key, default)
+            if isinstance(v, bool) or not isinstance(v, (int, float)) or v != v or v in (float("inf"), float("-inf")):
+                raise ValueError(f"{key} must be a finite number, got {v!r}")
+            return v
+        G = sys_param.get("grid_nerf")
+        if isinstance(G, bool) or not isinstance(G, int) or not 2 <= G <= 1024:
+            raise ValueError(f"grid_nerf must be an integer in [2, 1024], got {G!r}")
+        bmin, bmax = number("boader_min", None), number("boader_max", None)
+        if not bmin < bmax:
+            raise ValueError(f"boader_min must be below boader_max, got {bmin!r} and {bmax!r}")
+        self.grid_nerf, self.boader_min, self.boader_max = G, float(bmin), float(bmax)
+        self.sigma_init = float(number("sigma_init", None))
+        beta = number("voxel_beta", 0.1)
+        if not 0.0 < beta <= 1.0:
+            raise ValueError(f"voxel_beta must be in (0, 1], got {beta!r}")
+        thresh = number("voxel_thresh", 0.0)
+        warm = sys_param.get("voxel_warmup_epoch", 1)
+        if isinstance(warm, bool) or not isinstance(warm, int) or warm < 0:
+            raise ValueError(f"voxel_warmup_epoch must be an integer >= 0, got {warm!r}")
+        return dict(voxel_beta=float(beta), voxel_thresh=float(thresh), voxel_warmup_epoch=warm)
+
+    def voxel_grid(self) -> ops.VoxelGrid:
+        """The cache's two grids (allocated and filled with `sigma_init` on first use; each rank has its own)."""
+        if self.coarse_sampler != "voxel":
+            raise ops._lib.McnerfError("the voxel sigma cache exists in coarse_sampler = 'voxel' mode only")
+        if self._voxels is None:
+            self._voxels = ops.VoxelGrid(self.grid_nerf, self.boader_min, self.boader_max, self.sigma_init, self.z_vals_c.device)
+        return self._voxels
+
+    @property
+    def sigma_voxels(self) -> Optional[torch.Tensor]:
+        """[grid_nerf]^3 fp32 running raw coarse sigma ("voxel" mode), None in "dense" mode."""
+        return self.voxel_grid().vox if self.coarse_sampler == "voxel" else None
+
+    def query_sigma(self, xyz):
+        """Reference :859-862: xyz [M,3] -> the sigma of each point's cell [M]."""
+        return ops.voxel_query(self.voxel_grid(), xyz.reshape(-1, 3).float().contiguous())
+
+    def update_sigma(self, xyz, sigma, beta):
+        """Reference :864-867, with the cache's deterministic rule: per touched cell V <- (1 - beta) V + beta max(sigma in the cell)."""
+        ops.voxel_update_points(self.voxel_grid(), xyz.reshape(-1, 3).float().contiguous(), sigma.reshape(-1).float().contiguous(), beta)
+
+    def voxel_centres(self, lo: int, hi: int, device) -> torch.Tensor:
+        """Centres boader_min + (i + 1/2) (scope / G) of the cells with linear index lo .. hi-1, [hi - lo, 3] fp32."""
+        G = self.grid_nerf
+        axis = (torch.arange(G, dtype=torch.float32) + 0.5) * torch.tensor((self.boader_max - self.boader_min) / G, dtype=torch.float32) \
+            + torch.tensor(self.boader_min, dtype=torch.float32)
+        axis = axis.to(device)
+        lin = torch.arange(lo, hi, dtype=torch.int64, device=device)
+        return torch.stack([axis[lin // (G * G)], axis[(lin // G) % G], axis[lin % G]], -1).contiguous()
+
+    @torch.no_grad()
+    def rebuild_voxels(self, model_coarse=None, chunk: int = 1 << 19):
+        """V[cell] = raw sigma of the coarse net at the cell's centre, for every cell (the demo path: the grid is not in the
+        checkpoint).  Stand-alone exact-fp32 kernels (ops.encode + ops.mlp_apply) in `chunk`-cell pieces; sigma does not depend on
+        the view direction, which is fixed."""
+        grid = self.voxel_grid()
+        model = self.nerf_coarse if model_coarse is None else model_coarse
+        dev = grid.vox.device
+        net, flat = model.net, model.flat_params()
+        if flat.device != dev:              # (demo mode builds the grid at construction, before the caller's .to(device) moves the nets)
+            flat = ops.flatten_params(net, [p.detach() for p in model.ordered_parameters()], dev)
+        packed = ops.pack_weights(net, flat, precision="f32")
+        barf_w = self.emmbedding_xyz.barf_weights_on(1, dev)
+        total = self.grid_nerf ** 3
+        dirs = torch.tensor([0.0, 0.0, 1.0], device=dev).expand(min(chunk, total), 3).contiguous()
+        out = grid.vox.view(-1)
+        for lo in range(0, total, chunk):
+            hi = min(lo + chunk, total)
+            enc = ops.encode(self.voxel_centres(lo, hi, dev), barf_w)
+            out[lo:hi] = ops.mlp_apply(net, flat, packed, enc, dirs[:hi - lo])[:, 0]
+        return grid.vox
 
     # ------------------------------------------------------------------ API (:586-596)
     def forward(self, *args):
@@ -140,7 +230,9 @@ class NeRF_Model(nn.Module):
                                                     self._dev(jitter), self._dev(eps_c).contiguous(),
                                                     None if eps_sel is None else self._dev(eps_sel).contiguous(),
                                                     None if eps_f is None else self._dev(eps_f).contiguous(),
-                                                    cap_perm, self._dev(u).contiguous() if pdf else None, rays_d, rays_o, *params)
+                                                    cap_perm, self._dev(u).contiguous() if pdf else None,
+                                                    self.settings.voxel and cur_epoch >= self.settings.voxel_warmup_epoch,
+                                                    rays_d, rays_o, *params)
         if only_coarse:
             return rgb_c, None, depth_c
         return rgb_c, rgb_f
@@ -175,6 +267,8 @@ class NeRF_Model(nn.Module):
             rows_f = n_rays * st.samples_pdf
         else:
             rows_f = n_rays * (st.max_fine_per_ray if _cap_needed(st) else st.samples_f)
+        if st.voxel:
+            self.voxel_grid()                       # (the list itself has the dense pass's capacity: the pool's keys do not change)
         for net, rows in ((self.nerf_coarse.net, n_rays * st.samples_c), (self.nerf_fine.net, rows_f)):
             save = pool.take_save(net, rows, dev, st.precision)
             pool.give_grad(net, save, st.precision, pool.take_grad(net, save, st.precision))

@@ -9,6 +9,10 @@ The fine sampler is a setting (`fine_sampler`): "threshold" is the reference's w
 "pdf" draws `n_importance` depths per ray by inverse CDF from the coarse selection weights (ops.sample_pdf) and runs
 the fine net densely on the sorted [coarse + importance] depth rows (no selection, cap or default prefill).
 
+The coarse sampler is a setting too (`coarse_sampler`): "dense" is the reference's coarse pass on the whole [N,Sc] grid; "voxel" runs the
+coarse net on the (ray, sample) pairs that the owner's sigma grid lists (ops.voxel_select) over the (sigma_default, 1, 1, 1) prefill and
+keeps the grid current from every train call's evaluated samples (ops.voxel_update); rendering only queries the grid.
+
 Every random draw of the reference (jitter, the three N(0,1) tensors of sigma2weights, the cap
 permutation; in "pdf" mode the U(0,1) draws of the sampler) is an explicit tensor argument: generated with
 torch's device RNG by the caller in normal operation, passed in verbatim by the parity tests.
@@ -39,6 +43,13 @@ class RenderSettings:
     # sampling of n_importance depths per ray, the fine net evaluated on Sc + n_importance sorted depths per ray
     fine_sampler: str = "threshold"
     n_importance: int = 128
+    # "dense": the coarse net on the whole [N,Sc] grid (the reference); "voxel": on the (ray, sample) pairs whose cell of the owner's
+    # sigma grid holds a raw sigma > voxel_thresh (ops.voxel_select), the grid kept current by train calls (ops.voxel_update, rate
+    # voxel_beta); train calls with cur_epoch < voxel_warmup_epoch run the dense pass and only update the grid
+    coarse_sampler: str = "dense"
+    voxel_beta: float = 0.1
+    voxel_thresh: float = 0.0
+    voxel_warmup_epoch: int = 1
 
     @property
     def samples_f(self):
@@ -52,6 +63,10 @@ class RenderSettings:
     @property
     def pdf(self) -> bool:
         return self.fine_sampler == "pdf"
+
+    @property
+    def voxel(self) -> bool:
+        return self.coarse_sampler == "voxel"
 
 
 class WorkspacePool:
@@ -131,8 +146,10 @@ class RenderTrainFn(torch.autograd.Function):
     """rgb_c, rgb_f, depth_c = f(rays_d, rays_o, *coarse_params, *fine_params) with explicit draws."""
 
     @staticmethod
-    def forward(ctx, owner, model_c, model_f, step_r, only_coarse, jitter, eps_c, eps_sel, eps_f, cap_perm, u,
+    def forward(ctx, owner, model_c, model_f, step_r, only_coarse, jitter, eps_c, eps_sel, eps_f, cap_perm, u, prune,
                 rays_d, rays_o, *params):
+        """`prune` (read in "voxel" mode only): True = the coarse net runs on the grid's (ray, sample) list, False = the warm-up's dense
+        pass; either way the grid is then updated from the evaluated samples."""
         st: RenderSettings = owner.settings
         dev = rays_d.device
         N = rays_d.shape[0]
@@ -142,23 +159,46 @@ class RenderTrainFn(torch.autograd.Function):
         barf_w = owner.emmbedding_xyz.barf_weights_on(step_r, dev, pad=10)
         jit = jitter.reshape(-1).contiguous()
 
-        # ---- coarse pass (dense [N,Sc] grid)
+        # ---- coarse pass: the dense [N,Sc] grid, or ("voxel" mode past its warm-up) the grid's list over the default prefill
         net_c = model_c.net
         flat_c = model_c.flat_params()
         prec = st.precision
         packed_c = ops.pack_weights(net_c, flat_c, precision=prec, range_flags=model_c.range_flags(prec, dev))
-        out_c = torch.empty(N, st.samples_c, 4, dtype=torch.float32, device=dev)
-        save_c = _pool(owner).take_save(net_c, N * st.samples_c, dev, prec) if need_grad else None
-        ops.mlp_fwd(net_c, flat_c, packed_c, rays_o, rays_d, owner.z_vals_c, jit, barf_w, out_c, save=save_c, precision=prec)
+        rows_c = N * st.samples_c
+        grid = owner.voxel_grid() if st.voxel else None
+        idx_c = count_c = None
+        if grid is not None and prune:
+            idx_c, count_c, out_c = ops.voxel_select(grid, st.voxel_thresh, rays_o, rays_d, owner.z_vals_c, jit, st.sigma_default)
+        else:
+            out_c = torch.empty(N, st.samples_c, 4, dtype=torch.float32, device=dev)
+        save_c = _pool(owner).take_save(net_c, rows_c, dev, prec) if need_grad else None
+        if idx_c is None:
+            ops.mlp_fwd(net_c, flat_c, packed_c, rays_o, rays_d, owner.z_vals_c, jit, barf_w, out_c, save=save_c, precision=prec)
+        else:
+            try:
+                ops.mlp_fwd(net_c, flat_c, packed_c, rays_o, rays_d, owner.z_vals_c, jit, barf_w, out_c,
+                            idx=idx_c, count=count_c, max_rows=rows_c, save=save_c, precision=prec)
+            except BaseException:
+                if save_c is not None:                      # (no backward will give the set back)
+                    _pool(owner).give_save(net_c, save_c, prec)
+                raise
         rgb_c, depth_c, _, w_sel, wmax = ops.composite_fwd(out_c, rays_d, owner.z_vals_c, jit, eps_c,
                                                           None if only_coarse else eps_sel, st.white_back,
                                                           want_depth=only_coarse)
+        if grid is not None:
+            try:
+                ops.voxel_update(grid, st.voxel_beta, rays_o, rays_d, owner.z_vals_c, jit, out_c, idx_c, count_c, rows_c if idx_c is not None else 0)
+            except BaseException:
+                if save_c is not None:
+                    _pool(owner).give_save(net_c, save_c, prec)
+                raise
+        owner.last_coarse_selection = None if idx_c is None else (idx_c, count_c)
         ctx.only_coarse = only_coarse
         ctx.owner, ctx.model_c, ctx.model_f = owner, model_c, model_f
         ctx.n_c = len(model_c.ordered_parameters())
         if only_coarse:
             if need_grad:
-                ctx.save_for_backward(rays_d, rays_o, jit, eps_c, barf_w, out_c, flat_c, packed_c)
+                ctx.save_for_backward(rays_d, rays_o, jit, eps_c, barf_w, out_c, flat_c, packed_c, idx_c, count_c)
                 ctx.save_c = save_c
             ctx.mark_non_differentiable(depth_c)
             return rgb_c, None, depth_c
@@ -189,7 +229,7 @@ class RenderTrainFn(torch.autograd.Function):
         owner.last_z_all = z_all
         if need_grad:
             ctx.save_for_backward(rays_d, rays_o, jit, eps_c, barf_w, out_c, flat_c, packed_c,
-                                  eps_f, out_f, flat_f, packed_f, idx, count, z_all)
+                                  eps_f, out_f, flat_f, packed_f, idx, count, z_all, idx_c, count_c)
             ctx.save_c, ctx.save_f, ctx.max_rows = save_c, save_f, max_rows
         return rgb_c, rgb_f, None
 
@@ -204,9 +244,10 @@ class RenderTrainFn(torch.autograd.Function):
                                   "returned to the pool by the first backward; run the forward again")
         saved = ctx.saved_tensors
         rays_d, rays_o, jit, eps_c, barf_w, out_c, flat_c, packed_c = saved[:8]
+        idx_c, count_c = saved[-2:]                         # the coarse list of "voxel" mode, or None, None
         dev = rays_d.device
         N = rays_d.shape[0]
-        want_rays = ctx.needs_input_grad[11] or ctx.needs_input_grad[12]
+        want_rays = ctx.needs_input_grad[12] or ctx.needs_input_grad[13]
         d_od = torch.zeros(2, N, 3, dtype=torch.float32, device=dev) if want_rays else None      # (one fill for both)
         d_o, d_d = (d_od[0], d_od[1]) if want_rays else (None, None)
         # gradient buffers: slices of the step-level arena when a FlatGradSync provided one (so the whole
@@ -248,7 +289,7 @@ class RenderTrainFn(torch.autograd.Function):
         ctx.save_c = ctx.save_f = None
         ctx.workspaces_given_back = True
         if not ctx.only_coarse:
-            eps_f, out_f, flat_f, packed_f, idx, count, z_all = saved[8:]
+            eps_f, out_f, flat_f, packed_f, idx, count, z_all = saved[8:15]
             g_f = arena[n_c:n_c + n_f] if arena is not None else torch.zeros_like(flat_f)
             try:
                 net_backward(model_f, flat_f, packed_f, owner.z_vals_f, eps_f, out_f, d_rgb_f, save_f, g_f,
@@ -256,12 +297,13 @@ class RenderTrainFn(torch.autograd.Function):
             except BaseException:
                 _pool(owner).give_save(model_c.net, save_c, st.precision)      # (the coarse net's set never reaches its own backward)
                 raise
-        net_backward(model_c, flat_c, packed_c, owner.z_vals_c, eps_c, out_c, d_rgb_c, save_c, g_c)
+        net_backward(model_c, flat_c, packed_c, owner.z_vals_c, eps_c, out_c, d_rgb_c, save_c, g_c,
+                     idx=idx_c, count=count_c, max_rows=N * st.samples_c if idx_c is not None else 0)
         grads_c = model_c.grad_views(g_c)
         grads_f = model_f.grad_views(g_f) if g_f is not None else [None] * len(model_f.ordered_parameters())
         owner.last_flat_grads = (g_c, g_f)
-        return (None,) * 11 + (d_d if ctx.needs_input_grad[11] else None,
-                               d_o if ctx.needs_input_grad[12] else None) + tuple(grads_c) + tuple(grads_f)
+        return (None,) * 12 + (d_d if ctx.needs_input_grad[12] else None,
+                               d_o if ctx.needs_input_grad[13] else None) + tuple(grads_c) + tuple(grads_f)
 
 
 def render_test(owner, model_c, model_f, rays_d, rays_o, eps_c, eps_sel, eps_f, prepared=None, u=None):
@@ -281,8 +323,15 @@ def render_test(owner, model_c, model_f, rays_d, rays_o, eps_c, eps_sel, eps_f, 
                     ops.pack_weights(net_f, flat_f, precision=prec, range_flags=model_f.range_flags(prec, dev)),
                     owner.emmbedding_xyz.barf_weights_on(1, dev, pad=10))
     packed_c, packed_f, barf_w = prepared
-    out_c = torch.empty(N, st.samples_c, 4, dtype=torch.float32, device=dev)
-    ops.mlp_fwd(net_c, flat_c, packed_c, rays_o, rays_d, owner.z_vals_c, None, barf_w, out_c, precision=prec)
+    if st.voxel:                                            # query only: rendering never updates the grid
+        idx_c, count_c, out_c = ops.voxel_select(owner.voxel_grid(), st.voxel_thresh, rays_o, rays_d, owner.z_vals_c, None, st.sigma_default)
+        ops.mlp_fwd(net_c, flat_c, packed_c, rays_o, rays_d, owner.z_vals_c, None, barf_w, out_c,
+                    idx=idx_c, count=count_c, max_rows=N * st.samples_c, precision=prec)
+        owner.last_coarse_selection = (idx_c, count_c)
+    else:
+        out_c = torch.empty(N, st.samples_c, 4, dtype=torch.float32, device=dev)
+        ops.mlp_fwd(net_c, flat_c, packed_c, rays_o, rays_d, owner.z_vals_c, None, barf_w, out_c, precision=prec)
+        owner.last_coarse_selection = None
     _, _, _, w_sel, wmax = ops.composite_fwd(out_c, rays_d, owner.z_vals_c, None, eps_c, eps_sel, st.white_back)
     if st.pdf:
         z_all = ops.sample_pdf(w_sel, owner.z_vals_c, None, u)

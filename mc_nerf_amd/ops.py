@@ -474,6 +474,85 @@ def sample_pdf(w_sel: Tensor, zgrid: Tensor, jitter: Optional[Tensor], u: Tensor
     return z_all
 
 
+# --------------------------------------------------------------------------- voxel sigma cache (include/mcnerf.h: mcnerf_voxel_*)
+def _f32(x) -> Tensor:
+    return torch.tensor(float(x), dtype=torch.float32)
+
+
+def voxel_scale(G: int, bmin: float, bmax: float) -> float:
+    """Cells per unit length, s = float32(G) / float32(bmax - bmin): one fp32 division on the host."""
+    return float(_f32(G) / _f32(float(bmax) - float(bmin)))
+
+
+def voxel_blend(beta: float) -> Tuple[float, float]:
+    """(beta, 1 - beta) as the fp32 values the update kernels take (1 - beta is formed here, in fp32)."""
+    b = _f32(beta)
+    return float(b), float(_f32(1.0) - b)
+
+
+class VoxelGrid:
+    """The two device buffers of the cache and the grid's geometry: vox [G,G,G] fp32 (running raw sigma, filled with `sigma_init`),
+    scratch [G,G,G] int32 (the update kernels' uint32 words, all zero between calls), over the cube [bmin, bmax]^3."""
+
+    def __init__(self, G: int, bmin: float, bmax: float, sigma_init: float, device):
+        self.G, self.bmin, self.bmax = int(G), float(_f32(bmin)), float(bmax)
+        self.s = voxel_scale(G, bmin, bmax)
+        self.vox = torch.full((self.G,) * 3, float(sigma_init), dtype=torch.float32, device=device)
+        self.scratch = torch.zeros((self.G,) * 3, dtype=torch.int32, device=device)
+
+    @property
+    def geom(self):
+        return self.G, self.bmin, self.s
+
+
+def voxel_select(grid: VoxelGrid, thresh: float, rays_o: Tensor, rays_d: Tensor, zgrid: Tensor, jitter: Optional[Tensor],
+                 sigma_default: float, prefill: bool = True, idx: Optional[Tensor] = None):
+    """-> idx [N*Sc,2] int32 (first *count rows valid, torch.nonzero order), count [1] int32, out_c [N,Sc,4] | None: the (ray, sample)
+    pairs whose cell holds a sigma > thresh, and the (sigma_default, 1, 1, 1) prefill of the coarse pass.  No host synchronisation.
+    `idx`: the caller's own list buffer (rows beyond *count are left as they are)."""
+    N, Sc = rays_d.shape[0], zgrid.numel()
+    dev = rays_d.device
+    if idx is None:
+        idx = torch.empty(N * Sc, 2, dtype=torch.int32, device=dev)
+    elif idx.numel() < N * Sc * 2:
+        raise _lib.McnerfError(f"voxel_select: idx must hold N * Sc = {N * Sc} pairs, got {tuple(idx.shape)}")
+    count = torch.empty(1, dtype=torch.int32, device=dev)
+    rc = torch.empty(N, dtype=torch.int32, device=dev)
+    ro = torch.empty(N, dtype=torch.int32, device=dev)
+    out_c = torch.empty(N, Sc, 4, dtype=torch.float32, device=dev) if prefill else None
+    _lib.call("mcnerf_voxel_select", _p(grid.vox), *grid.geom, float(thresh), _p(rays_o), _p(rays_d), _p(zgrid), _p(jitter), N, Sc,
+              float(sigma_default), _p(rc, torch.int32), _p(ro, torch.int32), _p(idx, torch.int32), _p(count, torch.int32), _p(out_c), _stream())
+    return idx, count, out_c
+
+
+def voxel_update(grid: VoxelGrid, beta: float, rays_o: Tensor, rays_d: Tensor, zgrid: Tensor, jitter: Optional[Tensor], sig_rgb: Tensor,
+                 idx: Optional[Tensor] = None, count: Optional[Tensor] = None, max_rows: int = 0) -> None:
+    """The update rule on the listed (ray, sample) pairs (idx None: all N * Sc) with sigma = sig_rgb[n, j, 0]: per touched cell
+    V <- (1 - beta) V + beta max(sigma), deterministic in the order of arrival; grid.scratch is all zero again afterwards."""
+    N, Sc = rays_d.shape[0], zgrid.numel()
+    if sig_rgb.numel() != N * Sc * 4 or (jitter is not None and jitter.numel() != N):
+        raise _lib.McnerfError(f"voxel_update: sig_rgb must be [N = {N}, Sc = {Sc}, 4], got {tuple(sig_rgb.shape)}")
+    _lib.call("mcnerf_voxel_update", _p(grid.vox), _p(grid.scratch, torch.int32), *grid.geom, *voxel_blend(beta), _p(rays_o), _p(rays_d),
+              _p(zgrid), _p(jitter), N, Sc, _p(idx, torch.int32), _p(count, torch.int32), int(max_rows), _p(sig_rgb), _stream())
+
+
+def voxel_query(grid: VoxelGrid, xyz: Tensor) -> Tensor:
+    """query_sigma (model/mc_nerf.py:859-862): xyz [M,3] -> the cells' sigma [M]."""
+    M = xyz.shape[0]
+    out = torch.empty(M, dtype=torch.float32, device=xyz.device)
+    _lib.call("mcnerf_voxel_query", _p(grid.vox), *grid.geom, _p(xyz), M, _p(out), _stream())
+    return out
+
+
+def voxel_update_points(grid: VoxelGrid, xyz: Tensor, sigma: Tensor, beta: float) -> None:
+    """update_sigma (model/mc_nerf.py:864-867): the update rule on explicit points xyz [M,3] with sigma [M]."""
+    M = xyz.shape[0]
+    if sigma.numel() != M:
+        raise _lib.McnerfError(f"voxel_update_points: xyz [M,3] {tuple(xyz.shape)}, sigma [M] {tuple(sigma.shape)}")
+    _lib.call("mcnerf_voxel_update_points", _p(grid.vox), _p(grid.scratch, torch.int32), *grid.geom, *voxel_blend(beta), _p(xyz), _p(sigma),
+              M, _stream())
+
+
 def cap_gather(idx: Tensor, perm: Tensor, keep: int):
     idx2 = torch.empty(keep, 2, dtype=torch.int32, device=idx.device)
     count = torch.empty(1, dtype=torch.int32, device=idx.device)
