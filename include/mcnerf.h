@@ -287,6 +287,35 @@ int mcnerf_sample_perm(int64_t* out, long long n, int batch, const uint32_t* see
  * pix [n] int64 -> out [n,3] fp32.  Replaces the per-step H2D image copy + gather (model/mc_nerf.py:379, 80). */
 int mcnerf_gather_gt(const uint8_t* image, int channels, const int64_t* pix, int n, float* out, void* stream);
 
+/* ---- The ray preamble of a MULTI-CAMERA train step (`cams_per_step` > 1, a sys_param key of this build; the default, 1, runs the
+ * three single-camera entry points mcnerf_sample_perm / mcnerf_raygen_fwd / mcnerf_gather_gt as before).  New symbols only:
+ * MCNERF_ABI_VERSION stays 7.  The reference has no such step (it ships one float image per step through its loader).
+ *
+ * A batch of n rays is K SEGMENTS of consecutive rays: segment k = rays [seg_start[k], seg_start[k+1]) of camera seg_cam[k].
+ * seg_cam [K] and seg_start [K+1] are HOST arrays; the table is copied into the kernel arguments (no host-device copy, no host
+ * synchronisation).  Refused (before any device work): K < 1, K > 64, a camera id outside [0, C), a decreasing seg_start,
+ * seg_start[0] != 0, seg_start[K] != n, a segment longer than H * W when the pixels are drawn, channels not 3 or 4 with images.
+ * A camera may be listed more than once, in any order.
+ *
+ * mcnerf_ray_batch_fwd: ONE launch for the whole preamble.  Replaces MC_Model.get_rays + generate_rand_rays and the ground-truth
+ * gather (model/mc_nerf.py:124-145, 327-345, 379, 80) for a batch that spans cameras.  pose [C,3,4], kinv [C,3,3]; per ray i of
+ * segment k:
+ *   pixel  pix_in NULL: P_k(i - seg_start[k]), P_k the permutation of [0, H * W) of mcnerf_sample_perm keyed by
+ *          *seed + k * 0x9E3779B9 (mod 2^32): segment 0 draws exactly what mcnerf_sample_perm draws from the same word, every
+ *          segment's ids are distinct, two segments of one camera draw independently;  otherwise pix_in[i].  Written to pix_out [n];
+ *   ray    rays_d / rays_o [n,3] from pose[seg_cam[k]], kinv[seg_cam[k]]: the bits of mcnerf_raygen_fwd for that camera and pixel;
+ *   gt     images NULL: not written (gt may be NULL);  otherwise images [C, H*W, channels] uint8 -> gt [n,3], the bits of
+ *          mcnerf_gather_gt on images[seg_cam[k]]. */
+int mcnerf_ray_batch_fwd(const float* pose, const float* kinv, int C, const int32_t* seg_cam, const int32_t* seg_start, int K,
+                         int n, int H, int W, const int64_t* pix_in, const uint32_t* seed, const uint8_t* images, int channels,
+                         int64_t* pix_out, float* rays_d, float* rays_o, float* gt, void* stream);
+/* Backward of the above (autograd through model/mc_nerf.py:124-145, 327-345): d_rays_d, d_rays_o [n,3] and the forward's pixels
+ * pix [n] -> ACCUMULATES into d_pose [C,3,4] and d_kinv [C,3,3] (caller zeroes them: rows of cameras not in the table stay zero, a
+ * camera listed in two segments receives the sum).  mcnerf_raygen_bwd's per-ray terms, summed in another order (float atomics). */
+int mcnerf_ray_batch_bwd(const float* pose, const float* kinv, int C, const int32_t* seg_cam, const int32_t* seg_start, int K,
+                         int n, int W, const int64_t* pix, const float* d_rays_d, const float* d_rays_o,
+                         float* d_pose, float* d_kinv, void* stream);
+
 /* Fused camera parametrisation of all C cameras.
  * Replaces add_weights2intr / add_weights2pose / add_weights2calib_pose / se3_to_SE3 / taylor_A,B,C /
  * inverse_intrinsic (model/mc_nerf.py:171-210, 269-316) and the calibration reprojection branch get_reproject_pixels /

@@ -3,6 +3,7 @@
 #include "../../include/mcnerf.h"
 #include "mcnerf_kernels.h"
 #include "mcnerf_voxel.h"
+#include "mcnerf_multicam.h"
 #include "mcnerf_16.h"
 #include "mcnerf_x3.h"
 #include <stdio.h>
@@ -99,6 +100,47 @@ int mcnerf_raygen_bwd(const float* pose, const float* kinv, const int64_t* pix, 
     REQ(pose && kinv && pix && d_rays_d && d_rays_o && d_pose && d_kinv && n >= 0 && W > 0, "mcnerf_raygen_bwd");
     McnRaygenBwdArgs a = {pose, kinv, (const long long*)pix, n, W, d_rays_d, d_rays_o, d_pose, d_kinv};
     return check("mcnerf_raygen_bwd", mcn_launch_raygen_bwd(a, (hipStream_t)stream));
+}
+
+// The host-side segment table of a multi-camera ray batch, validated and copied into the by-value kernel argument.  Everything is
+// checked before any HIP call (a bad table is refused on a machine without a GPU too).  max_seg: the longest segment allowed
+// (H * W when the pixels are drawn without replacement, n otherwise).
+static int fill_segments(const char* name, McnSegTable& t, const int32_t* seg_cam, const int32_t* seg_start, int K, int C, int n, long long max_seg) {
+    REQ(seg_cam && seg_start, name);
+    REQ(K >= 1 && K <= MCN_MULTICAM_MAXSEG, name);
+    REQ(C >= 1 && n >= 0 && n <= (1 << 29), name);
+    REQ(seg_start[0] == 0 && seg_start[K] == n, name);
+    t.K = K;
+    for (int k = 0; k < K; ++k) {
+        REQ(seg_cam[k] >= 0 && seg_cam[k] < C, name);
+        REQ(seg_start[k + 1] >= seg_start[k], name);
+        REQ((long long)seg_start[k + 1] - seg_start[k] <= max_seg, name);
+        t.cam[k] = seg_cam[k]; t.start[k] = seg_start[k];
+    }
+    t.start[K] = n;
+    return 0;
+}
+
+int mcnerf_ray_batch_fwd(const float* pose, const float* kinv, int C, const int32_t* seg_cam, const int32_t* seg_start, int K,
+                         int n, int H, int W, const int64_t* pix_in, const uint32_t* seed, const uint8_t* images, int channels,
+                         int64_t* pix_out, float* rays_d, float* rays_o, float* gt, void* stream) {
+    REQ(H > 0 && W > 0 && (long long)H * W <= (1ll << 31), "mcnerf_ray_batch_fwd");
+    McnSegTable t = {};
+    if (int rc = fill_segments("mcnerf_ray_batch_fwd", t, seg_cam, seg_start, K, C, n, pix_in ? (long long)n : (long long)H * W)) return rc;
+    REQ(!images || channels == 3 || channels == 4, "mcnerf_ray_batch_fwd");
+    REQ(pose && kinv && pix_out && rays_d && rays_o && (pix_in || seed) && (!images || gt), "mcnerf_ray_batch_fwd");
+    McnRayBatchArgs a = {pose, kinv, (const long long*)pix_in, seed, images, channels, n, H, W, (long long*)pix_out, rays_d, rays_o, gt};
+    return check("mcnerf_ray_batch_fwd", mcn_launch_ray_batch_fwd(a, t, (hipStream_t)stream));
+}
+int mcnerf_ray_batch_bwd(const float* pose, const float* kinv, int C, const int32_t* seg_cam, const int32_t* seg_start, int K,
+                         int n, int W, const int64_t* pix, const float* d_rays_d, const float* d_rays_o,
+                         float* d_pose, float* d_kinv, void* stream) {
+    REQ(W > 0, "mcnerf_ray_batch_bwd");
+    McnSegTable t = {};
+    if (int rc = fill_segments("mcnerf_ray_batch_bwd", t, seg_cam, seg_start, K, C, n, n)) return rc;
+    REQ(pose && kinv && pix && d_rays_d && d_rays_o && d_pose && d_kinv, "mcnerf_ray_batch_bwd");
+    McnRayBatchBwdArgs a = {pose, kinv, (const long long*)pix, W, d_rays_d, d_rays_o, d_pose, d_kinv};
+    return check("mcnerf_ray_batch_bwd", mcn_launch_ray_batch_bwd(a, t, (hipStream_t)stream));
 }
 
 int mcnerf_mlp_fwd(int depth, int width, int skip, const float* params, const float* packed,

@@ -52,6 +52,16 @@ def shard_cameras(num_cams: int, epoch: int, rank: int, world: int, seed: int = 
     return order[rank:total:world]
 
 
+def group_cameras(ids: List[int], k: int) -> List[tuple]:
+    """The camera ids of `shard_cameras` as the K-tuples of multi-camera steps (`cams_per_step` = k): consecutive ids, the last
+    tuple padded by wrapping round to the start of the list.  Every id appears; ranks with equally long shards (what
+    `shard_cameras` deals) take the same number of steps."""
+    if isinstance(k, bool) or not isinstance(k, int) or k < 1:
+        raise ValueError(f"group_cameras needs an integer k >= 1, got {k!r}")
+    n = len(ids)
+    return [tuple(ids[(g * k + j) % n] for j in range(k)) for g in range((n + k - 1) // k)]
+
+
 class FlatGradSync:
     """One-collective gradient averaging for MC_Model.
 

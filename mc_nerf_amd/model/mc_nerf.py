@@ -23,7 +23,7 @@ import torch.distributed as dist
 from .. import ops
 from ..data import DeviceImageSet
 from .net_block import CorseFine_NeRF, SinCosEmbedding
-from .render import CameraFn, RaygenFn, RenderSettings, RenderTrainFn, render_test
+from .render import CameraFn, RayBatchFn, RaygenFn, RenderSettings, RenderTrainFn, render_test
 
 
 def _rank():
@@ -492,6 +492,16 @@ class MC_Model(nn.Module):
         self.mode = sys_param["mode"]
         self.device = sys_param["device_type"]
         self.batch = sys_param["batch"]
+        # "cams_per_step" is this build's own sys_param key (absent in the reference's config): the number K of cameras whose rays share
+        # one NeRF-stage train step.  1 (the default) is the reference's step, one camera; K > 1 splits the batch into K segments of
+        # consecutive rays, one camera each, through the fused ray-batch kernel (RayBatchFn)
+        self.cams_per_step = sys_param.get("cams_per_step", 1)
+        k = self.cams_per_step
+        if isinstance(k, bool) or not isinstance(k, int) or not 1 <= k <= ops.MULTICAM_MAXSEG or k > self.batch:
+            raise ValueError(f"cams_per_step must be an integer in [1, min({ops.MULTICAM_MAXSEG}, batch = {self.batch})], got {k!r}")
+        self.last_step_segments = None    # (camera ids, seg_start) of the last multi-camera step
+        self.last_step_pix = None         # its pixel ids [batch]
+        self._seg_index = None            # segment of every ray (device int64 [batch]; host float stacks only), built once
         self.intr = sys_param["intr_mat"]
         self.intr_inv = sys_param["intr_mat_inv"]
         # the constant intrinsics live on the device from the start (a per-step .to(device) of a host tensor is a
@@ -535,7 +545,9 @@ class MC_Model(nn.Module):
             t if isinstance(t, DeviceImageSet) or i == 1 else t.to(self.device) for i, t in enumerate(data)]
         loss_dict = {}
         emb = self.nerf.emmbedding_xyz
-        if epoch_type == "CAM_PARAM_EPOCH":
+        if self.cams_per_step > 1 and epoch_type != "CAM_PARAM_EPOCH":
+            self._forward_train_multi(data, images, gt_rgbs, intr_wpts, intr_pts, epoch, epoch_type, cur_ratio, loss_dict)
+        elif epoch_type == "CAM_PARAM_EPOCH":
             emb.barf_mode = False
             self.intr_adj, self.pose_adj, self.calib_pose_adj = self.add_weights2param(True, True, True, intr_wpts, extr_wpts)
             loss_dict["intr"] = [self._reproject(intr_wpts, self.intr_adj, self.calib_pose_adj, 0), intr_pts]
@@ -563,6 +575,41 @@ class MC_Model(nn.Module):
         pose_show = [self.gt_pose.detach(), self.pose_adj.detach()]
         self.last_epoch_type = epoch_type
         return loss_dict, intr_show, pose_show, rays_valid
+
+    def _forward_train_multi(self, data, images, gt_rgbs, intr_wpts, intr_pts, epoch, epoch_type, cur_ratio, loss_dict):
+        """The NeRF-stage step of `cams_per_step` = K > 1: `data[1]` holds K camera ids (duplicates allowed); the batch is K segments
+        of consecutive rays (`ops.ray_segments`), segment k of camera k, and pixels, rays and ground truth of all of them come from
+        ONE launch (RayBatchFn) that reads `pose_adj [C,3,4]` / `intr_inv_adj [C,3,3]` of all cameras as CameraFn left them.  The
+        renderer and the loss see an ordinary [batch] ray set."""
+        K = self.cams_per_step
+        cams = [int(c) for c in data[1].reshape(-1).tolist()]
+        if len(cams) != K:
+            raise ValueError(f"cams_per_step = {K}: data[1] must hold exactly {K} camera ids, got {len(cams)}")
+        if intr_wpts.shape[0] == K:        # a loader that batches K items stacks the (identical) calibration tensors K times
+            intr_wpts, intr_pts = intr_wpts[:1], intr_pts[:1]
+        joint = epoch_type == "GLOBAL_OPTIM_EPOCH"
+        self.nerf.emmbedding_xyz.barf_mode = joint
+        self.intr_adj, self.pose_adj, self.calib_pose_adj = self.add_weights2param(True, joint, True, intr_wpts, None)
+        loss_dict["intr"] = [self._reproject(intr_wpts, self.intr_adj, self.calib_pose_adj, 0), intr_pts]
+        kinv_all = self.intr_inv_adj if self.intr_inv_adj is not None else self.inverse_intrinsic(self.intr_adj)
+        seg_start = ops.ray_segments(self.batch, K)
+        pix_in = self.sample_pixels_multi(self.img_h * self.img_w, seg_start)
+        pix, rays_d, rays_o, gt = RayBatchFn.apply(self.pose_adj, kinv_all, cams, seg_start, self.img_h, self.img_w,
+                                                   images.images if images is not None else None, pix_in)
+        rgbs_c, rgbs_f = self.nerf(rays_d, rays_o, epoch, cur_ratio if joint else 1)
+        if gt is None:                     # host float stack [K,H,W,3] / [K,H*W,3]: item k is the image of segment k
+            if self._seg_index is None:
+                self._seg_index = ops.ray_segment_index(self.batch, K, pix.device)
+            gt = gt_rgbs.reshape(K, -1, 3)[self._seg_index, pix]
+        loss_dict["rgb"] = [rgbs_c, rgbs_f, gt]
+        self.opt_idx = 1 if joint else 2
+        self.last_step_segments, self.last_step_pix = (cams, seg_start), pix
+
+    def sample_pixels_multi(self, npix, seg_start):
+        """Hook of the multi-camera step: pixel ids [batch] to inject (segment k's at [seg_start[k], seg_start[k+1])), or None (the
+        default) = every segment draws its own subset without replacement on the device, inside the fused kernel; parity tests
+        replace this method."""
+        return None
 
     def sample_pixels(self, npix):
         """The step's pixel subset, randperm(npix)[:batch] of the reference (:329): on the GPU one kernel

@@ -369,6 +369,30 @@ class RaygenFn(torch.autograd.Function):
         return d_pose, d_kinv, None, None
 
 
+class RayBatchFn(torch.autograd.Function):
+    """pix, rays_d, rays_o, gt = f(pose[C,3,4], kinv[C,3,3]) for a batch of K segments of consecutive rays, segment k of camera
+    seg_cam[k] (`cams_per_step` > 1: ops.ray_batch_fwd, one launch).  Differentiable wrt pose and kinv; `pix` (injected, or drawn on
+    the device when None) and `gt` (from `images` [C, H*W, 3|4] uint8, None without) are non-differentiable outputs."""
+
+    @staticmethod
+    def forward(ctx, pose, kinv, seg_cam, seg_start, H, W, images=None, pix=None, seed=None):
+        pose = pose.contiguous().float()
+        kinv = kinv.contiguous().float()
+        pix, d, o, gt = ops.ray_batch_fwd(pose, kinv, seg_cam, seg_start, H, W, images=images,
+                                          pix=None if pix is None else pix.contiguous(), seed=seed)
+        ctx.save_for_backward(pose, kinv, pix)
+        ctx.table = (list(seg_cam), list(seg_start), W)
+        ctx.mark_non_differentiable(*(t for t in (pix, gt) if t is not None))
+        return pix, d, o, gt
+
+    @staticmethod
+    def backward(ctx, _g_pix, g_d, g_o, _g_gt):
+        pose, kinv, pix = ctx.saved_tensors
+        seg_cam, seg_start, W = ctx.table
+        d_pose, d_kinv = ops.ray_batch_bwd(pose, kinv, seg_cam, seg_start, W, pix, g_d.contiguous(), g_o.contiguous())
+        return d_pose, d_kinv, None, None, None, None, None, None, None
+
+
 class CameraFn(torch.autograd.Function):
     """K, Kinv, pose, calib_pose, pix_intr, pix_extr = f(weights_pose, weights_pose_intr, weights_fx, weights_fy, weights_ux,
     weights_uy; calibration world points) for all cameras in one fused kernel each way (reference: model/mc_nerf.py:171-210,

@@ -312,6 +312,77 @@ def sample_perm(n: int, batch: int, device, seed: Optional[Tensor] = None) -> Te
     return out
 
 
+MULTICAM_MAXSEG = 64        # MCN_MULTICAM_MAXSEG
+
+
+def ray_segments(batch: int, K: int):
+    """seg_start [K+1] of a `batch`-ray step over K cameras: segment k holds n_k = batch // K + (1 if k < batch % K else 0)
+    consecutive rays (sizes differ by at most one and sum to batch)."""
+    batch, K = int(batch), int(K)
+    if K < 1 or batch < 0:
+        raise ValueError(f"ray_segments needs K >= 1 and batch >= 0, got batch = {batch}, K = {K}")
+    q, r = divmod(batch, K)
+    start = [0]
+    for k in range(K):
+        start.append(start[-1] + q + (1 if k < r else 0))
+    return start
+
+
+def ray_segment_index(batch: int, K: int, device) -> Tensor:
+    """The segment of every ray of `ray_segments(batch, K)` as a device int64 [batch], from arithmetic on an arange: no host ->
+    device copy of a table and no host synchronisation (the first r = batch % K segments hold q + 1 rays, the others q)."""
+    q, r = divmod(int(batch), int(K))
+    i = torch.arange(int(batch), dtype=torch.int64, device=device)
+    head = r * (q + 1)
+    return torch.where(i < head, i // (q + 1), r + (i - head) // max(q, 1))
+
+
+def _seg_arrays(seg_cam, seg_start):
+    import ctypes
+    cams, start = [int(c) for c in seg_cam], [int(s) for s in seg_start]
+    if len(start) != len(cams) + 1:
+        raise _lib.McnerfError(f"seg_start must hold len(seg_cam) + 1 = {len(cams) + 1} entries, got {len(start)}")
+    return (ctypes.c_int32 * len(cams))(*cams), (ctypes.c_int32 * len(start))(*start), len(cams), start[-1]
+
+
+def ray_batch_fwd(pose: Tensor, kinv: Tensor, seg_cam, seg_start, H: int, W: int, images: Optional[Tensor] = None,
+                  pix: Optional[Tensor] = None, seed: Optional[Tensor] = None):
+    """The ray preamble of a multi-camera step in one launch.  pose [C,3,4], kinv [C,3,3]; segment k = rays
+    [seg_start[k], seg_start[k+1]) of camera seg_cam[k] (host lists; they travel as kernel arguments).  `pix` [n] int64 injects the
+    pixels; otherwise segment k draws the permutation of `sample_perm` keyed by seed + k * 0x9E3779B9 (`seed`: a device int32 word,
+    drawn from torch's device generator when not given, as `sample_perm` does).  `images` [C, H*W, 3|4] uint8 on the device gives the
+    ground truth.  -> (pix [n] int64, rays_d [n,3], rays_o [n,3], gt [n,3] | None)"""
+    cams, start, K, n = _seg_arrays(seg_cam, seg_start)
+    dev = pose.device
+    if pix is None and seed is None and pose.is_cuda:
+        seed = torch.randint(0, 2 ** 31 - 1, (1,), dtype=torch.int32, device=dev)
+    if pix is not None and pix.numel() != n:
+        raise _lib.McnerfError(f"pix must hold seg_start[-1] = {n} ids, got {pix.numel()}")
+    if images is not None and (images.dim() != 3 or images.shape[0] != pose.shape[0] or images.shape[1] != H * W):
+        raise _lib.McnerfError(f"images must be [C = {pose.shape[0]}, H*W = {H * W}, channels], got {tuple(images.shape)}")
+    pix_out = torch.empty(n, dtype=torch.int64, device=dev)
+    d = torch.empty(n, 3, dtype=torch.float32, device=dev)
+    o = torch.empty_like(d)
+    gt = torch.empty_like(d) if images is not None else None
+    _lib.call("mcnerf_ray_batch_fwd", _p(pose), _p(kinv), int(pose.shape[0]), cams, start, K, n, int(H), int(W),
+              _p(pix, torch.int64), _p(seed, torch.int32), _p(images, torch.uint8), int(images.shape[-1]) if images is not None else 0,
+              _p(pix_out, torch.int64), _p(d), _p(o), _p(gt), _stream())
+    return pix_out, d, o, gt
+
+
+def ray_batch_bwd(pose: Tensor, kinv: Tensor, seg_cam, seg_start, W: int, pix: Tensor, d_d: Tensor, d_o: Tensor) -> Tuple[Tensor, Tensor]:
+    """Backward of `ray_batch_fwd`: -> (d_pose [C,3,4], d_kinv [C,3,3]); rows of cameras not in the table are exactly zero."""
+    cams, start, K, n = _seg_arrays(seg_cam, seg_start)
+    C = int(pose.shape[0])
+    z = torch.zeros(C * 21, dtype=torch.float32, device=pose.device)     # (one fill for both accumulation targets)
+    d_pose, d_kinv = z[:C * 12].view(C, 3, 4), z[C * 12:].view(C, 3, 3)
+    if pix.numel() != n or d_d.numel() != 3 * n or d_o.numel() != 3 * n:
+        raise _lib.McnerfError(f"pix / d_rays_d / d_rays_o must hold seg_start[-1] = {n} rays")
+    _lib.call("mcnerf_ray_batch_bwd", _p(pose), _p(kinv), C, cams, start, K, n, int(W), _p(pix, torch.int64),
+              _p(d_d), _p(d_o), _p(d_pose), _p(d_kinv), _stream())
+    return d_pose, d_kinv
+
+
 def upload_f32(host_vals: Tensor, device) -> Tensor:
     """A small fp32 host tensor (<= 16 values) as a fresh device tensor, stream-ordered and without a host-device copy
     (the values travel as kernel arguments): the host never waits for the kernels already queued."""

@@ -1,7 +1,8 @@
 """Joint camera + radiance-field optimisation (the GLOBAL_OPTIM stage of MC-NeRF, BARF mask on) on the procedural scene of
 train_procedural.py, through MC_Model: device-resident uint8 images, fused camera kernels, HIP renderer, fused RAdam.
 Cameras start from the ground truth perturbed by `noise` in se(3) (rad / scene units); reports camera errors and PSNR.
-Usage (GPU box):  python scripts/train_joint.py [f32|f16x3] [steps] [noise]
+Usage (GPU box):  python scripts/train_joint.py [f32|f16x3] [steps] [noise] [cams_per_step]
+`cams_per_step` (default 1): cameras whose rays share one step (the multi-camera step of DESIGN.md 4c); the batch stays N rays.
 """
 import math, os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -13,6 +14,7 @@ from mc_nerf_amd.model import MC_Model, RAdam, MC_NeRF_Loss
 precision = sys.argv[1] if len(sys.argv) > 1 else "f16x3"
 steps = int(sys.argv[2]) if len(sys.argv) > 2 else 3000
 noise = float(sys.argv[3]) if len(sys.argv) > 3 else 0.02
+cams_per_step = int(sys.argv[4]) if len(sys.argv) > 4 else 1
 dev = torch.device("cuda:0")
 H = W = 200
 N = 8192
@@ -35,7 +37,8 @@ def render_gt(d, o, near=1.0, far=8.0, S_=384):
     return (wt.unsqueeze(-1) * col).sum(1) + (1 - wt.sum(1, keepdim=True))
 
 
-sp = S.make_sys_param(dev, samples=64, scale=2, batch=N, H=H, W=W, barf_mask=True, precision=precision)
+sp = S.make_sys_param(dev, samples=64, scale=2, batch=N, H=H, W=W, barf_mask=True, precision=precision,
+                      **({"cams_per_step": cams_per_step} if cams_per_step > 1 else {}))
 pose_gt, K_gt = sp["gt_pose"].to(dev), sp["intr_mat"][0].to(dev)
 Kinv_gt = torch.linalg.inv(K_gt)
 C = pose_gt.shape[0]
@@ -78,13 +81,13 @@ def report(tag):
           f"{float((c_e - c_g).norm(dim=-1).mean()):.4f}, focal error {float(foc) * 100:.2f} %, PSNR {sum(ps) / len(ps):.2f} dB")
 
 
-print(f"precision {precision}, {C} cameras {H}x{W}, se(3) noise {noise}, {N} rays/step, GLOBAL_OPTIM (BARF 0.1 -> 0.5 of the run)")
+print(f"precision {precision}, {C} cameras {H}x{W}, se(3) noise {noise}, {N} rays/step over {cams_per_step} camera(s), GLOBAL_OPTIM (BARF 0.1 -> 0.5 of the run)")
 report("step     0")
 t0 = time.time()
 sp_b = (sp["barf_start"], sp["barf_end"])
 for step in range(1, steps + 1):
-    cam = int(torch.randint(C, (1,)))
-    data = (images, torch.tensor([cam]), wpts, pts, wpts, pts)
+    cams = torch.randint(C, (cams_per_step,))
+    data = (images, cams, wpts, pts, wpts, pts)
     # progress ratio mapped so that the BARF window [barf_start, barf_end] covers 10 % .. 50 % of this run
     prog = step / steps
     ratio = sp_b[0] + (sp_b[1] - sp_b[0]) * min(max((prog - 0.1) / 0.4, 0.0), 1.0) if prog > 0.1 else 0.0
