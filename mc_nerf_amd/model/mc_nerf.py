@@ -23,11 +23,19 @@ import torch.distributed as dist
 from .. import ops
 from ..data import DeviceImageSet
 from .net_block import CorseFine_NeRF, SinCosEmbedding
-from .render import CameraFn, RayBatchFn, RaygenFn, RenderSettings, RenderTrainFn, render_test
+from .render import CameraFn, RayBatchFn, RaygenFn, Rays, RenderCall, RenderSettings, RenderTrainFn, SamplePass, _pool, render_test, run_pass
 
 
 def _rank():
     return dist.get_rank() if dist.is_available() and dist.is_initialized() else 0
+
+
+def _int_key(sys_param, key, default, lo, hi=None, text=None):
+    """sys_param[key] (`default` without one) when it is an integer, not a bool, in [lo, hi]; else a ValueError that names the key."""
+    v = sys_param.get(key, default)
+    if isinstance(v, bool) or not isinstance(v, int) or v < lo or (hi is not None and v > hi):
+        raise ValueError(f"{key} must be an integer {text or (f'>= {lo}' if hi is None else f'in [{lo}, {hi}]')}, got {v!r}")
+    return v
 
 
 # ============================================================================ renderer
@@ -74,11 +82,9 @@ class NeRF_Model(nn.Module):
         # reference's weight-threshold refinement, :613-632; the default) or "pdf" (inverse-CDF hierarchical sampling of
         # n_importance depths per ray from the coarse weights, the fine net evaluated on the Sc + n_importance sorted depths)
         self.fine_sampler = sys_param.get("fine_sampler", "threshold")
-        self.n_importance = sys_param.get("n_importance", 128)
         if self.fine_sampler not in ("threshold", "pdf"):
             raise ValueError(f"fine_sampler must be 'threshold' or 'pdf', got {self.fine_sampler!r}")
-        if isinstance(self.n_importance, bool) or not isinstance(self.n_importance, int) or self.n_importance < 1:
-            raise ValueError(f"n_importance must be an integer >= 1, got {self.n_importance!r}")
+        self.n_importance = _int_key(sys_param, "n_importance", 128, 1)
         if self.fine_sampler == "pdf" and not (self.samples_c >= 3 and self.samples_c + self.n_importance <= ops.PDF_MAX_SAMPLES):
             raise ValueError(f"fine_sampler 'pdf' needs samples >= 3 and samples + n_importance <= {ops.PDF_MAX_SAMPLES}, "
                              f"got samples = {self.samples_c}, n_importance = {self.n_importance}")
@@ -119,9 +125,7 @@ class NeRF_Model(nn.Module):
             if isinstance(v, bool) or not isinstance(v, (int, float)) or v != v or v in (float("inf"), float("-inf")):
                 raise ValueError(f"{key} must be a finite number, got {v!r}")
             return v
-        G = sys_param.get("grid_nerf")
-        if isinstance(G, bool) or not isinstance(G, int) or not 2 <= G <= 1024:
-            raise ValueError(f"grid_nerf must be an integer in [2, 1024], got {G!r}")
+        G = _int_key(sys_param, "grid_nerf", None, 2, 1024)
         bmin, bmax = number("boader_min", None), number("boader_max", None)
         if not bmin < bmax:
             raise ValueError(f"boader_min must be below boader_max, got {bmin!r} and {bmax!r}")
@@ -131,10 +135,7 @@ class NeRF_Model(nn.Module):
         if not 0.0 < beta <= 1.0:
             raise ValueError(f"voxel_beta must be in (0, 1], got {beta!r}")
         thresh = number("voxel_thresh", 0.0)
-        warm = sys_param.get("voxel_warmup_epoch", 1)
-        if isinstance(warm, bool) or not isinstance(warm, int) or warm < 0:
-            raise ValueError(f"voxel_warmup_epoch must be an integer >= 0, got {warm!r}")
-        return dict(voxel_beta=float(beta), voxel_thresh=float(thresh), voxel_warmup_epoch=warm)
+        return dict(voxel_beta=float(beta), voxel_thresh=float(thresh), voxel_warmup_epoch=_int_key(sys_param, "voxel_warmup_epoch", 1, 0))
 
     def voxel_grid(self) -> ops.VoxelGrid:
         """The cache's two grids (allocated and filled with `sigma_init` on first use; each rank has its own)."""
@@ -201,6 +202,25 @@ class NeRF_Model(nn.Module):
     def _dev(self, t):
         return t.to(device=self.z_vals_c.device, dtype=torch.float32)
 
+    def _draws(self, N, dev, train, only_coarse, jitter, eps_c, eps_sel, u, eps_f):
+        """The draws of one render, those not given drawn from torch's device generator in the reference's order (jitter, eps_c,
+        eps_sel, u, eps_f), as fp32 tensors on the model's device.  Rendering (`train` False) has no jitter, and its `u`
+        defaults to linspace(0, 1, n_importance) for every ray: a deterministic render."""
+        pdf = self.settings.pdf and not only_coarse
+        if train and jitter is None:
+            jitter = torch.empty(N, 1, device=dev).uniform_(0.0, (self.far - self.near) / self.samples_c)
+        if eps_c is None:
+            eps_c = torch.randn(N, self.samples_c, device=dev)
+        if not only_coarse:
+            if eps_sel is None:
+                eps_sel = torch.randn(N, self.samples_c, device=dev)
+            if pdf and u is None:
+                u = torch.rand(N, self.n_importance, device=dev) if train else torch.linspace(0.0, 1.0, self.n_importance, device=dev).expand(N, -1)
+            if eps_f is None:
+                eps_f = torch.randn(N, self.settings.samples_pdf if pdf else self.samples_f, device=dev)
+        on = lambda t: None if t is None else self._dev(t).contiguous()
+        return None if jitter is None else self._dev(jitter), on(eps_c), on(eps_sel), on(u) if pdf else None, on(eps_f)
+
     def render_rays_train(self, rays_d, rays_o, cur_epoch, step_r, only_coarse=False, *,
                           jitter=None, eps_c=None, eps_sel=None, eps_f=None, cap_perm=None, u=None):
         """Reference :598-646.  The keyword-only tensors are the reference's random draws
@@ -211,31 +231,14 @@ class NeRF_Model(nn.Module):
         if N == 0:                                  # empty batch: empty results (the reference's tensor ops do the same)
             e3, e1 = rays_d.new_zeros(0, 3), rays_d.new_zeros(0, 1)
             return (e3, None, e1) if only_coarse else (e3, e3.clone())
-        if jitter is None:
-            jitter = torch.empty(N, 1, device=dev).uniform_(0.0, (self.far - self.near) / self.samples_c)
-        if eps_c is None:
-            eps_c = torch.randn(N, self.samples_c, device=dev)
-        pdf = self.settings.pdf and not only_coarse
-        if not only_coarse:
-            if eps_sel is None:
-                eps_sel = torch.randn(N, self.samples_c, device=dev)
-            if pdf and u is None:
-                u = torch.rand(N, self.n_importance, device=dev)
-            if eps_f is None:
-                eps_f = torch.randn(N, self.settings.samples_pdf if pdf else self.samples_f, device=dev)
+        draws = self._draws(N, dev, True, only_coarse, jitter, eps_c, eps_sel, u, eps_f)
         params = self.nerf_coarse.ordered_parameters() + self.nerf_fine.ordered_parameters()
         self.nerf_coarse.flat_params()
         self.nerf_fine.flat_params()
-        rgb_c, rgb_f, depth_c = RenderTrainFn.apply(self, self.nerf_coarse, self.nerf_fine, step_r, only_coarse,
-                                                    self._dev(jitter), self._dev(eps_c).contiguous(),
-                                                    None if eps_sel is None else self._dev(eps_sel).contiguous(),
-                                                    None if eps_f is None else self._dev(eps_f).contiguous(),
-                                                    cap_perm, self._dev(u).contiguous() if pdf else None,
-                                                    self.settings.voxel and cur_epoch >= self.settings.voxel_warmup_epoch,
-                                                    rays_d, rays_o, *params)
-        if only_coarse:
-            return rgb_c, None, depth_c
-        return rgb_c, rgb_f
+        call = RenderCall(self, self.nerf_coarse, self.nerf_fine, step_r, only_coarse, *draws, cap_perm,
+                          prune=self.settings.voxel and cur_epoch >= self.settings.voxel_warmup_epoch)
+        rgb_c, rgb_f, depth_c = RenderTrainFn.apply(rays_d, rays_o, call, *params)
+        return (rgb_c, None, depth_c) if only_coarse else (rgb_c, rgb_f)
 
     @torch.no_grad()
     def render_rays_test(self, rays_d, rays_o, model_coarse, model_fine, *, eps_c=None, eps_sel=None, eps_f=None, _prepared=None, u=None):
@@ -245,31 +248,16 @@ class NeRF_Model(nn.Module):
         N, dev = rays_d.shape[0], rays_d.device
         if N == 0:
             return rays_d.new_zeros(0, 3), rays_d.new_zeros(0, 1), rays_d.new_zeros(0, 1)
-        if eps_c is None:
-            eps_c = torch.randn(N, self.samples_c, device=dev)
-        if eps_sel is None:
-            eps_sel = torch.randn(N, self.samples_c, device=dev)
-        pdf = self.settings.pdf
-        if eps_f is None:
-            eps_f = torch.randn(N, self.settings.samples_pdf if pdf else self.samples_f, device=dev)
-        if pdf:
-            u = (torch.linspace(0.0, 1.0, self.n_importance, device=dev).expand(N, -1) if u is None else self._dev(u)).contiguous()
-        return render_test(self, model_coarse, model_fine, rays_d.float(), rays_o.float(),
-                           self._dev(eps_c).contiguous(), self._dev(eps_sel).contiguous(), self._dev(eps_f).contiguous(), _prepared,
-                           u=u if pdf else None)
+        _, eps_c, eps_sel, u, eps_f = self._draws(N, dev, False, False, None, eps_c, eps_sel, u, eps_f)
+        return render_test(self, model_coarse, model_fine, rays_d.float(), rays_o.float(), eps_c, eps_sel, eps_f, _prepared, u=u)
 
     def reserve_workspaces(self, n_rays: int):
         """Sizes the training workspaces of both nets for `n_rays`-ray steps now (they are re-used from step to step afterwards:
         render.WorkspacePool), so that the first timed / synchronised step of a multi-GPU run allocates nothing."""
-        from .render import _cap_needed, _pool
         dev, st, pool = self.z_vals_c.device, self.settings, _pool(self)
-        if st.pdf:
-            rows_f = n_rays * st.samples_pdf
-        else:
-            rows_f = n_rays * (st.max_fine_per_ray if _cap_needed(st) else st.samples_f)
         if st.voxel:
             self.voxel_grid()                       # (the list itself has the dense pass's capacity: the pool's keys do not change)
-        for net, rows in ((self.nerf_coarse.net, n_rays * st.samples_c), (self.nerf_fine.net, rows_f)):
+        for net, rows in ((self.nerf_coarse.net, n_rays * st.samples_c), (self.nerf_fine.net, st.fine_rows(n_rays, train=True))):
             save = pool.take_save(net, rows, dev, st.precision)
             pool.give_grad(net, save, st.precision, pool.take_grad(net, save, st.precision))
             pool.give_save(net, save, st.precision)
@@ -318,20 +306,19 @@ class NeRF_Model(nn.Module):
         flat = model.flat_params()
         packed = ops.pack_weights(model.net, flat, precision=st.precision)
         barf_w = embedding_xyz.barf_weights_on(step_r, dev, pad=10)
+        idx = count = None
         if idx_render is None:
             out = torch.empty(N, S_, 4, dtype=torch.float32, device=dev)
-            ops.mlp_fwd(model.net, flat, packed, rays_o, rays_d, grid, jitter, barf_w, out, precision=st.precision)
         else:                                                   # scatter into the defaults (:692-694, 701)
             out = torch.ones(N, S_, 4, dtype=torch.float32, device=dev)
             out[..., 0] = st.sigma_default
             idx = idx_render.to(device=dev, dtype=torch.int32).contiguous()
             count = torch.tensor([idx.shape[0]], dtype=torch.int32, device=dev)
-            ops.mlp_fwd(model.net, flat, packed, rays_o, rays_d, grid, jitter, barf_w, out, idx=idx, count=count,
-                        max_rows=idx.shape[0], precision=st.precision)
         if eps is None:
             eps = torch.randn(N, S_, device=dev)
-        rgb, depth, opacity, _, _ = ops.composite_fwd(out, rays_d, grid, jitter, self._dev(eps).float().contiguous(), None,
-                                                      st.white_back, want_depth=True)
+        p = SamplePass(model, flat, packed, grid, jitter, None, self._dev(eps).float().contiguous(), out,
+                       idx, count, 0 if idx is None else idx.shape[0])
+        rgb, depth, opacity, _, _ = run_pass(p, st, Rays(rays_o, rays_d, barf_w), want_depth=True)
         return rgb, out[..., 0], xyz, depth, opacity
 
     def _inference_general(self, model, embedding_xyz, step_r, xyz, rays_d, z_vals, idx_render, eps):
@@ -495,10 +482,8 @@ class MC_Model(nn.Module):
         # "cams_per_step" is this build's own sys_param key (absent in the reference's config): the number K of cameras whose rays share
         # one NeRF-stage train step.  1 (the default) is the reference's step, one camera; K > 1 splits the batch into K segments of
         # consecutive rays, one camera each, through the fused ray-batch kernel (RayBatchFn)
-        self.cams_per_step = sys_param.get("cams_per_step", 1)
-        k = self.cams_per_step
-        if isinstance(k, bool) or not isinstance(k, int) or not 1 <= k <= ops.MULTICAM_MAXSEG or k > self.batch:
-            raise ValueError(f"cams_per_step must be an integer in [1, min({ops.MULTICAM_MAXSEG}, batch = {self.batch})], got {k!r}")
+        self.cams_per_step = _int_key(sys_param, "cams_per_step", 1, 1, min(ops.MULTICAM_MAXSEG, self.batch),
+                                      f"in [1, min({ops.MULTICAM_MAXSEG}, batch = {self.batch})]")
         self.last_step_segments = None    # (camera ids, seg_start) of the last multi-camera step
         self.last_step_pix = None         # its pixel ids [batch]
         self._seg_index = None            # segment of every ray (device int64 [batch]; host float stacks only), built once

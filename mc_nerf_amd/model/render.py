@@ -1,24 +1,28 @@
 """Autograd glue between the reference-shaped Python API and the HIP kernels.
 
-``RenderTrainFn`` is one differentiable op for the whole of NeRF_Model.render_rays_train
-(reference: model/mc_nerf.py:598-646): coarse MLP -> composite -> device-side selection -> fine MLP ->
-composite, with a hand-written backward (composite bwd -> dX chain -> dW) instead of autograd
-through ~900 ATen ops.  ``RaygenFn`` does the same for MC_Model.get_rays on selected pixels.
+The render pipeline (reference: model/mc_nerf.py:598-680) is two PASSES, each a net evaluated on a sample set and composited.  A
+``SamplePass`` record describes one: the net, the depths (the shared grid plus per-ray jitter, or per-ray rows), the [N,S,4] output, an
+optional (ray, sample) list over a prefilled output, the saved-operand set of a training call.  ``run_pass`` runs it (ops.mlp_fwd,
+ops.composite_fwd), ``pass_backward`` differentiates it (composite bwd -> dX chain -> dW).  ``coarse_pass`` and ``fine_pass`` build the
+two passes of a render; ``RenderTrainFn`` (ONE differentiable op for NeRF_Model.render_rays_train, with that hand-written backward
+instead of autograd through ~900 ATen ops), ``render_test`` and NeRF_Model._inference run what they return.  ``RaygenFn`` is the
+same kind of op for MC_Model.get_rays on selected pixels.
 
-The fine sampler is a setting (`fine_sampler`): "threshold" is the reference's weight-threshold selection above;
-"pdf" draws `n_importance` depths per ray by inverse CDF from the coarse selection weights (ops.sample_pdf) and runs
-the fine net densely on the sorted [coarse + importance] depth rows (no selection, cap or default prefill).
+What a sampler setting changes in its pass:
+  fine_sampler "threshold" (the reference): the list ops.select_fine compacts from the coarse selection weights, over the
+      (sigma_default, 1, 1, 1) prefill of the fine grid; training caps it at 128 per ray.
+  fine_sampler "pdf": dense per-ray depth rows, ops.sample_pdf's sorted [coarse + n_importance inverse-CDF] depths (a constant of
+      the pass: no gradient through the sampler); the rows hold the jitter.
+  coarse_sampler "voxel": the list ops.voxel_select reads off the owner's sigma grid, over the prefill.  Train calls keep the grid
+      current from their evaluated samples (ops.voxel_update) and run dense in the warm-up; rendering only queries.
 
-The coarse sampler is a setting too (`coarse_sampler`): "dense" is the reference's coarse pass on the whole [N,Sc] grid; "voxel" runs the
-coarse net on the (ray, sample) pairs that the owner's sigma grid lists (ops.voxel_select) over the (sigma_default, 1, 1, 1) prefill and
-keeps the grid current from every train call's evaluated samples (ops.voxel_update); rendering only queries the grid.
-
-Every random draw of the reference (jitter, the three N(0,1) tensors of sigma2weights, the cap
-permutation; in "pdf" mode the U(0,1) draws of the sampler) is an explicit tensor argument: generated with
-torch's device RNG by the caller in normal operation, passed in verbatim by the parity tests.
+Every random draw of the reference (jitter, the three N(0,1) tensors of sigma2weights, the cap permutation; in "pdf" mode the
+sampler's U(0,1) draws) is an explicit tensor argument: drawn from torch's device RNG by the caller, or passed in by the parity tests.
 """
 from __future__ import annotations
 
+from collections import namedtuple
+from contextlib import AbstractContextManager
 from dataclasses import dataclass
 from typing import Optional
 
@@ -68,6 +72,12 @@ class RenderSettings:
     def voxel(self) -> bool:
         return self.coarse_sampler == "voxel"
 
+    def fine_rows(self, n_rays: int, train: bool) -> int:
+        """Row capacity of the fine pass; the cap of model/mc_nerf.py:630-632 (128 per ray) applies in training only."""
+        if self.pdf:
+            return n_rays * self.samples_pdf
+        return n_rays * (min(self.samples_f, self.max_fine_per_ray) if train else self.samples_f)
+
 
 class WorkspacePool:
     """The MLP kernels' saved-operand and gradient workspaces (up to ~46 GB per step at 32768 rays in the split-f16 mode), sized
@@ -107,15 +117,102 @@ class WorkspacePool:
         self._give(self._key("grad", net, save.capacity, save.act.device, precision), ws)
 
 
+class WorkspaceLease(AbstractContextManager):
+    """The sets ONE forward or backward holds from the pool.  When an exception leaves its `with` block (a range overflow raised by a
+    kernel, out of memory in a take) everything still held goes back: a retried step must find the pool as it was, not one set short.
+    Otherwise the sets stay held: the forward leaves its lease with ctx, the backward gives each set back (`give`) once everything that
+    reads it is enqueued.  `held` = (set, the pool's method that takes it back, its arguments) in the order taken; nothing in it refers
+    to the lease: a forward whose backward never runs frees its tens of GB with the graph, by reference count, not by the cycle collector."""
+
+    def __init__(self, pool: WorkspacePool, precision):
+        self.pool, self.precision, self.held = pool, precision, []
+
+    def take_save(self, net, capacity, device):
+        save = self.pool.take_save(net, capacity, device, self.precision)
+        self.held.append((save, self.pool.give_save, (net, save, self.precision)))
+        return save
+
+    def take_grad(self, net, save):
+        ws = self.pool.take_grad(net, save, self.precision)
+        self.held.append((ws, self.pool.give_grad, (net, save, self.precision, ws)))
+        return ws
+
+    def give(self, ws):
+        _, back, args = self.held.pop(next(i for i, entry in enumerate(self.held) if entry[0] is ws))
+        back(*args)
+
+    def __exit__(self, exc_type, exc, tb):
+        while exc_type is not None and self.held:
+            self.give(self.held[-1][0])                     # (the set taken last first)
+
+
 def _pool(owner) -> WorkspacePool:
     if getattr(owner, "ws_pool", None) is None:
         owner.ws_pool = WorkspacePool()
     return owner.ws_pool
 
 
-def _cap_needed(st: RenderSettings) -> bool:
-    """The cap of model/mc_nerf.py:630-632 can only bind when a ray can select more than 128 samples."""
-    return st.samples_f > st.max_fine_per_ray
+# What both passes of a render share: origins and directions [N,3] (contiguous) and the BARF weights of the encoding.
+Rays = namedtuple("Rays", "o d barf_w")
+
+
+@dataclass
+class SamplePass:
+    """One net evaluated on one sample set and composited.  Holds references only.  Depths: the shared `zgrid` [S] plus `jitter` [N]
+    (None: no jitter), or per-ray `z_rows` [N,S] (zgrid and jitter None).  `idx` / `count` / `max_rows`: the (ray, sample) list the
+    net runs on over the prefilled `out`, None / None / 0 = every sample.  `save`: the saved-operand set of a training call."""
+    model: object
+    flat: torch.Tensor
+    packed: torch.Tensor
+    zgrid: Optional[torch.Tensor]
+    jitter: Optional[torch.Tensor]
+    z_rows: Optional[torch.Tensor]
+    eps: torch.Tensor
+    out: torch.Tensor
+    idx: Optional[torch.Tensor] = None
+    count: Optional[torch.Tensor] = None
+    max_rows: int = 0
+    save: Optional[ops.MlpSave] = None
+
+    TENSORS = ("flat", "packed", "zgrid", "jitter", "z_rows", "eps", "out", "idx", "count")
+
+    @property
+    def rows(self) -> int:
+        """Rows the net is evaluated on at the most: the saved-operand set's capacity, and the row count the dW kernel takes."""
+        return self.max_rows if self.idx is not None else self.out.shape[0] * self.out.shape[1]
+
+    def tensors(self):
+        """For ctx.save_for_backward; `restored` takes them off the front of an iterator over ctx.saved_tensors."""
+        return tuple(getattr(self, name) for name in self.TENSORS)
+
+    @classmethod
+    def restored(cls, model, saved, max_rows, save):
+        return cls(model, **{name: next(saved) for name in cls.TENSORS}, max_rows=max_rows, save=save)
+
+
+def run_pass(p: SamplePass, st: RenderSettings, rays: Rays, lease: Optional[WorkspaceLease] = None, eps_sel=None, want_depth=False):
+    """The net on the pass's samples, then the composite -> ops.composite_fwd's (rgb, depth, opacity, w_sel, wmax).  With a `lease`
+    the operands of the backward are saved, in a set taken through it."""
+    net = p.model.net
+    if lease is not None:
+        p.save = lease.take_save(net, p.rows, rays.d.device)
+    ops.mlp_fwd(net, p.flat, p.packed, rays.o, rays.d, p.zgrid, p.jitter, rays.barf_w, p.out,
+                idx=p.idx, count=p.count, max_rows=p.max_rows, save=p.save, precision=st.precision, z_rows=p.z_rows)
+    return ops.composite_fwd(p.out, rays.d, p.zgrid, p.jitter, p.eps, eps_sel, st.white_back, want_depth=want_depth, z_rows=p.z_rows)
+
+
+def pass_backward(p: SamplePass, st: RenderSettings, rays: Rays, d_rgb, grads, d_o, d_d, lease: WorkspaceLease):
+    """The pass's composite backward, dX chain (into d_o / d_d [N,3] when given) and weight gradients (into `grads`); nothing when
+    `d_rgb` is None.  Either way the pass's saved-operand set goes back to the pool."""
+    net = p.model.net
+    if d_rgb is not None:
+        d_out, gmax = ops.composite_bwd(p.out, p.zgrid, p.jitter, p.eps, d_rgb.contiguous(), st.white_back, want_gmax=True, z_rows=p.z_rows)
+        dy, dsh = ws = lease.take_grad(net, p.save)
+        ops.mlp_bwd(net, p.flat, p.packed, rays.o, rays.d, p.zgrid, p.jitter, rays.barf_w, p.out, d_out, p.save, dy, dsh,
+                    d_o, d_d, idx=p.idx, count=p.count, max_rows=p.max_rows, precision=st.precision, gmax=gmax, z_rows=p.z_rows)
+        ops.mlp_dw(net, p.save, dy, dsh, grads, p.rows, count=p.count, precision=st.precision, gmax=gmax)
+        lease.give(ws)
+    lease.give(p.save)
 
 
 def select_and_cap(st: RenderSettings, w_sel, wmax, n_rays, cap_perm, train: bool):
@@ -124,9 +221,8 @@ def select_and_cap(st: RenderSettings, w_sel, wmax, n_rays, cap_perm, train: boo
     from torch's device generator.  Only a caller-supplied permutation (`cap_perm`, the parity-test input that replays
     the reference's CPU randperm, :631) goes through the host: its length IS the host-side count."""
     idx, count, out_f = ops.select_fine(w_sel, wmax, st.weight_thresh, st.scale, st.sigma_default)
-    max_rows = n_rays * st.samples_f
-    if train and _cap_needed(st):
-        keep = n_rays * st.max_fine_per_ray
+    max_rows, keep = st.fine_rows(n_rays, train=False), st.fine_rows(n_rays, train=True)
+    if train and keep < max_rows:
         if cap_perm is not None:
             k = int(count.item())                  # (test path only)
             if k > keep:
@@ -142,211 +238,129 @@ def select_and_cap(st: RenderSettings, w_sel, wmax, n_rays, cap_perm, train: boo
     return idx, count, out_f, max_rows
 
 
+def coarse_pass(owner, model, flat, packed, rays: Rays, jitter, eps, prune: bool) -> SamplePass:
+    """The coarse pass: the dense [N,Sc] grid, or (`prune`, read in "voxel" mode only: a train call past the warm-up, or rendering)
+    the sigma grid's list over the default prefill."""
+    st: RenderSettings = owner.settings
+    N = rays.d.shape[0]
+    grid = owner.voxel_grid() if st.voxel else None
+    idx = count = None
+    if grid is not None and prune:
+        idx, count, out = ops.voxel_select(grid, st.voxel_thresh, rays.o, rays.d, owner.z_vals_c, jitter, st.sigma_default)
+    else:
+        out = torch.empty(N, st.samples_c, 4, dtype=torch.float32, device=rays.d.device)
+    owner.last_coarse_selection = None if idx is None else (idx, count)
+    return SamplePass(model, flat, packed, owner.z_vals_c, jitter, None, eps, out, idx, count, N * st.samples_c if idx is not None else 0)
+
+
+def fine_pass(owner, model, flat, packed, rays: Rays, jitter, w_sel, wmax, eps, u, cap_perm, train: bool) -> SamplePass:
+    """The fine pass from the coarse composite's selection weights: the selected (ray, sample) list over the default prefill (no host
+    sync), or in "pdf" mode dense rows of inverse-CDF depths drawn with `u`."""
+    st: RenderSettings = owner.settings
+    if st.pdf:
+        z_all = ops.sample_pdf(w_sel, owner.z_vals_c, jitter, u)
+        out = torch.empty(*z_all.shape, 4, dtype=torch.float32, device=rays.d.device)
+        p = SamplePass(model, flat, packed, None, None, z_all, eps, out)
+    else:
+        idx, count, out, max_rows = select_and_cap(st, w_sel, wmax, rays.d.shape[0], cap_perm, train)
+        p = SamplePass(model, flat, packed, owner.z_vals_f, jitter, None, eps, out, idx, count, max_rows)
+    owner.last_selection, owner.last_z_all = None if p.idx is None else (p.idx, p.count), p.z_rows
+    return p
+
+
+def _packed(model, flat, st: RenderSettings, dev):
+    return ops.pack_weights(model.net, flat, precision=st.precision, range_flags=model.range_flags(st.precision, dev))
+
+
+# Everything non-differentiable of one RenderTrainFn call.  `prune` (read in "voxel" mode only): True = the coarse net runs on the
+# grid's (ray, sample) list, False = the warm-up's dense pass; either way the grid is then updated from the evaluated samples.
+RenderCall = namedtuple("RenderCall", "owner model_c model_f step_r only_coarse jitter eps_c eps_sel u eps_f cap_perm prune")
+
+
 class RenderTrainFn(torch.autograd.Function):
-    """rgb_c, rgb_f, depth_c = f(rays_d, rays_o, *coarse_params, *fine_params) with explicit draws."""
+    """rgb_c, rgb_f, depth_c = f(rays_d, rays_o, call, *coarse_params, *fine_params); `call` (RenderCall) holds the explicit draws."""
 
     @staticmethod
-    def forward(ctx, owner, model_c, model_f, step_r, only_coarse, jitter, eps_c, eps_sel, eps_f, cap_perm, u, prune,
-                rays_d, rays_o, *params):
-        """`prune` (read in "voxel" mode only): True = the coarse net runs on the grid's (ray, sample) list, False = the warm-up's dense
-        pass; either way the grid is then updated from the evaluated samples."""
-        st: RenderSettings = owner.settings
-        dev = rays_d.device
-        N = rays_d.shape[0]
-        rays_d = rays_d.contiguous()
-        rays_o = rays_o.contiguous()
+    def forward(ctx, rays_d, rays_o, call: RenderCall, *params):
+        owner, st, dev = call.owner, call.owner.settings, rays_d.device
         need_grad = any(ctx.needs_input_grad)
-        barf_w = owner.emmbedding_xyz.barf_weights_on(step_r, dev, pad=10)
-        jit = jitter.reshape(-1).contiguous()
-
-        # ---- coarse pass: the dense [N,Sc] grid, or ("voxel" mode past its warm-up) the grid's list over the default prefill
-        net_c = model_c.net
-        flat_c = model_c.flat_params()
-        prec = st.precision
-        packed_c = ops.pack_weights(net_c, flat_c, precision=prec, range_flags=model_c.range_flags(prec, dev))
-        rows_c = N * st.samples_c
-        grid = owner.voxel_grid() if st.voxel else None
-        idx_c = count_c = None
-        if grid is not None and prune:
-            idx_c, count_c, out_c = ops.voxel_select(grid, st.voxel_thresh, rays_o, rays_d, owner.z_vals_c, jit, st.sigma_default)
-        else:
-            out_c = torch.empty(N, st.samples_c, 4, dtype=torch.float32, device=dev)
-        save_c = _pool(owner).take_save(net_c, rows_c, dev, prec) if need_grad else None
-        if idx_c is None:
-            ops.mlp_fwd(net_c, flat_c, packed_c, rays_o, rays_d, owner.z_vals_c, jit, barf_w, out_c, save=save_c, precision=prec)
-        else:
-            try:
-                ops.mlp_fwd(net_c, flat_c, packed_c, rays_o, rays_d, owner.z_vals_c, jit, barf_w, out_c,
-                            idx=idx_c, count=count_c, max_rows=rows_c, save=save_c, precision=prec)
-            except BaseException:
-                if save_c is not None:                      # (no backward will give the set back)
-                    _pool(owner).give_save(net_c, save_c, prec)
-                raise
-        rgb_c, depth_c, _, w_sel, wmax = ops.composite_fwd(out_c, rays_d, owner.z_vals_c, jit, eps_c,
-                                                          None if only_coarse else eps_sel, st.white_back,
-                                                          want_depth=only_coarse)
-        if grid is not None:
-            try:
-                ops.voxel_update(grid, st.voxel_beta, rays_o, rays_d, owner.z_vals_c, jit, out_c, idx_c, count_c, rows_c if idx_c is not None else 0)
-            except BaseException:
-                if save_c is not None:
-                    _pool(owner).give_save(net_c, save_c, prec)
-                raise
-        owner.last_coarse_selection = None if idx_c is None else (idx_c, count_c)
-        ctx.only_coarse = only_coarse
-        ctx.owner, ctx.model_c, ctx.model_f = owner, model_c, model_f
-        ctx.n_c = len(model_c.ordered_parameters())
-        if only_coarse:
-            if need_grad:
-                ctx.save_for_backward(rays_d, rays_o, jit, eps_c, barf_w, out_c, flat_c, packed_c, idx_c, count_c)
-                ctx.save_c = save_c
+        rays = Rays(d=rays_d.contiguous(), o=rays_o.contiguous(), barf_w=owner.emmbedding_xyz.barf_weights_on(call.step_r, dev, pad=10))
+        jit = call.jitter.reshape(-1).contiguous()
+        with WorkspaceLease(_pool(owner), st.precision) as lease:
+            saving = lease if need_grad else None
+            flat_c = call.model_c.flat_params()
+            coarse = coarse_pass(owner, call.model_c, flat_c, _packed(call.model_c, flat_c, st, dev), rays, jit, call.eps_c, call.prune)
+            rgb_c, depth_c, _, w_sel, wmax = run_pass(coarse, st, rays, saving, None if call.only_coarse else call.eps_sel,
+                                                      want_depth=call.only_coarse)
+            if st.voxel:
+                ops.voxel_update(owner.voxel_grid(), st.voxel_beta, rays.o, rays.d, coarse.zgrid, jit, coarse.out,
+                                 coarse.idx, coarse.count, coarse.max_rows)
+            passes, rgb_f = [coarse], None
+            if not call.only_coarse:
+                flat_f = call.model_f.flat_params()
+                fine = fine_pass(owner, call.model_f, flat_f, _packed(call.model_f, flat_f, st, dev), rays, jit, w_sel, wmax,
+                                 call.eps_f, call.u, call.cap_perm, train=True)
+                rgb_f = run_pass(fine, st, rays, saving)[0]
+                passes.append(fine)
+        if need_grad:                                       # the lease, with the sets it holds, waits in ctx for the backward
+            ctx.owner, ctx.model_f, ctx.lease = owner, call.model_f, lease          # (not `call`: it would keep every draw alive)
+            ctx.stubs = [(p.model, p.max_rows, p.save) for p in passes]
+            ctx.save_for_backward(*rays, *(t for p in passes for t in p.tensors()))
+        if depth_c is not None:                             # (only_coarse; rgb_f is None then)
             ctx.mark_non_differentiable(depth_c)
-            return rgb_c, None, depth_c
-
-        net_f = model_f.net
-        flat_f = model_f.flat_params()
-        packed_f = ops.pack_weights(net_f, flat_f, precision=prec, range_flags=model_f.range_flags(prec, dev))
-        if st.pdf:
-            # ---- inverse-CDF samples (a constant of the fine pass: no gradient through the sampler) and the dense fine pass on
-            # the sorted per-ray depth rows; the rows hold the jitter
-            z_all = ops.sample_pdf(w_sel, owner.z_vals_c, jit, u)
-            idx = count = None
-            max_rows = N * z_all.shape[1]
-            out_f = torch.empty(N, z_all.shape[1], 4, dtype=torch.float32, device=dev)
-            save_f = _pool(owner).take_save(net_f, max_rows, dev, prec) if need_grad else None
-            ops.mlp_fwd(net_f, flat_f, packed_f, rays_o, rays_d, None, None, barf_w, out_f, save=save_f, precision=prec, z_rows=z_all)
-            rgb_f, _, _, _, _ = ops.composite_fwd(out_f, rays_d, None, None, eps_f, None, st.white_back, z_rows=z_all)
-            owner.last_selection = None
-        else:
-            # ---- selection (no host sync) and fine pass on the compacted (ray, sample) list
-            z_all = None
-            idx, count, out_f, max_rows = select_and_cap(st, w_sel, wmax, N, cap_perm, train=True)
-            save_f = _pool(owner).take_save(net_f, max_rows, dev, prec) if need_grad else None
-            ops.mlp_fwd(net_f, flat_f, packed_f, rays_o, rays_d, owner.z_vals_f, jit, barf_w, out_f,
-                        idx=idx, count=count, max_rows=max_rows, save=save_f, precision=prec)
-            rgb_f, _, _, _, _ = ops.composite_fwd(out_f, rays_d, owner.z_vals_f, jit, eps_f, None, st.white_back)
-            owner.last_selection = (idx, count)
-        owner.last_z_all = z_all
-        if need_grad:
-            ctx.save_for_backward(rays_d, rays_o, jit, eps_c, barf_w, out_c, flat_c, packed_c,
-                                  eps_f, out_f, flat_f, packed_f, idx, count, z_all, idx_c, count_c)
-            ctx.save_c, ctx.save_f, ctx.max_rows = save_c, save_f, max_rows
-        return rgb_c, rgb_f, None
+        return rgb_c, rgb_f, depth_c
 
     @staticmethod
     def backward(ctx, d_rgb_c, d_rgb_f, _d_depth):
-        owner, model_c, model_f = ctx.owner, ctx.model_c, ctx.model_f
-        st: RenderSettings = owner.settings
         if getattr(ctx, "workspaces_given_back", False):
             # retain_graph=True + a second backward: the saved-operand set went back to the pool after the first one and the next
             # forward may already have overwritten it -- refuse instead of returning gradients of clobbered operands
             raise ops._lib.McnerfError("RenderTrainFn.backward ran twice on one forward (retain_graph): its saved-operand workspaces were "
                                   "returned to the pool by the first backward; run the forward again")
-        saved = ctx.saved_tensors
-        rays_d, rays_o, jit, eps_c, barf_w, out_c, flat_c, packed_c = saved[:8]
-        idx_c, count_c = saved[-2:]                         # the coarse list of "voxel" mode, or None, None
-        dev = rays_d.device
-        N = rays_d.shape[0]
-        want_rays = ctx.needs_input_grad[12] or ctx.needs_input_grad[13]
+        owner, st, model_f = ctx.owner, ctx.owner.settings, ctx.model_f
+        saved = iter(ctx.saved_tensors)
+        rays = Rays(next(saved), next(saved), next(saved))
+        coarse, *fine = [SamplePass.restored(model, saved, max_rows, save) for model, max_rows, save in ctx.stubs]
+        N, dev = rays.d.shape[0], rays.d.device
+        want_rays = ctx.needs_input_grad[0] or ctx.needs_input_grad[1]
         d_od = torch.zeros(2, N, 3, dtype=torch.float32, device=dev) if want_rays else None      # (one fill for both)
         d_o, d_d = (d_od[0], d_od[1]) if want_rays else (None, None)
         # gradient buffers: slices of the step-level arena when a FlatGradSync provided one (so the whole
         # step's gradient is one contiguous all-reduce message), otherwise fresh zeroed buffers
         arena = getattr(owner, "grad_arena", None)
-        n_c, n_f = flat_c.numel(), model_f.flat_params().numel()
-        if arena is not None:
-            g_c = arena[:n_c]
-            owner.grad_arena_used = True
-        else:
-            g_c = torch.zeros_like(flat_c)
+        n_c, n_f = coarse.flat.numel(), model_f.flat_params().numel()
+        g_c = arena[:n_c] if arena is not None else torch.zeros_like(coarse.flat)
         g_f = None
-
-        def net_backward(model, flat, packed, zgrid, eps, out, d_rgb, save, grads, idx=None, count=None, max_rows=0, z_rows=None):
-            """One net's composite backward, dX chain and weight gradients (`z_rows`: the per-ray depth rows of the "pdf" fine pass,
-            which hold the jitter).  The saved-operand set goes back to the pool on EVERY way
-            out -- no gradient wanted, or an error (a range overflow raised by a kernel, out of memory in take_grad) --: a retried
-            step must find the pool as the forward left it, not one set short."""
-            net = model.net
-            pool = _pool(owner)
-            jit_ = jit if z_rows is None else None
-            try:
-                if d_rgb is None:
-                    return
-                d_out, gmax = ops.composite_bwd(out, zgrid, jit_, eps, d_rgb.contiguous(), st.white_back, want_gmax=True, z_rows=z_rows)
-                dy, dsh = pool.take_grad(net, save, st.precision)
-                try:
-                    ops.mlp_bwd(net, flat, packed, rays_o, rays_d, zgrid, jit_, barf_w, out, d_out, save, dy, dsh,
-                                d_o, d_d, idx=idx, count=count, max_rows=max_rows, precision=st.precision, gmax=gmax, z_rows=z_rows)
-                    rows = max_rows if idx is not None else N * (zgrid.numel() if z_rows is None else z_rows.shape[1])
-                    ops.mlp_dw(net, save, dy, dsh, grads, rows, count=count, precision=st.precision, gmax=gmax)
-                finally:
-                    pool.give_grad(net, save, st.precision, (dy, dsh))
-            finally:
-                pool.give_save(net, save, st.precision)       # (everything that reads the set is enqueued: the next step may overwrite it)
-
+        if arena is not None:
+            owner.grad_arena_used = True
         # from here on the saved-operand sets leave this context, whatever happens: a second backward on a retained graph is refused
-        save_c, save_f = ctx.save_c, (None if ctx.only_coarse else ctx.save_f)
-        ctx.save_c = ctx.save_f = None
+        lease, ctx.lease, ctx.stubs = ctx.lease, None, None
         ctx.workspaces_given_back = True
-        if not ctx.only_coarse:
-            eps_f, out_f, flat_f, packed_f, idx, count, z_all = saved[8:15]
-            g_f = arena[n_c:n_c + n_f] if arena is not None else torch.zeros_like(flat_f)
-            try:
-                net_backward(model_f, flat_f, packed_f, owner.z_vals_f, eps_f, out_f, d_rgb_f, save_f, g_f,
-                             idx=idx, count=count, max_rows=ctx.max_rows, z_rows=z_all)
-            except BaseException:
-                _pool(owner).give_save(model_c.net, save_c, st.precision)      # (the coarse net's set never reaches its own backward)
-                raise
-        net_backward(model_c, flat_c, packed_c, owner.z_vals_c, eps_c, out_c, d_rgb_c, save_c, g_c,
-                     idx=idx_c, count=count_c, max_rows=N * st.samples_c if idx_c is not None else 0)
-        grads_c = model_c.grad_views(g_c)
+        with lease:
+            for p in fine:                                  # (none after an only_coarse call)
+                g_f = arena[n_c:n_c + n_f] if arena is not None else torch.zeros_like(p.flat)
+                pass_backward(p, st, rays, d_rgb_f, g_f, d_o, d_d, lease)
+            pass_backward(coarse, st, rays, d_rgb_c, g_c, d_o, d_d, lease)
+        grads_c = coarse.model.grad_views(g_c)
         grads_f = model_f.grad_views(g_f) if g_f is not None else [None] * len(model_f.ordered_parameters())
         owner.last_flat_grads = (g_c, g_f)
-        return (None,) * 12 + (d_d if ctx.needs_input_grad[12] else None,
-                               d_o if ctx.needs_input_grad[13] else None) + tuple(grads_c) + tuple(grads_f)
+        return (d_d if ctx.needs_input_grad[0] else None, d_o if ctx.needs_input_grad[1] else None, None, *grads_c, *grads_f)
 
 
 def render_test(owner, model_c, model_f, rays_d, rays_o, eps_c, eps_sel, eps_f, prepared=None, u=None):
-    """NeRF_Model.render_rays_test (model/mc_nerf.py:648-680): no jitter, step_r = 1, no cap, no grad.
-    `prepared` = (packed_c, packed_f, barf_w) from an enclosing chunk loop (the weights do not change inside it).
+    """NeRF_Model.render_rays_test (model/mc_nerf.py:648-680): no jitter, step_r = 1, no cap, no grad; "voxel" mode only queries the
+    grid.  `prepared` = (packed_c, packed_f, barf_w) from an enclosing chunk loop (the weights do not change inside it).
     "pdf" mode: `u` [N, n_importance] are the sampler's draws (the caller passes linspace(0, 1) rows: a deterministic render)."""
-    st: RenderSettings = owner.settings
-    dev = rays_d.device
-    N = rays_d.shape[0]
-    rays_d = rays_d.contiguous()
-    rays_o = rays_o.contiguous()
-    net_c, net_f = model_c.net, model_f.net
+    st, dev = owner.settings, rays_d.device
     flat_c, flat_f = model_c.flat_params(), model_f.flat_params()
-    prec = st.precision
     if prepared is None:
-        prepared = (ops.pack_weights(net_c, flat_c, precision=prec, range_flags=model_c.range_flags(prec, dev)),
-                    ops.pack_weights(net_f, flat_f, precision=prec, range_flags=model_f.range_flags(prec, dev)),
-                    owner.emmbedding_xyz.barf_weights_on(1, dev, pad=10))
+        prepared = (_packed(model_c, flat_c, st, dev), _packed(model_f, flat_f, st, dev), owner.emmbedding_xyz.barf_weights_on(1, dev, pad=10))
     packed_c, packed_f, barf_w = prepared
-    if st.voxel:                                            # query only: rendering never updates the grid
-        idx_c, count_c, out_c = ops.voxel_select(owner.voxel_grid(), st.voxel_thresh, rays_o, rays_d, owner.z_vals_c, None, st.sigma_default)
-        ops.mlp_fwd(net_c, flat_c, packed_c, rays_o, rays_d, owner.z_vals_c, None, barf_w, out_c,
-                    idx=idx_c, count=count_c, max_rows=N * st.samples_c, precision=prec)
-        owner.last_coarse_selection = (idx_c, count_c)
-    else:
-        out_c = torch.empty(N, st.samples_c, 4, dtype=torch.float32, device=dev)
-        ops.mlp_fwd(net_c, flat_c, packed_c, rays_o, rays_d, owner.z_vals_c, None, barf_w, out_c, precision=prec)
-        owner.last_coarse_selection = None
-    _, _, _, w_sel, wmax = ops.composite_fwd(out_c, rays_d, owner.z_vals_c, None, eps_c, eps_sel, st.white_back)
-    if st.pdf:
-        z_all = ops.sample_pdf(w_sel, owner.z_vals_c, None, u)
-        out_f = torch.empty(N, z_all.shape[1], 4, dtype=torch.float32, device=dev)
-        ops.mlp_fwd(net_f, flat_f, packed_f, rays_o, rays_d, None, None, barf_w, out_f, precision=prec, z_rows=z_all)
-        rgb, depth, opacity, _, _ = ops.composite_fwd(out_f, rays_d, None, None, eps_f, None, st.white_back, want_depth=True, z_rows=z_all)
-        owner.last_selection, owner.last_z_all = None, z_all
-        return rgb, depth, opacity
-    idx, count, out_f, max_rows = select_and_cap(st, w_sel, wmax, N, None, train=False)
-    ops.mlp_fwd(net_f, flat_f, packed_f, rays_o, rays_d, owner.z_vals_f, None, barf_w, out_f,
-                idx=idx, count=count, max_rows=max_rows, precision=prec)
-    rgb, depth, opacity, _, _ = ops.composite_fwd(out_f, rays_d, owner.z_vals_f, None, eps_f, None, st.white_back,
-                                                  want_depth=True)
-    owner.last_selection = (idx, count)
-    return rgb, depth, opacity
+    rays = Rays(d=rays_d.contiguous(), o=rays_o.contiguous(), barf_w=barf_w)
+    coarse = coarse_pass(owner, model_c, flat_c, packed_c, rays, None, eps_c, prune=True)
+    _, _, _, w_sel, wmax = run_pass(coarse, st, rays, eps_sel=eps_sel)
+    fine = fine_pass(owner, model_f, flat_f, packed_f, rays, None, w_sel, wmax, eps_f, u, None, train=False)
+    return run_pass(fine, st, rays, want_depth=True)[:3]                    # rgb, depth, opacity
 
 
 class RaygenFn(torch.autograd.Function):
