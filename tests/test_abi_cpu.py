@@ -115,3 +115,27 @@ def test_register_chain_dtypes_and_workspace_sizes(built_lib):
                     assert l.mcnerf_ws_bytes_16(depth, width, 2, cap, which) == 2 * l.mcnerf_ws_bytes_16(depth, width, 0, cap, which)
             assert l.mcnerf_ws_bytes_16(depth, width, 3, cap, 4) == l.mcnerf_ws_bytes_16(depth, width, 2, cap, 4) == 2 * l.mcnerf_ws_bytes_16(depth, width, 0, cap, 4)
     assert l.mcnerf_packed_bytes_16(8, 256, 4, 4, 0) == -1 and l.mcnerf_ws_bytes_16(8, 256, -1, 4096, 0) == -1 and l.mcnerf_ws_bytes_16(8, 256, 4, 4096, 0) == -1
+
+
+def test_hi_plane_mode_workspace_layout(built_lib):
+    """The layout contract tests/test_mlpx3h_gpu.py compares workspaces under: at capacities around a tile and around a pass, "f16x3h"
+    sizes its slots, encoding, ReLU words and dY tile like "f16" (one 16-bit plane: [slot][tile][k-step][2][32][8]), keeps "f16x3"'s
+    fp32 sh.2 tile, and "f16x3" holds exactly two such planes per tile -- over the same number of 32-row tiles, whole passes of both
+    wave configurations of the chains."""
+    from mc_nerf_amd import ops
+    for depth, width in ((4, 32), (8, 64), (4, 128), (8, 256), (2, 256)):
+        net = ops.Net(depth, width, depth // 2)
+        for cap in (1, 31, 32, 33, 257, 4099):
+            ws = lambda which, precision: ops.ws_bytes_16(net, cap, which, precision)
+            for which in (0, 1, 2, 3):
+                assert ws(which, "f16x3h") == ws(which, "f16") > 0
+            assert ws(4, "f16x3h") == ws(4, "f16x3") > 0
+            for which in (0, 1, 3):
+                assert ws(which, "f16x3") == 2 * ws(which, "f16x3h")
+            assert ws(2, "f16x3") == ws(2, "f16x3h")
+            # the geometry ops.decode_frags_16 / decode_masks_16 / decode_sh_x3 assume: 1 KiB per (tile, k-step) fragment
+            tiles, rem = divmod(ws(1, "f16x3h"), 4 * 1024)
+            assert rem == 0 and 32 * tiles >= cap and tiles % 8 == 0
+            assert ws(0, "f16x3h") == (depth + 2) * tiles * (width // 16) * 1024
+            assert ws(2, "f16x3h") == (depth + 2) * tiles * 64 * 4 * max(1, width // 64)
+            assert ws(3, "f16x3h") == tiles * 2 * 1024 and ws(4, "f16x3h") == tiles * 4096

@@ -1,0 +1,446 @@
+"""GPU tests of the hi-plane mode ("f16x3h", dtype 3 of the register-chain entry points) below NeRF_Model: the three device paths
+only this mode runs -- mlp_x3_fwd_kernel<W, 2> (one saved plane per tile, two fragment stores per output tile), mlp_x3_bwd_kernel<W,
+true> (one-plane dY) and the single-pass f16 weight-gradient kernel reading those planes with x_scale = 2^3.
+
+Two references throughout:
+  * the split-f16 mode "f16x3" on the same inputs, BIT for bit: the chains are the same instructions on the same data, so the output,
+    the ReLU words, the fp32 sh.2 tile and the hi plane of every saved operand must be equal as raw bits;
+  * the CPU oracle (forward, per layer) and an fp64 GEMM of the very operands the weight-gradient kernel read (decoded planes): a
+    32-row tile dropped or counted twice moves a gradient by about 1 / tiles of its size, far above the 2e-5 gate, where the model
+    level gates (sized for the mode's 11-bit operand rounding) do not see it.
+Every workspace is filled with 0xFF bytes (f16 NaN) first, so that nothing stale can pass.  Run with -s for the measured figures
+(profiles/x3h_op_parity.txt).
+"""
+import math
+from types import SimpleNamespace
+
+import numpy as np
+import pytest
+import torch
+
+from oracle import mcnerf_oracle as O
+
+pytestmark = pytest.mark.gpu
+
+NETS = {32: O.NetCfg(4, 32, (2,)), 64: O.NetCfg(8, 64, (4,)), 128: O.NetCfg(4, 128, (2,)), 256: O.NetCfg(8, 256, (4,))}
+P, PX = "f16x3h", "f16x3"
+
+
+def _ops():
+    from mc_nerf_amd import ops
+    return ops
+
+
+def make_rays(n, seed, radius=3.0):
+    g = torch.Generator().manual_seed(seed)
+    o = torch.nn.functional.normalize(torch.randn(n, 3, generator=g), dim=-1) * radius
+    tgt = (torch.rand(n, 3, generator=g) - 0.5) * 1.5
+    d = torch.nn.functional.normalize(tgt - o, dim=-1)
+    return d.contiguous(), o.contiguous()
+
+
+def net_of(nc):
+    return _ops().Net(nc.depth, nc.width, nc.skips[0])
+
+
+def flat_params(nc, p, dev):
+    ops = _ops()
+    net = net_of(nc)
+    return ops.flatten_params(net, [p[k].to(dev) for k in net.names()], dev)
+
+
+def maxerr(a, b):
+    return float((a.detach().cpu().double() - b.detach().cpu().double()).abs().max())
+
+
+def pass_rows(width):
+    """Rows of one pass of the forward / backward chains: 32 per wave, mcnx3_waves(width) waves (csrc/mcnerf_x3.h)."""
+    return 32 * (4 if width >= 128 else 8)
+
+
+def covered_tiles(rows, width):
+    """32-row tiles the chains write for a launch over `rows` rows: every wave of every pass that runs stores its tile."""
+    R = pass_rows(width)
+    return -(-rows // R) * (R // 32)
+
+
+def alloc_ff(ops, net, cap, dev, precision):
+    """The forward's and the backward's workspaces, every byte 0xFF."""
+    save = ops.alloc_save(net, cap, dev, precision=precision)
+    dy, dsh = ops.alloc_grad_ws(net, save, precision)
+    for b in (save.act, save.enc, save.sh, save.mask, dy, dsh):
+        b.view(torch.uint8).fill_(0xFF)
+    return save, dy, dsh
+
+
+def planes16(buf, n_slots, ks, precision):
+    """A fragment workspace as raw 16-bit patterns [slot][tile][ks * 512]: the whole tile in the hi-plane mode
+    ([slot][tile][ks][2][32][8]), part 0 of [slot][tile][2][ks][2][32][8] in f16x3."""
+    v = buf.view(torch.int16)
+    if precision == PX:
+        return v.view(n_slots, -1, 2, ks * 512)[:, :, 0]
+    return v.view(n_slots, -1, ks * 512)
+
+
+def assert_hi_planes(what, buf_h, buf_x, n_slots, ks, tiles):
+    """Tiles [0, tiles) of the hi-plane workspace equal f16x3's hi planes bit for bit; the tiles behind them still hold the fill."""
+    a, b = planes16(buf_h, n_slots, ks, P), planes16(buf_x, n_slots, ks, PX)
+    assert a.shape == b.shape and tiles <= a.shape[1], (what, tuple(a.shape), tuple(b.shape), tiles)
+    ne = a[:, :tiles] != b[:, :tiles]
+    if bool(ne.any()):
+        s, t_ = (int(v) for v in torch.nonzero(ne.any(-1))[0])
+        raise AssertionError(f"{what}: differs from the f16x3 hi plane in {int(ne.sum())} values, first in slot {s}, tile {t_}")
+    assert bool((a[:, tiles:] == -1).all()), f"{what}: written behind tile {tiles}, the last one the launch covers"
+
+
+def tile_of(ops, buf, n_slots, width, tile):
+    """Rows [32 tile, 32 tile + 32) of every slot of a hi-plane workspace, decoded: [n_slots, 32, width]."""
+    v = buf.view(n_slots, -1, (width // 16) * 1024)[:, tile].contiguous()
+    return ops.decode_frags_16(v.reshape(-1), n_slots, width, 32, P)
+
+
+def assert_zero_past(ops, nc, dy, dsh, rows):
+    """Decoded dY rows [rows, end of that row's tile) are exactly zero: the forward clamps them to a copy of the last listed row, so
+    this zero is what keeps them out of the weight gradient."""
+    if rows % 32 == 0:
+        return
+    t_, r0 = rows // 32, rows % 32
+    tail = tile_of(ops, dy, nc.depth + 2, nc.width, t_)[:, r0:]
+    assert bool((tail == 0).all()), f"dy rows {rows} .. {32 * t_ + 31}: {int((tail != 0).sum())} values not zero (NaN counts)"
+    tail = tile_of(ops, dsh, 1, 32, t_)[:, r0:]
+    assert bool((tail == 0).all()), f"dsh rows {rows} .. {32 * t_ + 31}: {int((tail != 0).sum())} values not zero (NaN counts)"
+
+
+def grad_scale(gmax):
+    """mcn16_grad_scale (csrc/mcnerf_16.h): the power of two the backward multiplies dY by."""
+    return 2.0 ** (4 - math.ceil(math.log2(gmax)))
+
+
+def dw_operand_reference(ops, nc, save, dy, dsh, rows, sg):
+    """Every parameter gradient as the fp64 GEMM / column sum, on the device, of the operands the weight-gradient kernel read:
+    rows [0, rows) of the decoded hi planes, X / SPLIT_SCALE_X and dY / sg."""
+    D, W, skip = nc.depth, nc.width, nc.skips[0]
+    sx = ops.SPLIT_SCALE_X
+    na, ny = save.act.numel() // (D + 2), dy.numel() // (D + 2)
+    act = lambda l: ops.decode_frags_16(save.act[l * na:(l + 1) * na], 1, W, rows, P)[0].double() / sx
+    dyl = lambda l: ops.decode_frags_16(dy[l * ny:(l + 1) * ny], 1, W, rows, P)[0].double() / sg
+    enc = ops.decode_frags_16(save.enc, 1, 64, rows, P)[0][:, :63].double() / sx
+    dshv = ops.decode_frags_16(dsh, 1, 32, rows, P)[0].double() / sg
+    ref = {}
+    for l in range(D):
+        x = enc if l == 0 else (torch.cat([enc, act(l - 1)], 1) if l == skip else act(l - 1))
+        g = dyl(l)
+        ref[f"xyz_encoding_{l + 1}.0.weight"], ref[f"xyz_encoding_{l + 1}.0.bias"] = g.t() @ x, g.sum(0)
+    trunk = act(D - 1)
+    g = dyl(D)
+    ref["sigma.0.weight"], ref["sigma.0.bias"] = g.t() @ trunk, g.sum(0)
+    g = dyl(D + 1)
+    ref["sh.0.weight"], ref["sh.0.bias"] = g.t() @ trunk, g.sum(0)
+    ref["sh.2.weight"], ref["sh.2.bias"] = dshv[:, :27].t() @ act(D + 1), dshv[:, :27].sum(0)
+    ref["sigma.2.weight"], ref["sigma.2.bias"] = dshv[:, 27:28].t() @ act(D), dshv[:, 27:28].sum(0)
+    return {k: v.cpu() for k, v in ref.items()}
+
+
+def assert_dw_exact(ops, net, grads, ref, tag):
+    """fp32 accumulation of exact products of 11-bit operands: only summation-order noise, 2e-5 of the tensor's largest entry (the
+    gate tests/test_mlp16_gpu.py::test_mlp16_dw_at_scale holds this kernel to).  -> the worst error as a fraction of max|ref|."""
+    worst, worst_name = 0.0, ""
+    for off, shp, name in zip(ops.param_offsets(net), net.shapes(), net.names()):
+        n = int(np.prod(shp))
+        got = grads[off:off + n].view(shp).double().cpu()
+        want = ref[name].view(shp)
+        scale = float(want.abs().max())
+        err = float((got - want).abs().max())
+        assert math.isfinite(err) and err <= 2e-5 * scale + 1e-9, f"{tag} {name}: err {err:.3e}, max|ref| {scale:.3e}"
+        if scale > 0 and err / scale > worst:
+            worst, worst_name = err / scale, name
+    return worst, worst_name
+
+
+# --------------------------------------------------------------------------------------------------------------------- 1, 5: dense
+def dense_case(dev, width, barf, per_ray):
+    ops = _ops()
+    nc = NETS[width]
+    net = net_of(nc)
+    D = nc.depth
+    S, N = 48, 37                 # 1776 rows: neither a multiple of 32 nor of a pass
+    rows = N * S
+    cfg = O.RenderCfg(samples=S, scale=2, coarse=nc, fine=nc, barf_mode=barf, barf_start=0.3846, barf_end=0.6923)
+    step_r = 0.5
+    p = O.init_params(nc, 100 + width)
+    d, o = make_rays(N, 5 + width)
+    g = torch.Generator().manual_seed(1)
+    if per_ray:                   # sorted depths of each ray's own, as the pdf sampler hands them to the fine pass (no jitter: the rows hold it)
+        z = torch.sort(cfg.near + (cfg.far - cfg.near) * torch.rand(N, S, generator=g), dim=1).values.contiguous()
+        depth_args = lambda: dict(zgrid=None, jitter=None, z_rows=z.to(dev))
+    else:
+        jitter = torch.rand(N, 1, generator=g) * (cfg.far - cfg.near) / S
+        zg = torch.linspace(cfg.near, cfg.far, S)
+        z = zg.unsqueeze(0) + jitter
+        depth_args = lambda: dict(zgrid=zg.to(dev), jitter=jitter.reshape(-1).to(dev).contiguous())
+    xyz = (o.unsqueeze(1) + d.unsqueeze(1) * z.unsqueeze(2)).reshape(-1, 3)
+    dirs = d.unsqueeze(1).expand(-1, S, -1).reshape(-1, 3)
+    x_enc = O.embed(xyz, step_r, cfg)
+    ref, hidden, sh = O.mlp_forward(p, nc, x_enc, dirs, return_hidden=True)
+
+    flat = flat_params(nc, p, dev)
+    bw = O.barf_weights(step_r, cfg).to(dev)
+    res = {}
+    for precision in (P, PX):
+        packed = ops.pack_weights(net, flat, precision=precision)
+        save, _, _ = alloc_ff(ops, net, rows, dev, precision)
+        out = torch.full((N, S, 4), float("nan"), device=dev)
+        out2 = torch.full((N, S, 4), float("nan"), device=dev)
+        ka = depth_args()
+        ops.mlp_fwd(net, flat, packed, o.to(dev), d.to(dev), ka.pop("zgrid"), ka.pop("jitter"), bw, out, save=save, precision=precision, **ka)
+        ka = depth_args()
+        ops.mlp_fwd(net, flat, packed, o.to(dev), d.to(dev), ka.pop("zgrid"), ka.pop("jitter"), bw, out2, precision=precision, **ka)
+        torch.cuda.synchronize()
+        res[precision] = (out, out2, save)
+    (out, out2, save), (out_x, _, save_x) = res[P], res[PX]
+
+    # ---- against f16x3, bit for bit
+    assert torch.equal(out, out_x)
+    assert torch.equal(out, out2)                          # the no-save instantiation
+    assert torch.equal(save.mask, save_x.mask)
+    assert torch.equal(save.sh, save_x.sh)
+    tiles = covered_tiles(rows, width)
+    assert_hi_planes("activations", save.act, save_x.act, D + 2, width // 16, tiles)
+    assert_hi_planes("encoding", save.enc, save_x.enc, 1, 4, tiles)
+
+    # ---- against the oracle, layer by layer: f16 round-to-nearest of the split (2^-11 relative) on top of the chain's own 2e-5 (2e-6
+    #      on the encoding, tests/test_mlpx3_gpu.py::test_x3_fwd_dense; there the rounding applies to the kernel's value, hence 1 + 2^-11)
+    sx = ops.SPLIT_SCALE_X
+    raw = ops.decode_frags_16(save.act, D + 2, width, rows, P).cpu()
+    enc = ops.decode_frags_16(save.enc, 1, 64, rows, P)[0][:, :63].cpu().double() / sx
+    worst = 0.0
+    e = (enc - x_enc.double()).abs()
+    assert bool((e <= 2.0 ** -11 * x_enc.double().abs() + 2e-6 * (1 + 2.0 ** -11)).all()), f"encoding: {float(e.max()):.3e}"
+    for l, h in enumerate(hidden):
+        e = (raw[l].double() / sx - h.double()).abs()
+        bound = 2.0 ** -11 * h.double().abs() + 2e-5
+        worst = max(worst, float((e / bound).max()))
+        assert bool((e <= bound).all()), f"layer {l}: worst error {float(e.max()):.3e}, {float((e / bound).max()):.2f} of its bound"
+    assert maxerr(ops.decode_sh_x3(save.sh, rows)[:, :27], sh) < 2e-5
+    e_out = maxerr(out.view(-1, 4), ref)
+    print(f"[x3h dense W={width} barf={barf} per_ray={per_ray}] hi planes: worst error {worst:.3f} of 2^-11 |h| + 2e-5; out {e_out:.1e}")
+    assert e_out < 2e-5
+    masks = ops.decode_masks_16(save.mask, D + 2, width, rows)
+    assert torch.equal(masks, raw > 0)
+
+
+@pytest.mark.parametrize("width", [32, 64, 128, 256])
+@pytest.mark.parametrize("barf", [False, True])
+def test_x3h_fwd_dense(gpu_device, width, barf):
+    """Dense grid, ragged row count: output, ReLU words, sh.2 tile and every saved hi plane equal f16x3's bit for bit; the hi planes
+    within 2^-11 |h| + 2e-5 of the oracle's hidden layers; the ReLU bits are those of the saved planes."""
+    dense_case(gpu_device, width, barf, per_ray=False)
+
+
+def test_x3h_fwd_dense_per_ray_depths(gpu_device):
+    """The same with per-ray depth rows `z_rows` [N, S] (what the pdf sampler feeds the fine pass) instead of the shared grid."""
+    dense_case(gpu_device, 256, True, per_ray=True)
+
+
+# --------------------------------------------------------------------------------------------------------------------- 2 - 4: indexed
+def indexed_case(dev, width, N, S, K=None, seed=0):
+    """Rays, a (ray, sample) list of about 60 % of the (N, S) grid in torch.nonzero order (its first K entries when K is given), the
+    net of this width with a skip layer, BARF on."""
+    ops = _ops()
+    nc = NETS[width]
+    c = SimpleNamespace(nc=nc, net=net_of(nc), N=N, S=S, step_r=0.6)
+    c.cfg = O.RenderCfg(samples=20, scale=2, coarse=nc, fine=nc, barf_mode=True, barf_start=0.2, barf_end=0.9)
+    c.p = O.init_params(nc, 200 + width + seed)
+    c.d, c.o = make_rays(N, 9 + width + seed)
+    g = torch.Generator().manual_seed(2 + seed)
+    c.jitter = torch.rand(N, 1, generator=g) * 0.2
+    c.zg = torch.linspace(c.cfg.near, c.cfg.far, S)
+    idx = torch.nonzero(torch.rand(N, S, generator=g) < 0.6)
+    if K is not None:
+        assert idx.shape[0] >= K, (idx.shape[0], K)
+        idx = idx[:K]
+    c.idx, c.K, c.gen = idx, idx.shape[0], g
+    c.flat = flat_params(nc, c.p, dev)
+    c.bw = O.barf_weights(c.step_r, c.cfg).to(dev)
+    c.dev_in = (c.o.to(dev), c.d.to(dev), c.zg.to(dev), c.jitter.reshape(-1).to(dev).contiguous())
+    return c
+
+
+def listed_mask(c, count, dev):
+    m = torch.zeros(c.N, c.S, dtype=torch.bool, device=dev)
+    ix = c.idx[:count].to(dev)
+    m[ix[:, 0], ix[:, 1]] = True
+    return m
+
+
+def run_chain(dev, c, precision, cap, count, d_out, gmax, bwd=True, dw=True):
+    """forward (saving) -> backward -> weight gradient of one mode over the first `count` list entries, workspaces 0xFF-filled."""
+    ops = _ops()
+    net = c.net
+    packed = ops.pack_weights(net, c.flat, precision=precision)
+    idx_d = torch.zeros(cap, 2, dtype=torch.int32, device=dev)
+    n = min(cap, c.K)
+    idx_d[:n] = c.idx[:n].to(torch.int32).to(dev)
+    cnt = torch.tensor([count], dtype=torch.int32, device=dev)
+    od, dd, zd, jd = c.dev_in
+    r = SimpleNamespace(out=torch.full((c.N, c.S, 4), 7.0, device=dev), grads=torch.zeros_like(c.flat),
+                        d_o=torch.zeros(c.N, 3, device=dev), d_d=torch.zeros(c.N, 3, device=dev))
+    r.save, r.dy, r.dsh = alloc_ff(ops, net, cap, dev, precision)
+    ops.mlp_fwd(net, c.flat, packed, od, dd, zd, jd, c.bw, r.out, idx=idx_d, count=cnt, max_rows=cap, save=r.save, precision=precision)
+    if bwd:
+        ops.mlp_bwd(net, c.flat, packed, od, dd, zd, jd, c.bw, r.out, d_out, r.save, r.dy, r.dsh, r.d_o, r.d_d,
+                    idx=idx_d, count=cnt, max_rows=cap, precision=precision, gmax=gmax)
+        if dw:
+            ops.mlp_dw(net, r.save, r.dy, r.dsh, r.grads, cap, count=cnt, precision=precision, gmax=gmax)
+    torch.cuda.synchronize()
+    return r
+
+
+def assert_planes_match(c, h, x, rows):
+    """Every hi plane of the forward's and the backward's workspaces against f16x3's, over the tiles a launch on `rows` rows covers."""
+    D, W = c.nc.depth, c.nc.width
+    tiles = covered_tiles(rows, W)
+    assert torch.equal(h.save.mask, x.save.mask)
+    assert torch.equal(h.save.sh, x.save.sh)
+    assert_hi_planes("activations", h.save.act, x.save.act, D + 2, W // 16, tiles)
+    assert_hi_planes("encoding", h.save.enc, x.save.enc, 1, 4, tiles)
+    assert_hi_planes("dy", h.dy, x.dy, D + 2, W // 16, tiles)
+    assert_hi_planes("dsh", h.dsh, x.dsh, 1, 2, tiles)
+
+
+@pytest.mark.parametrize("width", [32, 64, 128, 256])
+def test_x3h_fwd_bwd_dw_indexed(gpu_device, width):
+    """Fine-pass mode at the small shape: forward against the oracle, ray gradients against fp64 autograd and against f16x3, the dY
+    planes against f16x3's bit for bit and zero past the count, every weight gradient against the fp64 GEMM of its own operands
+    (2e-5) and against f16x3's (the operand-rounding gate of tests/test_model_gpu.py::test_f16x3h_runs_the_f16x3_chains)."""
+    ops = _ops()
+    dev = gpu_device
+    c = indexed_case(dev, width, N=29, S=40)
+    nc, net, K = c.nc, c.net, c.K
+    r_, j_ = c.idx[:, 0], c.idx[:, 1]
+    gout = torch.randn(K, 4, generator=c.gen) * 1e-4          # gradient magnitudes of a mean-reduced loss
+    z = c.zg.unsqueeze(0) + c.jitter
+    with torch.no_grad():                                      # fp32 oracle: the sample positions round as the kernel's do
+        ref = O.mlp_forward(c.p, nc, O.embed(c.o[r_] + c.d[r_] * z[r_, j_].unsqueeze(-1), c.step_r, c.cfg), c.d[r_])
+    p64 = {k: v.double().requires_grad_(True) for k, v in c.p.items()}
+    d64, o64 = c.d.double().requires_grad_(True), c.o.double().requires_grad_(True)
+    ref64 = O.mlp_forward(p64, nc, O.embed(o64[r_] + d64[r_] * z.double()[r_, j_].unsqueeze(-1), c.step_r, c.cfg), d64[r_])
+    (ref64 * gout.double()).sum().backward()
+
+    cap = K + 17
+    listed = listed_mask(c, K, dev)
+    d_out = torch.zeros(c.N, c.S, 4, device=dev)
+    d_out[r_.to(dev), j_.to(dev)] = gout.to(dev)
+    gmax = d_out.abs().max().reshape(1).view(torch.int32)      # what composite_bwd hands to the backward
+    h = run_chain(dev, c, P, cap, K, d_out, gmax)
+    x = run_chain(dev, c, PX, cap, K, d_out, gmax)
+
+    assert torch.all(h.out[~listed] == 7.0)                    # untouched elsewhere
+    assert maxerr(h.out[r_.to(dev), j_.to(dev)], ref) < 2e-5
+    assert torch.equal(h.out, x.out)
+    # ray gradients: the oracle's, and f16x3's up to the order of the lane atomics
+    e_o, e_d = maxerr(h.d_o, o64.grad), maxerr(h.d_d, d64.grad)
+    assert e_o < 2e-5 * max(1.0, float(o64.grad.abs().max())), (e_o, float(o64.grad.abs().max()))
+    assert e_d < 2e-5 * max(1.0, float(d64.grad.abs().max())), (e_d, float(d64.grad.abs().max()))
+    assert float((h.d_o - x.d_o).abs().max()) <= 1e-6 * float(x.d_o.abs().max())
+    assert float((h.d_d - x.d_d).abs().max()) <= 1e-6 * float(x.d_d.abs().max())
+    assert_planes_match(c, h, x, K)
+    assert_zero_past(ops, nc, h.dy, h.dsh, K)
+    # dW: exactly the GEMM of the operands it read ...
+    sg = grad_scale(float(d_out.abs().max()))
+    worst, worst_name = assert_dw_exact(ops, net, h.grads, dw_operand_reference(ops, nc, h.save, h.dy, h.dsh, K, sg), f"W={width}")
+    # ... and f16x3's up to the rounding of the operands to 11 bits
+    gnet = float(x.grads.abs().max())
+    rnd = 0.0
+    for off, shp, name in zip(ops.param_offsets(net), net.shapes(), net.names()):
+        n = int(np.prod(shp))
+        ga, gb = x.grads[off:off + n], h.grads[off:off + n]
+        e, gt = float((ga - gb).abs().max()), float(ga.abs().max())
+        rnd = max(rnd, e / max(gt, 5e-4 * gnet))
+        assert e <= max(1e-3 * gt, 5e-7 * gnet), (name, e, gt, gnet)
+    print(f"[x3h indexed W={width}] {K} rows: d_o {e_o:.1e} d_d {e_d:.1e}; dW vs fp64 GEMM of its operands: worst {worst:.1e} of max|ref| "
+          f"({worst_name}); dW vs f16x3: worst {rnd:.1e} of a tensor's max")
+
+
+@pytest.mark.parametrize("width", [32, 64, 128, 256])
+def test_x3h_multi_pass_ragged(gpu_device, width):
+    """3 C R + 37 listed rows on C compute units (R rows per pass): every workgroup of the chains runs three passes and the first a
+    fourth, ragged one; the weight-gradient kernel streams > 100 tiles per workgroup (stage ring full, wait ladder at every range's
+    tail).  Skip layer merged into one segment at widths 128 / 256, split at 32 / 64."""
+    ops = _ops()
+    dev = gpu_device
+    C = torch.cuda.get_device_properties(dev).multi_processor_count
+    R = pass_rows(width)
+    K = 3 * C * R + 37
+    S = 64
+    N = -(-K // int(S * 0.55))                                 # 60 % of the grid is listed: enough for K entries
+    c = indexed_case(dev, width, N=N, S=S, K=K, seed=1)
+    nc, net = c.nc, c.net
+    cap = K + 64
+    listed = listed_mask(c, K, dev)
+    d_out = torch.randn(N, S, 4, device=dev, generator=torch.Generator(device=dev).manual_seed(3)) * 1e-4
+    gmax = d_out.abs().max().reshape(1).view(torch.int32)
+    h = run_chain(dev, c, P, cap, K, d_out, gmax)
+    x = run_chain(dev, c, PX, cap, K, d_out, gmax, dw=False)
+
+    assert torch.equal(h.out, x.out)
+    assert torch.all(h.out[~listed] == 7.0)
+    assert_planes_match(c, h, x, K)
+    del x
+    assert_zero_past(ops, nc, h.dy, h.dsh, K)
+    # oracle on a subset of the rows (the whole list takes a while on the CPU)
+    sub = torch.randperm(K, generator=c.gen)[:4000]
+    r_, j_ = c.idx[sub, 0], c.idx[sub, 1]
+    z = c.zg.unsqueeze(0) + c.jitter
+    ref = O.mlp_forward(c.p, nc, O.embed(c.o[r_] + c.d[r_] * z[r_, j_].unsqueeze(-1), c.step_r, c.cfg), c.d[r_])
+    e_out = maxerr(h.out[r_.to(dev), j_.to(dev)], ref)
+    assert e_out < 2e-5
+    sg = grad_scale(float(d_out.abs().max()))
+    worst, worst_name = assert_dw_exact(ops, net, h.grads, dw_operand_reference(ops, nc, h.save, h.dy, h.dsh, K, sg), f"W={width}")
+    print(f"[x3h multi-pass W={width}] {C} CUs, {K} rows: out {e_out:.1e}; dW vs fp64 GEMM of its operands: worst {worst:.1e} of max|ref| "
+          f"({worst_name})")
+
+
+def count_case(dev, width):
+    c = indexed_case(dev, width, N=29, S=40)
+    d_out = torch.zeros(c.N, c.S, 4, device=dev)
+    d_out[c.idx[:, 0].to(dev), c.idx[:, 1].to(dev)] = (torch.randn(c.K, 4, generator=c.gen) * 1e-4).to(dev)
+    return c, 2 * pass_rows(width) + 64, d_out, d_out.abs().max().reshape(1).view(torch.int32)
+
+
+@pytest.mark.parametrize("width", [64, 256])
+@pytest.mark.parametrize("edge", ["1", "31", "32", "33", "R", "R+1"])
+def test_x3h_count_edges(gpu_device, width, edge):
+    """Device-side counts around a tile and around a pass: output touched on exactly the first `count` list entries and equal to
+    f16x3's there, dY zero past the count, the weight gradient exactly the GEMM of rows [0, count)."""
+    ops = _ops()
+    dev = gpu_device
+    R = pass_rows(width)
+    count = {"R": R, "R+1": R + 1}.get(edge) or int(edge)
+    c, cap, d_out, gmax = count_case(dev, width)
+    assert count <= c.K
+    h = run_chain(dev, c, P, cap, count, d_out, gmax)
+    x = run_chain(dev, c, PX, cap, count, d_out, gmax, bwd=False)
+    listed = listed_mask(c, count, dev)
+    assert int(listed.sum()) == count
+    assert torch.all(h.out[~listed] == 7.0)
+    assert torch.equal(h.out, x.out) and bool(torch.isfinite(h.out[listed]).all())
+    tiles = covered_tiles(count, width)
+    assert_hi_planes("activations", h.save.act, x.save.act, c.nc.depth + 2, width // 16, tiles)
+    assert_hi_planes("encoding", h.save.enc, x.save.enc, 1, 4, tiles)
+    assert_zero_past(ops, c.nc, h.dy, h.dsh, count)
+    sg = grad_scale(float(d_out.abs().max()))
+    worst, worst_name = assert_dw_exact(ops, c.net, h.grads, dw_operand_reference(ops, c.nc, h.save, h.dy, h.dsh, count, sg), f"W={width} count={count}")
+    print(f"[x3h count W={width}] count {count}: dW vs fp64 GEMM of its operands: worst {worst:.1e} of max|ref| ({worst_name})")
+
+
+@pytest.mark.parametrize("width", [64, 256])
+def test_x3h_count_zero(gpu_device, width):
+    """count = 0: the three kernels return at their entry guards (before any row index is clamped to count - 1): nothing is written."""
+    dev = gpu_device
+    c, cap, d_out, gmax = count_case(dev, width)
+    h = run_chain(dev, c, P, cap, 0, d_out, gmax)
+    assert torch.all(h.out == 7.0)
+    assert torch.all(h.grads == 0) and torch.all(h.d_o == 0) and torch.all(h.d_d == 0)
+    for b in (h.save.act, h.save.enc, h.save.sh, h.save.mask, h.dy, h.dsh):
+        assert bool((b.view(torch.uint8) == 0xFF).all())
