@@ -1,4 +1,4 @@
-// Launcher interface of the multi-camera ray preamble (multicam.hip) between the C ABI (api.hip) and its kernels.  A header of its
+// Launcher interface of the multi-camera ray preamble (rays.hip) between the C ABI (api.hip) and its kernels.  A header of its
 // own: mcnerf_kernels.h is part of the digest that ties the recorded MLP-kernel traffic (profiles/pmc_traffic_*.json) to the sources.
 #pragma once
 #include "mcnerf_common.h"

@@ -1,23 +1,10 @@
-// The ray preamble of a MULTI-CAMERA train step (`cams_per_step` > 1, a sys_param key of this build): the batch is K
-// segments of consecutive rays, segment k = n_k rays of camera cam_k.  One launch draws every segment's pixels, generates the rays
-// from that camera's pose / inverse intrinsics and gathers the ground truth from that camera's resident uint8 image -- what
-// sample_perm_kernel + raygen_fwd_kernel + gather_gt_kernel (select_raygen.hip) do for one camera in three launches, and with their
-// bits.  Replaces MC_Model.get_rays + generate_rand_rays and the ground-truth gather (model/mc_nerf.py:124-145, 327-345, 379, 80)
-// for a batch that spans cameras; the reference has no such step.
-// The segment table travels by value in the kernel arguments (McnSegTable): no host-device copy, no host synchronisation.
-//
-// The per-ray device functions below RESTATE the arithmetic of the single-camera kernels, operation for operation.  They are not
-// shared with select_raygen.hip: calling them from there re-ordered the operands of commutative instructions in sample_perm_kernel,
-// raygen_fwd_kernel and raygen_bwd_kernel (scripts/device_code_diff.py: same results, other instruction streams), and those
-// kernels' code objects stay as they are.  Every multiply / add that decides a bit is either an explicit __f*_rn or compiled with
-// -ffp-contract=off, so equal text gives equal bits; tests/test_multicam_gpu.py holds the two files to torch.equal.
-#include "mcnerf_multicam.h"
-
-__device__ __forceinline__ unsigned mc_key(unsigned seed, unsigned i) {
-    unsigned x = i * 0x9E3779B9u + seed;          // murmur3 finaliser: every output bit depends on every input bit
-    x ^= x >> 16; x *= 0x85EBCA6Bu; x ^= x >> 13; x *= 0xC2B2AE35u; x ^= x >> 16;
-    return x;
-}
+// The per-ray device arithmetic of the ray preamble, defined ONCE: the pixel permutation, the forward ray formula, the backward's
+// per-ray terms and block flush, the ground-truth colour.  The single-camera kernels and the multi-camera ray-batch kernels (rays.hip)
+// both call these functions, so they produce the same bits by construction.  Every multiply / add that decides a bit is either an
+// explicit __f*_rn or compiled with -ffp-contract=off: do not re-associate an expression here.
+// P [12] = one camera's world->cam [R|t] row-major and K [9] = its inverse intrinsics, in LDS or global memory.
+#pragma once
+#include "mcnerf_hash.h"
 
 // P(i) of the keyed pseudo-random permutation P of [0, n): a 6-round balanced Feistel network on 2 * half bits (the smallest even
 // width covering n) with the murmur finaliser as round function, cycle-walked back into [0, n).
@@ -32,7 +19,7 @@ __device__ __forceinline__ unsigned mcn_feistel_perm(unsigned i, unsigned n, con
         unsigned L = x >> half, R = x & mask;
 #pragma unroll
         for (unsigned r = 0; r < 6; ++r) {
-            const unsigned f = mc_key(sd + 0x632BE5ABu * (r + 1), R) & mask;
+            const unsigned f = mcn_hash32(sd + 0x632BE5ABu * (r + 1), R) & mask;
             const unsigned nl = R;
             R = L ^ f; L = nl;
         }
@@ -135,60 +122,4 @@ __device__ __forceinline__ void mcn_gt_of_pixel(const unsigned char* __restrict_
     } else {
         out[i * 3 + 0] = r; out[i * 3 + 1] = g; out[i * 3 + 2] = b;
     }
-}
-
-// One thread per ray i.  Its segment is found by a scan of the table: every table word is a wave-uniform scalar load and the ray
-// keeps the last segment that starts at or before it (empty segments are passed over; the host checked that start is monotone from
-// 0 to n).  The camera's 21 matrix floats are read per ray through the cache: a block may straddle segments, so they cannot be
-// staged once per block as raygen_fwd_kernel does.
-__global__ __launch_bounds__(256) void ray_batch_fwd_kernel(McnRayBatchArgs a, McnSegTable t) {
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= a.n) return;
-    int k = 0, cam = t.cam[0], lo = 0;
-    for (int s = 1; s < t.K; ++s) {
-        const int st = t.start[s];
-        if (i >= st) { k = s; cam = t.cam[s]; lo = st; }
-    }
-    const unsigned npix = (unsigned)a.H * (unsigned)a.W;
-    // segment k's own permutation of [0, H W): key *seed + k * 0x9E3779B9 (mod 2^32), so segment 0 draws what sample_perm_kernel draws
-    const long long pid = a.pix_in ? a.pix_in[i] : (long long)mcn_feistel_perm((unsigned)(i - lo), npix, a.seed, (unsigned)k * 0x9E3779B9u);
-    a.pix_out[i] = pid;
-    mcn_ray_of_pixel(a.pose + (size_t)cam * 12, a.kinv + (size_t)cam * 9, pid, a.W, a.rays_d, a.rays_o, i);
-    if (a.images) mcn_gt_of_pixel(a.images + ((size_t)cam * npix + (size_t)pid) * a.channels, a.channels, a.gt, i);
-}
-
-hipError_t mcn_launch_ray_batch_fwd(const McnRayBatchArgs& a, const McnSegTable& t, hipStream_t st) {
-    if (a.n <= 0) return hipSuccess;
-    hipLaunchKernelGGL(ray_batch_fwd_kernel, dim3((a.n + 255) / 256), dim3(256), 0, st, a, t);
-    return hipGetLastError();
-}
-
-// Backward: blockIdx.y = segment.  A block grid-strides over its OWN segment only, so all its rays share one camera: the matrices
-// are staged in LDS and the 21 accumulators reduced as in raygen_bwd_kernel, then one atomic per block and value goes into that
-// camera's rows of d_pose [C,3,4] / d_kinv [C,3,3] (a camera listed in two segments receives both; the caller zeroes the outputs).
-__global__ __launch_bounds__(256) void ray_batch_bwd_kernel(McnRayBatchBwdArgs a, McnSegTable t) {
-    __shared__ float P[12], K[9];
-    __shared__ float red[4][24];
-    const int seg = blockIdx.y, cam = t.cam[seg], lo = t.start[seg], hi = t.start[seg + 1];
-    if (lo + (int)(blockIdx.x * blockDim.x) >= hi) return;          // (block-uniform: no ray of this segment for this block)
-    if (threadIdx.x < 12) P[threadIdx.x] = a.pose[(size_t)cam * 12 + threadIdx.x];
-    if (threadIdx.x < 9) K[threadIdx.x] = a.kinv[(size_t)cam * 9 + threadIdx.x];
-    __syncthreads();
-    float acc[21];
-#pragma unroll
-    for (int k = 0; k < 21; ++k) acc[k] = 0.f;
-    for (int i = lo + blockIdx.x * blockDim.x + threadIdx.x; i < hi; i += gridDim.x * blockDim.x) {
-        mcn_raygen_bwd_ray(P, K, a.pix, a.W, a.d_rays_d, a.d_rays_o, i, acc);
-    }
-    mcn_raygen_bwd_flush(acc, P, red, a.d_pose + (size_t)cam * 12, a.d_kinv + (size_t)cam * 9);
-}
-
-hipError_t mcn_launch_ray_batch_bwd(const McnRayBatchBwdArgs& a, const McnSegTable& t, hipStream_t st) {
-    int longest = 0;
-    for (int k = 0; k < t.K; ++k) longest = max(longest, t.start[k + 1] - t.start[k]);
-    if (longest <= 0) return hipSuccess;
-    int gx = (longest + 255) / 256;
-    if (gx > 512) gx = 512;
-    hipLaunchKernelGGL(ray_batch_bwd_kernel, dim3(gx, t.K), dim3(256), 0, st, a, t);
-    return hipGetLastError();
 }

@@ -1,11 +1,12 @@
-// (1) Weight-threshold fine-sample selection + compaction, entirely on the device:
-//     replaces nonzero / expand / arithmetic / index_put of model/mc_nerf.py:623-629, 692-694 and
-//     removes the reference's host syncs (.item(), nonzero).
-// (2) Per-pixel ray generation from one camera's world->cam pose and inverse intrinsics, forward and
-//     backward: replaces MC_Model.get_rays + generate_rand_rays (model/mc_nerf.py:124-145, 213-256,
-//     327-345) for the selected pixels only.
+// What the fine pass needs between the coarse weights and the fine MLP, entirely on the device:
+// (1) Weight-threshold fine-sample selection + compaction (count / scan / write): replaces nonzero / expand / arithmetic / index_put
+//     of model/mc_nerf.py:623-629, 692-694 and removes the reference's host syncs (.item(), nonzero).  The scan also serves voxel.hip.
+// (2) The random cap of the selected list (model/mc_nerf.py:630-632): cap_gather replays a given permutation, cap_random draws the
+//     subset on the device.
+// (3) The stand-alone positional encoding and its backward, and upload_f32 (small host values as kernel arguments).
 #include "mcnerf_kernels.h"
 #include "mcnerf_voxel.h"
+#include "mcnerf_hash.h"
 
 // ------------------------------------------------------------------ selection
 __device__ __forceinline__ float sel_threshold(const McnSelectArgs& a) {
@@ -145,21 +146,16 @@ hipError_t mcn_launch_cap_gather(const int2* idx_in, const long long* perm, int 
 
 // ---- The random cap of model/mc_nerf.py:630-632 without a host round trip.  The reference keeps idx[randperm(K)[:keep]]
 // when K > keep: a uniformly random subset of size `keep` (the order of the list never reaches a result).  Here every
-// entry i < K gets a 32-bit key hash(seed, i) and the `keep` smallest keys are kept: two 65536-bin histogram passes find
+// entry i < K gets a 32-bit key mcn_hash32(seed, i) and the `keep` smallest keys are kept: two 65536-bin histogram passes find
 // the exact threshold key, a counting pass and an ordered compaction write the kept entries in list order.  K <= keep keeps everything.
 // ws (uint32): [0 .. 65535] histogram of the high 16 key bits, [65536 .. 131071] histogram of the low 16 bits inside the
 // boundary bin, [131072] boundary bin (0x10000 = keep all), [131073] entries below it, [131074] threshold key,
 // [131075] ties to take at the threshold, [MCN_CAP_LT + b] / [MCN_CAP_EQ + b] entries of chunk b below / at the threshold.
-__device__ __forceinline__ unsigned cap_key(unsigned seed, unsigned i) {
-    unsigned x = i * 0x9E3779B9u + seed;          // murmur3 finaliser: every output bit depends on every input bit
-    x ^= x >> 16; x *= 0x85EBCA6Bu; x ^= x >> 13; x *= 0xC2B2AE35u; x ^= x >> 16;
-    return x;
-}
 __global__ __launch_bounds__(256) void cap_hist_hi_kernel(const int* count, int max_rows, int keep, const unsigned* seed, unsigned* ws) {
     const int K = min(*count, max_rows);
     if (K <= keep) return;
     const unsigned sd = *seed;
-    for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < K; i += gridDim.x * blockDim.x) atomicAdd(&ws[cap_key(sd, i) >> 16], 1u);
+    for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < K; i += gridDim.x * blockDim.x) atomicAdd(&ws[mcn_hash32(sd, i) >> 16], 1u);
 }
 // one workgroup: first bin whose inclusive prefix reaches `target`; writes (bin, prefix before it)
 __device__ void cap_find(const unsigned* hist, unsigned target, unsigned* out_bin, unsigned* out_below) {
@@ -189,7 +185,7 @@ __global__ __launch_bounds__(256) void cap_hist_lo_kernel(const int* count, int 
     if (K <= keep) return;
     const unsigned sd = *seed, bin = ws[131072];
     for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < K; i += gridDim.x * blockDim.x) {
-        const unsigned k = cap_key(sd, i);
+        const unsigned k = mcn_hash32(sd, i);
         if ((k >> 16) == bin) atomicAdd(&ws[65536 + (k & 0xFFFFu)], 1u);
     }
 }
@@ -215,7 +211,7 @@ __global__ __launch_bounds__(256) void cap_count_kernel(const int* count, int ma
     const int chunk = cap_chunk(K, gridDim.x), lo = blockIdx.x * chunk, hi = min(K, lo + chunk);
     unsigned lt = 0, eq = 0;
     for (int i = lo + threadIdx.x; i < hi; i += 256) {
-        const unsigned k = cap_key(sd, (unsigned)i);
+        const unsigned k = mcn_hash32(sd, (unsigned)i);
         lt += k < thr; eq += k == thr;
     }
 #pragma unroll
@@ -257,7 +253,7 @@ __global__ __launch_bounds__(256) void cap_write_kernel(const int2* idx_in, cons
     unsigned pos = lt + min(eq_run, ties);
     for (int base = lo; base < hi; base += 256) {
         const int i = base + threadIdx.x;
-        const unsigned k = i < hi ? cap_key(sd, (unsigned)i) : 0xFFFFFFFFu;
+        const unsigned k = i < hi ? mcn_hash32(sd, (unsigned)i) : 0xFFFFFFFFu;
         const bool is_eq = i < hi && k == thr;
         unsigned n_eq, n_sel;
         const unsigned tie_rank = cap_block_rank(is_eq, wsum, n_eq);
@@ -327,37 +323,6 @@ hipError_t mcn_launch_encode_bwd(const float* x, const float* barf_w, int n, int
     return hipGetLastError();
 }
 
-// ---- The pixel subset of a train step: randperm(H * W)[:batch] (model/mc_nerf.py:329, a uniformly random ordered subset
-// without replacement) as `batch` evaluations of a keyed pseudo-random PERMUTATION of [0, n): a 6-round balanced Feistel
-// network on 2 * half bits (the smallest even width covering n) with the murmur finaliser as round function, cycle-walked
-// back into [0, n) (the domain is < 4 n, so < 4 walks on average).  One 7 us kernel instead of the 22 kernels of a
-// device randperm of 640 000 keys (radix sort + merges, 0.2 ms/step).
-__global__ __launch_bounds__(256) void sample_perm_kernel(long long* out, unsigned n, int batch, const unsigned* seed) {
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= batch) return;
-    int bits = 1;
-    while (bits < 32 && (1ull << bits) < n) ++bits;
-    const int half = (bits + 1) / 2;
-    const unsigned mask = (1u << half) - 1u, sd = *seed;
-    unsigned x = (unsigned)i;
-    do {
-        unsigned L = x >> half, R = x & mask;
-#pragma unroll
-        for (unsigned r = 0; r < 6; ++r) {
-            const unsigned f = cap_key(sd + 0x632BE5ABu * (r + 1), R) & mask;
-            const unsigned nl = R;
-            R = L ^ f; L = nl;
-        }
-        x = (L << half) | R;
-    } while (x >= n);
-    out[i] = (long long)x;
-}
-hipError_t mcn_launch_sample_perm(long long* out, long long n, int batch, const unsigned* seed, hipStream_t st) {
-    if (batch <= 0) return hipSuccess;
-    hipLaunchKernelGGL(sample_perm_kernel, dim3((batch + 255) / 256), dim3(256), 0, st, out, (unsigned)n, batch, seed);
-    return hipGetLastError();
-}
-
 // up to 16 host floats by value (kernel arguments) -> device memory: a stream-ordered upload that never blocks the host
 struct McnFloats16 { float v[16]; };
 __global__ void upload_f32_kernel(float* dst, McnFloats16 vals, int n) {
@@ -367,137 +332,5 @@ hipError_t mcn_launch_upload_f32(float* dst, const float* host_vals, int n, hipS
     McnFloats16 v = {};
     for (int i = 0; i < n && i < 16; ++i) v.v[i] = host_vals[i];
     hipLaunchKernelGGL(upload_f32_kernel, dim3(1), dim3(64), 0, st, dst, v, n);
-    return hipGetLastError();
-}
-
-// ------------------------------------------------------------------ ray generation
-// d = normalize(R^T K^-1 [u+.5, v+.5, 1]^T), o = -R^T t, following the reference's op order
-// (pix @ K^-T, lift, @ pose_inv^T, minus origin, normalise) so results agree to ~1e-7.
-__global__ __launch_bounds__(256) void raygen_fwd_kernel(McnRaygenArgs a) {
-    __shared__ float P[12], K[9];
-    if (threadIdx.x < 12) P[threadIdx.x] = a.pose[threadIdx.x];
-    if (threadIdx.x < 9) K[threadIdx.x] = a.kinv[threadIdx.x];
-    __syncthreads();
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= a.n) return;
-    const long long pid = a.pix[i];
-    const float u = (float)(pid % a.W) + 0.5f, v = (float)(pid / a.W) + 0.5f;
-    float cam[3];
-#pragma unroll
-    for (int r = 0; r < 3; ++r) cam[r] = __fadd_rn(__fadd_rn(__fmul_rn(u, K[r * 3]), __fmul_rn(v, K[r * 3 + 1])), K[r * 3 + 2]);
-    float d[3], o[3];
-#pragma unroll
-    for (int c = 0; c < 3; ++c) {
-        // pose_inv row c = [R[0][c], R[1][c], R[2][c], -(R^T t)[c]]
-        const float ti = -(__fadd_rn(__fadd_rn(__fmul_rn(P[0 * 4 + c], P[3]), __fmul_rn(P[1 * 4 + c], P[7])), __fmul_rn(P[2 * 4 + c], P[11])));
-        const float w = __fadd_rn(__fadd_rn(__fadd_rn(__fmul_rn(cam[0], P[0 * 4 + c]), __fmul_rn(cam[1], P[1 * 4 + c])), __fmul_rn(cam[2], P[2 * 4 + c])), ti);
-        o[c] = ti;
-        d[c] = __fsub_rn(w, ti);
-    }
-    const float nrm = sqrtf(d[0] * d[0] + d[1] * d[1] + d[2] * d[2]);
-#pragma unroll
-    for (int c = 0; c < 3; ++c) { a.rays_d[i * 3 + c] = d[c] / nrm; a.rays_o[i * 3 + c] = o[c]; }
-}
-
-hipError_t mcn_launch_raygen_fwd(const McnRaygenArgs& a, hipStream_t st) {
-    if (a.n <= 0) return hipSuccess;
-    hipLaunchKernelGGL(raygen_fwd_kernel, dim3((a.n + 255) / 256), dim3(256), 0, st, a);
-    return hipGetLastError();
-}
-
-// Backward: accumulates d_pose[3][4] and d_kinv[3][3] over the n rays (block reduction + one atomic
-// per block and value).
-__global__ __launch_bounds__(256) void raygen_bwd_kernel(McnRaygenBwdArgs a) {
-    __shared__ float P[12], K[9];
-    __shared__ float red[4][24];
-    if (threadIdx.x < 12) P[threadIdx.x] = a.pose[threadIdx.x];
-    if (threadIdx.x < 9) K[threadIdx.x] = a.kinv[threadIdx.x];
-    __syncthreads();
-    float acc[21];
-#pragma unroll
-    for (int k = 0; k < 21; ++k) acc[k] = 0.f;
-    for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < a.n; i += gridDim.x * blockDim.x) {
-        const long long pid = a.pix[i];
-        const float p[3] = {(float)(pid % a.W) + 0.5f, (float)(pid / a.W) + 0.5f, 1.f};
-        float cam[3], q[3];
-#pragma unroll
-        for (int r = 0; r < 3; ++r) cam[r] = p[0] * K[r * 3] + p[1] * K[r * 3 + 1] + K[r * 3 + 2];
-#pragma unroll
-        for (int c = 0; c < 3; ++c) q[c] = cam[0] * P[c] + cam[1] * P[4 + c] + cam[2] * P[8 + c];
-        const float inv = 1.f / sqrtf(q[0] * q[0] + q[1] * q[1] + q[2] * q[2]);
-        const float gd[3] = {a.d_rays_d[i * 3], a.d_rays_d[i * 3 + 1], a.d_rays_d[i * 3 + 2]};
-        const float dn[3] = {q[0] * inv, q[1] * inv, q[2] * inv};
-        const float dot = dn[0] * gd[0] + dn[1] * gd[1] + dn[2] * gd[2];
-        float gq[3], gcam[3];
-#pragma unroll
-        for (int c = 0; c < 3; ++c) gq[c] = (gd[c] - dn[c] * dot) * inv;
-#pragma unroll
-        for (int j = 0; j < 3; ++j) {
-            gcam[j] = P[j * 4] * gq[0] + P[j * 4 + 1] * gq[1] + P[j * 4 + 2] * gq[2];
-#pragma unroll
-            for (int c = 0; c < 3; ++c) acc[j * 3 + c] += cam[j] * gq[c];        // dR[j][c] from the direction
-#pragma unroll
-            for (int k = 0; k < 3; ++k) acc[9 + j * 3 + k] += gcam[j] * p[k];     // dKinv[j][k]
-        }
-#pragma unroll
-        for (int c = 0; c < 3; ++c) acc[18 + c] += a.d_rays_o[i * 3 + c];         // sum of origin gradients
-    }
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-#pragma unroll
-    for (int k = 0; k < 21; ++k) {
-        float v = acc[k];
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-        if (lane == 0) red[wv][k] = v;
-    }
-    __syncthreads();
-    if (threadIdx.x < 21) {
-        const int k = threadIdx.x;
-        const float v = red[0][k] + red[1][k] + red[2][k] + red[3][k];
-        if (k < 9) atomicAdd(&a.d_pose[(k / 3) * 4 + (k % 3)], v);
-        else if (k < 18) atomicAdd(&a.d_kinv[k - 9], v);
-        else {
-            // o_c = -sum_j R[j][c] t_j:  dR[j][c] += -t_j * Go_c ;  dt_j = -sum_c R[j][c] Go_c
-            const int c = k - 18;
-#pragma unroll
-            for (int j = 0; j < 3; ++j) {
-                atomicAdd(&a.d_pose[j * 4 + c], -P[j * 4 + 3] * v);
-                atomicAdd(&a.d_pose[j * 4 + 3], -P[j * 4 + c] * v);
-            }
-        }
-    }
-}
-
-hipError_t mcn_launch_raygen_bwd(const McnRaygenBwdArgs& a, hipStream_t st) {
-    if (a.n <= 0) return hipSuccess;
-    int grid = (a.n + 255) / 256;
-    if (grid > 512) grid = 512;
-    hipLaunchKernelGGL(raygen_bwd_kernel, dim3(grid), dim3(256), 0, st, a);
-    return hipGetLastError();
-}
-
-// ------------------------------------------------------------------ device-resident images
-// GT colour of the selected pixels of one camera straight from uint8 images kept in HBM:
-//   rgb = rgb8/255 * a + (1 - a),  a = alpha8/255   (RGBA composited on white, data/data_read.py:130-137;
-//   ToTensor's /255 first, then the blend in fp32, as the reference does), or rgb8/255 for 3-channel images.
-// Replaces the 7.7 MB/step H2D copy of a float image plus `gt_rgbs.reshape(-1,3)[rand_idx]` (model/mc_nerf.py:379, 80).
-__global__ __launch_bounds__(256) void gather_gt_kernel(const unsigned char* __restrict__ img, int channels,
-                                                        const long long* __restrict__ pix, int n, float* __restrict__ out) {
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    const unsigned char* p = img + (size_t)pix[i] * channels;
-    const float r = (float)p[0] / 255.0f, g = (float)p[1] / 255.0f, b = (float)p[2] / 255.0f;
-    if (channels == 4) {
-        const float a = (float)p[3] / 255.0f;
-        out[i * 3 + 0] = r * a + (1.0f - a);
-        out[i * 3 + 1] = g * a + (1.0f - a);
-        out[i * 3 + 2] = b * a + (1.0f - a);
-    } else {
-        out[i * 3 + 0] = r; out[i * 3 + 1] = g; out[i * 3 + 2] = b;
-    }
-}
-hipError_t mcn_launch_gather_gt(const unsigned char* img, int channels, const long long* pix, int n, float* out, hipStream_t st) {
-    if (n <= 0) return hipSuccess;
-    hipLaunchKernelGGL(gather_gt_kernel, dim3((n + 255) / 256), dim3(256), 0, st, img, channels, pix, n, out);
     return hipGetLastError();
 }

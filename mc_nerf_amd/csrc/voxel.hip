@@ -10,7 +10,7 @@
 // linear index (ix * G + iy) * G + iz in 64 bits.  Sample j of ray n sits at p = o + d * z, z = zgrid[j] + jitter[n], every step a
 // separately rounded fp32 operation (as sample_pdf.hip forms its depths): the cell of a sample is a pure function of its inputs.
 //
-// SELECT: count per ray -> exclusive scan (select_scan_kernel of select_raygen.hip) -> ordered write.  The list is in torch.nonzero
+// SELECT: count per ray -> exclusive scan (select_scan_kernel of select.hip) -> ordered write.  The list is in torch.nonzero
 // (row-major) order and no atomic decides a position; the predicate is a gather vox[cell] > thresh (a NaN cell is empty).
 //
 // UPDATE, deterministic whatever the order of arrival: (1) every sample takes atomicMax of an order-preserving uint32 key of its

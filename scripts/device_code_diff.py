@@ -1,22 +1,22 @@
 """Compares the gfx950 device code of two builds of the library, kernel by kernel: for a change that must leave the GPU's
-instructions alone (host-side refactors, header moves).
+instructions alone (host-side refactors, header moves, kernels moved between source files).
 
     python scripts/device_code_diff.py <build dir A> <build dir B> [out.txt]      (build dir = mc_nerf_amd/build of a tree)
 
-Per object of build.SOURCES the gfx950 code object is extracted (llvm-objdump --offloading) and, per kernel symbol, compared:
-the set of kernels; the sequence of (encoding, instruction text) of each kernel -- addresses and the order of kernels inside
-an object are not compared, a host-side change of instantiation order permutes them; the kernel's metadata note (register
-counts, LDS, scratch, kernarg size and argument offsets).  One line per kernel; exit status 1 unless every line says identical.
+From every *.o of a build directory the gfx950 code object is extracted (llvm-objdump --offloading) and its kernels collected by
+symbol, whichever object holds them.  Per symbol are compared: the sequence of (encoding, instruction text) -- addresses, the
+order of kernels inside an object and the padding behind a kernel's last instruction are not compared, they depend on its neighbours; the kernel's metadata
+note (register counts, LDS, scratch, kernarg size and argument offsets).  One line per kernel, naming its object in A (and in B where
+it moved); a kernel that differs also gets its instruction count and VGPR / SGPR / LDS / scratch figures of both builds.  Exit
+status 1 unless every line says identical.
 """
+import glob
 import os
 import re
 import shutil
 import subprocess
 import sys
 import tempfile
-
-sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-from mc_nerf_amd import build  # noqa: E402
 
 LLVM = "/opt/rocm/lib/llvm/bin"
 
@@ -47,28 +47,44 @@ def kernels(elf):
             m = re.match(r"\s*(.*?)\s*//\s*[0-9A-Fa-f]+:\s*(.*)$", line)
             if m:
                 ins.append((m.group(2).strip(), m.group(1)))
+        while ins and ins[-1][1].split()[0] in ("s_nop", "s_code_end"):      # padding up to the next symbol: depends on the neighbour
+            ins.pop()
         code[name] = ins
     return {k: (code.get(k), meta[k]) for k in meta}
 
 
+def build_kernels(build_dir):
+    """{kernel symbol: (object name, [(encoding, instruction)], metadata note text)} over every *.o of a build directory"""
+    out = {}
+    for obj in sorted(glob.glob(os.path.join(build_dir, "*.o"))):
+        with tempfile.TemporaryDirectory() as tmp:
+            for name, (code, meta) in kernels(device_elf(obj, tmp)).items():
+                assert name not in out, f"{name} is in {out[name][0]} and in {os.path.basename(obj)}"
+                out[name] = (os.path.basename(obj), code, meta)
+    return out
+
+
+def figures(code, meta):
+    f = dict(re.findall(r"\.(vgpr_count|sgpr_count|group_segment_fixed_size|private_segment_fixed_size):\s+(\d+)", meta))
+    return (f"{len(code or ())} instructions, {f['vgpr_count']} VGPR, {f['sgpr_count']} SGPR, {f['group_segment_fixed_size']} B LDS, "
+            f"{f['private_segment_fixed_size']} B scratch")
+
+
 def main():
-    dir_a, dir_b = sys.argv[1:3]
+    ka, kb = build_kernels(sys.argv[1]), build_kernels(sys.argv[2])
     out = open(sys.argv[3], "w") if len(sys.argv) > 3 else sys.stdout
     different = 0
-    for src in build.SOURCES:
-        obj = src.replace(".hip", ".o")
-        with tempfile.TemporaryDirectory() as ta, tempfile.TemporaryDirectory() as tb:
-            ka, kb = kernels(device_elf(os.path.join(dir_a, obj), ta)), kernels(device_elf(os.path.join(dir_b, obj), tb))
-        for name in sorted(set(ka) | set(kb)):
-            if name not in ka or name not in kb:
-                verdict = "ONLY IN " + ("A" if name in ka else "B")
-            else:
-                (ca, ma), (cb, mb) = ka[name], kb[name]
-                what = [w for w, same in (("instructions", ca is not None and ca == cb), ("metadata", ma == mb)) if not same]
-                verdict = "identical" if not what else "DIFFERENT " + " + ".join(what)
-            different += verdict != "identical"
-            n = len(ka[name][0] or ()) if name in ka else 0
-            print(f"{obj:18s} {name:75s} {n:7d} instructions  {verdict}", file=out)
+    for name in sorted(set(ka) | set(kb), key=lambda k: ((ka.get(k) or kb[k])[0], k)):
+        obj, code, meta = ka.get(name) or kb[name]
+        if name not in ka or name not in kb:
+            verdict = "ONLY IN " + ("A" if name in ka else "B")
+        else:
+            ob, cb, mb = kb[name]
+            obj += "" if ob == obj else " -> " + ob
+            what = [w for w, same in (("instructions", code is not None and code == cb), ("metadata", meta == mb)) if not same]
+            verdict = "identical" if not what else f"DIFFERENT {' + '.join(what)}  [A: {figures(code, meta)}]  [B: {figures(cb, mb)}]"
+        different += verdict != "identical"
+        print(f"{obj:18s} {name:75s} {len(code or ()):7d} instructions  {verdict}", file=out)
     print(f"{different} kernel(s) not identical", file=out)
     return 1 if different else 0
 

@@ -1,5 +1,5 @@
-"""fp64 restatement of the ray formula of csrc/select_raygen.hip / csrc/multicam.hip (written from the kernels' comments) for a batch
-that spans cameras, differentiable by autograd:
+"""fp64 restatement of the ray formula of csrc/mcnerf_rays.h (written from its comments; every ray kernel of csrc/rays.hip calls it)
+for a batch that spans cameras, differentiable by autograd:
 
     u = pix % W + 0.5, v = pix // W + 0.5                      pixel centres, pix = v * W + u
     cam = Kinv [u, v, 1]^T                                      lift through the inverse intrinsics

@@ -28,7 +28,7 @@ def test_abi_declares_the_ray_batch_entry_points_and_keeps_its_version():
     from mc_nerf_amd import _lib, build
     hdr = open(os.path.join(ROOT, "include", "mcnerf.h")).read()
     code = re.sub(r"/\*.*?\*/", "", hdr, flags=re.S)
-    assert "multicam.hip" in build.SOURCES and os.path.isfile(os.path.join(build.CSRC, "multicam.hip"))
+    assert "rays.hip" in build.SOURCES and os.path.isfile(os.path.join(build.CSRC, "rays.hip"))
     lib = ctypes.CDLL(build.build(verbose=False))
     for name in SYMBOLS:
         assert f"int {name}(" in code and name in _lib.SIGNATURES and hasattr(lib, name), name

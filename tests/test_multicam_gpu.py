@@ -1,4 +1,4 @@
-"""The multi-camera train step (`cams_per_step`; csrc/multicam.hip) on the GPU.
+"""The multi-camera train step (`cams_per_step`; csrc/rays.hip) on the GPU.
 
 A batch is K segments of consecutive rays, segment k of camera cam_k.  The fused forward is held to BIT identity with the three
 single-camera kernels it stands for (sample_perm, raygen_fwd, gather_gt: the same arithmetic in the same order); the backward sums
@@ -117,7 +117,7 @@ def test_torch_seed_governs_the_device_draw(scenes, gpu_device):
 def _record_parity(shape, line):
     """profiles/multicam_parity.txt: one line per shape, rewritten by every run of the backward test."""
     path = os.path.join(ROOT, "profiles", "multicam_parity.txt")
-    head = ("# ray_batch_bwd (csrc/multicam.hip) against the fp64 restatement tests/multicam_ref.py, beside raygen_bwd summed over the same\n"
+    head = ("# ray_batch_bwd (csrc/rays.hip) against the fp64 restatement tests/multicam_ref.py, beside raygen_bwd summed over the same\n"
             "# segments (e_old); max abs error per tensor; written by tests/test_multicam_gpu.py::test_backward_against_fp64\n")
     try:
         lines = {}

@@ -1,0 +1,122 @@
+"""The six kernels of the ray preamble (csrc/rays.hip: sample_perm, raygen_fwd, raygen_bwd, gather_gt, ray_batch_fwd, ray_batch_bwd)
+against tests/golden/ray_preamble.npz, bit for bit.
+
+The fixture was recorded on an MI355X from the library of the commit before the per-ray arithmetic moved into csrc/mcnerf_rays.h
+(tests/golden/make_ray_preamble.py, which also holds the cases: they exist once); the single- and the multi-camera kernels had their
+own copy of it then.  Equality with that recording is what says that sharing the functions changed no bit.  No tolerance anywhere
+except where the order of float atomics is not fixed (below).  The integer path is pinned by arithmetic as well: a uint32 restatement
+of the Feistel walk in numpy."""
+import importlib.util
+import os
+
+import numpy as np
+import pytest
+import torch
+
+from conftest import GOLDEN, load_golden
+
+pytestmark = pytest.mark.gpu
+
+_spec = importlib.util.spec_from_file_location("make_ray_preamble", os.path.join(GOLDEN, "make_ray_preamble.py"))
+cases = importlib.util.module_from_spec(_spec)
+_spec.loader.exec_module(cases)
+
+
+@pytest.fixture(scope="module")
+def recorded():
+    return load_golden("ray_preamble")
+
+
+@pytest.fixture(scope="module")
+def got(recorded, gpu_device):
+    """Every case, run once."""
+    return cases.run(recorded, gpu_device)
+
+
+def _same(got, recorded, prefix, n_expected):
+    keys = sorted(k for k in recorded if k.startswith(prefix))
+    assert len(keys) == n_expected, keys
+    for k in keys:
+        assert got[k].shape == recorded[k].shape and got[k].dtype.kind == recorded[k].dtype.kind, k
+        assert np.array_equal(got[k], recorded[k]), (k, int((got[k] != recorded[k]).sum()), "entries differ")
+
+
+def feistel_perm(i, n, seed):
+    """mcn_feistel_perm(i, n, &seed, 0) in numpy: uint32 arithmetic held in uint64 (a product of two 32-bit words fits)."""
+    u, M = np.uint64, np.uint64(0xFFFFFFFF)
+    bits = 1
+    while bits < 32 and (1 << bits) < n:
+        bits += 1
+    half = u((bits + 1) // 2)
+    mask = u((1 << int(half)) - 1)
+
+    def hash32(sd, x):
+        x = (x * u(0x9E3779B9) + u(sd)) & M
+        x ^= x >> u(16); x = (x * u(0x85EBCA6B)) & M; x ^= x >> u(13); x = (x * u(0xC2B2AE35)) & M; x ^= x >> u(16)
+        return x
+    x = np.asarray(i, dtype=u)
+    walking = np.ones(x.shape, dtype=bool)
+    while walking.any():
+        L, R = x >> half, x & mask
+        for r in range(6):
+            L, R = R, L ^ (hash32((seed + 0x632BE5AB * (r + 1)) & 0xFFFFFFFF, R) & mask)
+        x = np.where(walking, (L << half) | R, x)
+        walking &= x >= u(n)
+    return x.astype(np.int64)
+
+
+def test_sample_perm(got, recorded):
+    _same(got, recorded, "sample_perm.", len(cases.PERM_CASES) * len(cases.PERM_SEEDS))
+    for n, batch in cases.PERM_CASES:
+        for seed in cases.PERM_SEEDS:
+            assert np.array_equal(got[f"sample_perm.{n}.{batch}.{seed}"], feistel_perm(np.arange(batch), n, seed)), (n, batch, seed)
+
+
+def test_raygen_fwd(got, recorded):
+    _same(got, recorded, "raygen_fwd.", 2 * (1 + len(cases.FWD_COUNTS)))
+    assert recorded["raygen_fwd.7x5.d"].shape == (35, 3) and recorded["raygen_fwd.40x30.257.o"].shape == (257, 3)
+
+
+def test_gather_gt(got, recorded):
+    _same(got, recorded, "gather_gt.", 2)
+    assert not np.array_equal(recorded["gather_gt.3"], recorded["gather_gt.4"])
+
+
+def test_raygen_bwd_in_one_workgroup(got, recorded):
+    """n <= 256: one workgroup, one fixed order of its atomics.  (At 257 two workgroups add to every word in an order that is not
+    fixed: tests/test_a_ops_gpu.py::test_raygen covers that size with its tolerance.)"""
+    _same(got, recorded, "raygen_bwd.", 2 * len(cases.BWD_COUNTS))
+    assert all(np.abs(recorded[f"raygen_bwd.{n}.d_pose"]).max() > 0 for n in cases.BWD_COUNTS)
+
+
+def test_ray_batch_fwd(got, recorded):
+    """Segments of 86 / 86 / 0 / 85 rays; injected pixels and the device draw; with images (pix, d, o, gt) and without (pix, d, o)."""
+    _same(got, recorded, "ray_batch_fwd.", 2 * (4 + 3))
+    for draw in ("injected", "drawn"):
+        for key in ("pix", "d", "o"):       # the images change nothing but gt
+            assert np.array_equal(got[f"ray_batch_fwd.{draw}.images.{key}"], got[f"ray_batch_fwd.{draw}.no_images.{key}"])
+    drawn = got["ray_batch_fwd.drawn.images.pix"]
+    for k, (lo, hi) in enumerate(zip(cases.SEG_START, cases.SEG_START[1:])):
+        key = (cases.BATCH_SEED + k * 0x9E3779B9) & 0xFFFFFFFF
+        assert np.array_equal(drawn[lo:hi], feistel_perm(np.arange(hi - lo), cases.BH * cases.BW, key)), k
+
+
+def test_ray_batch_bwd(got, recorded):
+    """Every segment <= 256 rays: one workgroup per segment.  With distinct cameras every word has one workgroup's atomics in their
+    fixed order: bit equality.  Where camera 5 owns two segments, two workgroups add to its words: a word of d_kinv receives ONE
+    value from each, and two contributions onto a zeroed word commute exactly: bit equality.  A word of that camera's d_pose
+    receives two or three values from each workgroup (its own sum, and the origin terms of mcn_raygen_bwd_flush), four to six values
+    in an order that is not fixed, so for those 12 words the gate is the one tests/test_multicam_gpu.py uses for unordered
+    atomics, 16 * 2^-24 of the tensor's largest entry; every other camera's rows stay bit-equal."""
+    _same(got, recorded, "ray_batch_bwd.distinct.", 2)
+    _same(got, recorded, "ray_batch_bwd.shared.d_kinv", 1)
+    new, old = got["ray_batch_bwd.shared.d_pose"], recorded["ray_batch_bwd.shared.d_pose"]
+    shared = cases.SEG_CAMS["shared"][0]
+    others = [c for c in range(cases.C) if c != shared]
+    assert np.array_equal(new[others], old[others])
+    err, big = float(np.abs(new[shared] - old[shared]).max()), float(np.abs(old).max())
+    print(f"[ray_batch_bwd, camera in two segments] d_pose rows of that camera: max |new - recorded| {err:.3e}, max|recorded| {big:.3e}, "
+          f"bit-equal: {np.array_equal(new[shared], old[shared])}")
+    assert err <= 16.0 * 2.0 ** -24 * big
+    unused = [c for c in range(cases.C) if c not in cases.SEG_CAMS["shared"]]
+    assert np.abs(new[unused]).max() == 0.0 and np.abs(recorded["ray_batch_bwd.shared.d_kinv"][shared]).max() > 0
