@@ -353,6 +353,31 @@ int mcnerf_train_loss(const float* pd, const float* pt_gt, int np, int H, int W,
                       float* out, float* d_pd, float* d_c, float* d_f, void* stream);
 int mcnerf_scale3(float* a, int na, float* b, int nb, float* c, int nc, const float* g, void* stream);
 
+/* mcnerf_train_loss with a per-camera colour calibration (this build's own sys_param key "color_calib" = "affine"; it extends
+ * MC_NeRF_Loss.forward for the keys {"intr", "rgb"}, model/loss.py:13-31, the reference has no colour correction): camera c is modelled
+ * to observe g_c * rgb + b_c of the rendered colour, g_c = 1 + color_w[c, 0:3], b_c = color_w[c, 3:6], coarse and fine render alike.
+ * The n rays are K segments of consecutive rays, segment k = rays [seg_start[k], seg_start[k+1]) of camera seg_cam[k] (HOST arrays, as
+ * mcnerf_ray_batch_fwd's: they travel by value in the kernel arguments -- no host->device copy, no host synchronisation):
+ *   L_rgb = mean_i,ch (g rgb_c[i] + b - gt[i])^2 + the same for rgb_f [may be null]      (g, b of the camera of ray i's segment)
+ *   L_reg = reg_lambda * (1/K) sum_k mean_j color_w[c_k, j]^2                            (an empty segment adds nothing)
+ *   total = the L_intr term exactly as mcnerf_train_loss (incl. the value-1 normalisation) + L_rgb + L_reg
+ * Value and every gradient in ONE launch, deterministic (no float atomic decides a value): per ray and channel
+ * e = (g rgb + b) - gt, evaluated in fp64 from the fp32 operands and rounded once (a small residual carries no cancellation error
+ * into its camera's gradient row), and d rgb = (gr e) g with gr = 2 / (3 n), in that order, so that at color_w = 0 the residual
+ * -- for colours in [0, 1] the correctly rounded rgb - gt -- and d_c / d_f are the bits of mcnerf_train_loss.  rgb_*, gt, d_c, d_f [n,3]; color_w, d_color [C,6] (rows of cameras outside the table
+ * are exactly zero; a camera listed twice receives the sum of its segments);
+ * out[MCNERF_TRAIN_LOSS_CALIB_OUT]: out[0..3] = {total, L_intr, L_rgb, L_reg}, out[4] an arrival counter that must be ZERO on entry
+ * (it is zero again on exit); partials[MCNERF_TRAIN_LOSS_CALIB_WS] floats of scratch (seven partial sums per block, never read
+ * before they are written: no initialisation needed).
+ * Refused ahead of any device work: K < 1 or K > 64, a camera id outside [0, C), a decreasing seg_start, seg_start[0] != 0,
+ * seg_start[K] != n, n < 1, reg_lambda < 0, a null required pointer. */
+#define MCNERF_TRAIN_LOSS_CALIB_OUT 8
+#define MCNERF_TRAIN_LOSS_CALIB_WS 896
+int mcnerf_train_loss_calib(const float* pd, const float* pt_gt, int np, int H, int W, int normalise,
+                            const float* rgb_c, const float* rgb_f, const float* gt, int n,
+                            const float* color_w, int C, const int32_t* seg_cam, const int32_t* seg_start, int K, float reg_lambda,
+                            float* out, float* d_pd, float* d_c, float* d_f, float* d_color, float* partials, void* stream);
+
 /* Fused multi-tensor Rectified-Adam step (one launch for all tensors of a param group).
  * Replaces the per-tensor loop of RAdam.step (model/net_utils.py:38-99).  The arrays of n_tensors device
  * pointers / sizes live on the HOST; step_size and `rectified` (N_sma >= 5) are the host-side scalars of the

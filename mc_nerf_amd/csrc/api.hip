@@ -4,6 +4,7 @@
 #include "mcnerf_kernels.h"
 #include "mcnerf_voxel.h"
 #include "mcnerf_multicam.h"
+#include "mcnerf_colorcal.h"
 #include "mcnerf_16.h"
 #include "mcnerf_x3.h"
 #include <stdio.h>
@@ -172,6 +173,19 @@ int mcnerf_train_loss(const float* pd, const float* pt_gt, int np, int H, int W,
                       float* out, float* d_pd, float* d_c, float* d_f, void* stream) {
     REQ(np >= 0 && (np == 0 || (pd && pt_gt && d_pd)) && rgb_c && gt && nrgb > 0 && out && d_c && (!rgb_f || d_f) && H > 0 && W > 0, "mcnerf_train_loss");
     return check("mcnerf_train_loss", mcn_launch_train_loss(pd, pt_gt, np, H, W, normalise, rgb_c, rgb_f, gt, nrgb, out, d_pd, d_c, d_f, (hipStream_t)stream));
+}
+int mcnerf_train_loss_calib(const float* pd, const float* pt_gt, int np, int H, int W, int normalise,
+                            const float* rgb_c, const float* rgb_f, const float* gt, int n,
+                            const float* color_w, int C, const int32_t* seg_cam, const int32_t* seg_start, int K, float reg_lambda,
+                            float* out, float* d_pd, float* d_c, float* d_f, float* d_color, float* partials, void* stream) {
+    McnSegTable t = {};
+    if (int rc = fill_segments("mcnerf_train_loss_calib", t, seg_cam, seg_start, K, C, n, n)) return rc;
+    REQ(n >= 1 && np >= 0 && (np == 0 || (pd && pt_gt && d_pd)) && H > 0 && W > 0, "mcnerf_train_loss_calib");
+    REQ(rgb_c && gt && color_w && out && d_c && (!rgb_f || d_f) && d_color && partials, "mcnerf_train_loss_calib");
+    REQ(reg_lambda >= 0.f && reg_lambda <= 3.0e38f, "mcnerf_train_loss_calib");
+    McnTrainLossCalibArgs a = {pd, pt_gt, np, 1.0f / ((float)W * (float)W), 1.0f / ((float)H * (float)H), normalise, rgb_c, rgb_f, gt, n,
+                               color_w, C, reg_lambda, out, d_pd, d_c, d_f, d_color, partials};
+    return check("mcnerf_train_loss_calib", mcn_launch_train_loss_calib(a, t, (hipStream_t)stream));
 }
 int mcnerf_scale3(float* a, int na, float* b, int nb, float* c, int nc, const float* g, void* stream) {
     REQ(g && na >= 0 && nb >= 0 && nc >= 0 && (na == 0 || a) && (nb == 0 || b), "mcnerf_scale3");

@@ -5,6 +5,21 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
+COLOR_CALIB_MODES = ("none", "affine")
+COLOR_CALIB_REG = 1e-3      # default of "color_calib_reg": a starting value, NOT tuned
+
+
+def color_calib_settings(sys_param):
+    """(mode, reg) of this build's own sys_param keys "color_calib" ("none", the default, or "affine") and "color_calib_reg" (a float
+    >= 0; default COLOR_CALIB_REG); a ValueError names the key."""
+    mode = sys_param.get("color_calib", "none")
+    if not isinstance(mode, str) or mode not in COLOR_CALIB_MODES:
+        raise ValueError(f"color_calib must be one of {COLOR_CALIB_MODES}, got {mode!r}")
+    reg = sys_param.get("color_calib_reg", COLOR_CALIB_REG)
+    if isinstance(reg, bool) or not isinstance(reg, (int, float)) or not 0.0 <= reg < float("inf"):
+        raise ValueError(f"color_calib_reg must be a finite float >= 0, got {reg!r}")
+    return mode, float(reg)
+
 
 class MC_NeRF_Loss(nn.Module):
     def __init__(self, sys_param, tblogger=None):
@@ -14,6 +29,7 @@ class MC_NeRF_Loss(nn.Module):
         self.global_step = 0
         self.img_h = sys_param["data_img_h"]
         self.img_w = sys_param["data_img_w"]
+        self.color_reg = color_calib_settings(sys_param)[1]
 
     def forward(self, loss_dict, epoch_type):
         self.global_step += 1
@@ -24,6 +40,19 @@ class MC_NeRF_Loss(nn.Module):
             pd, pt_gt = loss_dict["intr"]
             rgb_c, rgb_f, gt = loss_dict["rgb"]
             return TrainLossFn.apply(pd, pt_gt.to(pd.device), rgb_c, rgb_f, gt, self.img_h, self.img_w, epoch_type != "CAM_PARAM_EPOCH")
+        if set(loss_dict) == {"intr", "rgb", "color"}:
+            # the NeRF stages with the per-camera colour calibration: one launch as well (csrc/color_calib.hip) on
+            # device tensors, the eager formulation of the same loss on host tensors
+            weights_color, cams, seg_start = loss_dict["color"]
+            pd, pt_gt = loss_dict["intr"]
+            if loss_dict["rgb"][0].is_cuda:
+                from .render import TrainLossCalibFn
+                rgb_c, rgb_f, gt = loss_dict["rgb"]
+                return TrainLossCalibFn.apply(pd, pt_gt.to(pd.device), rgb_c, rgb_f, gt, weights_color, cams, seg_start,
+                                              self.img_h, self.img_w, epoch_type != "CAM_PARAM_EPOCH", self.color_reg)
+            l_intr = self.get_reproject_loss(loss_dict["intr"])
+            l_intr = l_intr if epoch_type == "CAM_PARAM_EPOCH" else l_intr / (l_intr.detach() + 1e-8)
+            return l_intr + self.get_rgb_loss_calibrated(loss_dict["rgb"], weights_color, cams, seg_start)
         total = 0.0
         if "intr" in loss_dict:
             l_intr = self.get_reproject_loss(loss_dict["intr"])
@@ -41,6 +70,31 @@ class MC_NeRF_Loss(nn.Module):
         if rgb_f is not None:
             loss = loss + F.mse_loss(rgb_f, gt)
         return loss
+
+    def get_rgb_loss_calibrated(self, rgbs_list, weights_color, cams, seg_start, reg=None):
+        """get_rgb_loss with the per-camera colour calibration weights_color [C,6], for loops that drive NeRF_Model
+        directly: rays [seg_start[k], seg_start[k+1]) are camera cams[k]'s (host lists), which is modelled to observe
+        (1 + w[0:3]) * rgb + w[3:6] of either render; + reg * (1/K) sum_k mean_j w[c_k, j]^2 over the non-empty segments (`reg`
+        None: the model's "color_calib_reg").  Device tensors: one launch (TrainLossCalibFn); host tensors: eager torch."""
+        rgb_c, rgb_f, gt = rgbs_list
+        reg = self.color_reg if reg is None else float(reg)
+        if reg < 0.0:
+            raise ValueError(f"color_calib_reg must be >= 0, got {reg!r}")
+        cams, seg_start = [int(c) for c in cams], [int(x) for x in seg_start]
+        if rgb_c.is_cuda:
+            from .render import TrainLossCalibFn
+            return TrainLossCalibFn.apply(None, None, rgb_c, rgb_f, gt, weights_color, cams, seg_start, self.img_h, self.img_w, False, reg)
+        K = len(cams)
+        if len(seg_start) != K + 1 or K < 1 or seg_start[0] != 0 or seg_start[-1] != rgb_c.shape[0]:
+            raise ValueError(f"seg_start must hold len(cams) + 1 entries from 0 to {rgb_c.shape[0]}, got {seg_start}")
+        lens = torch.tensor([b - a for a, b in zip(seg_start, seg_start[1:])])
+        cam_idx = torch.tensor(cams, dtype=torch.int64)
+        w = weights_color[torch.repeat_interleave(cam_idx, lens)]                # [n,6]: the calibration of every ray's camera
+        g, b = 1.0 + w[:, :3], w[:, 3:]
+        loss = F.mse_loss(g * rgb_c + b, gt)
+        if rgb_f is not None:
+            loss = loss + F.mse_loss(g * rgb_f + b, gt)
+        return loss + reg * (weights_color[cam_idx[lens > 0]] ** 2).mean(1).sum() / K
 
     def get_reproject_loss(self, rpro_list):
         pd, gt = rpro_list

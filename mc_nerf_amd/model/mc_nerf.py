@@ -22,6 +22,7 @@ import torch.distributed as dist
 
 from .. import ops
 from ..data import DeviceImageSet
+from .loss import color_calib_settings
 from .net_block import CorseFine_NeRF, SinCosEmbedding
 from .render import CameraFn, RayBatchFn, RaygenFn, Rays, RenderCall, RenderSettings, RenderTrainFn, SamplePass, _pool, render_test, run_pass
 
@@ -487,6 +488,10 @@ class MC_Model(nn.Module):
         self.last_step_segments = None    # (camera ids, seg_start) of the last multi-camera step
         self.last_step_pix = None         # its pixel ids [batch]
         self._seg_index = None            # segment of every ray (device int64 [batch]; host float stacks only), built once
+        # "color_calib" / "color_calib_reg" are this build's own keys as well: "none" (the default: today's path, no
+        # parameter) or "affine" -- one more parameter weights_color [C,6], camera c is modelled to observe
+        # (1 + weights_color[c, 0:3]) * rgb + weights_color[c, 3:6] of the rendered colour, fused into the NeRF stages' loss
+        self.color_calib, self.color_calib_reg = color_calib_settings(sys_param)
         self.intr = sys_param["intr_mat"]
         self.intr_inv = sys_param["intr_mat_inv"]
         # the constant intrinsics live on the device from the start (a per-step .to(device) of a host tensor is a
@@ -515,6 +520,15 @@ class MC_Model(nn.Module):
         for name, shape in (("weights_pose", (C, 6)), ("weights_pose_intr", (C, 6)), ("weights_ux", (C,)),
                             ("weights_uy", (C,)), ("weights_fx", (C,)), ("weights_fy", (C,))):
             self.register_parameter(name, nn.Parameter(torch.ones(shape, device=dev), requires_grad=True))
+        if self.color_calib == "affine":     # an offset from identity (zeros): weight decay pulls towards "no correction"
+            self.register_parameter("weights_color", nn.Parameter(torch.zeros(C, 6, device=dev), requires_grad=True))
+
+    def color_correction(self):
+        """(gain [C,3], bias [C,3]) of the training cameras, detached: camera c observes gain[c] * rgb + bias[c]."""
+        if self.color_calib != "affine":
+            raise ValueError("color_correction() needs color_calib = 'affine'")
+        w = self.weights_color.detach()
+        return 1.0 + w[:, :3], w[:, 3:].clone()
 
     # ------------------------------------------------------------------ forward (:58-122)
     def forward(self, *args):
@@ -551,6 +565,8 @@ class MC_Model(nn.Module):
             rgbs_c, rgbs_f = self.nerf(rays_d, rays_o, epoch, cur_ratio if joint else 1)
             gt = images.gather(cam, rand_idx) if images is not None else gt_rgbs.reshape(-1, 3)[rand_idx]
             loss_dict["rgb"] = [rgbs_c, rgbs_f, gt]
+            if self.color_calib == "affine":
+                loss_dict["color"] = [self.weights_color, [cam], [0, int(rgbs_c.shape[0])]]
             self.opt_idx = 1 if joint else 2
         # validation rays of the same index, every step, as the reference (:97-99)
         with torch.no_grad():
@@ -587,6 +603,8 @@ class MC_Model(nn.Module):
                 self._seg_index = ops.ray_segment_index(self.batch, K, pix.device)
             gt = gt_rgbs.reshape(K, -1, 3)[self._seg_index, pix]
         loss_dict["rgb"] = [rgbs_c, rgbs_f, gt]
+        if self.color_calib == "affine":
+            loss_dict["color"] = [self.weights_color, cams, seg_start]
         self.opt_idx = 1 if joint else 2
         self.last_step_segments, self.last_step_pix = (cams, seg_start), pix
 
@@ -605,10 +623,17 @@ class MC_Model(nn.Module):
         return torch.randperm(npix, device=self.device)[: self.batch]
 
     @torch.no_grad()
-    def render_image_device(self, img_id):
-        """The demo render of one test camera (:106-122) with the result left on the device."""
+    def render_image_device(self, img_id, as_camera=None):
+        """The demo render of one test camera (:106-122) with the result left on the device.  `as_camera` = c (color_calib =
+        "affine"): the colours as training camera c is modelled to observe them, gain[c] * rgb + bias[c]; None (the default): the
+        canonical, uncorrected scene."""
         rays_d, rays_o = self.get_rays(self.test_pose, img_id, self.intr_test_inv)
-        return self.nerf.render_chunked(rays_d, rays_o, self.nerf.nerf_coarse, self.nerf.nerf_fine, chunk=self.batch)
+        rgb, depth, opacity = self.nerf.render_chunked(rays_d, rays_o, self.nerf.nerf_coarse, self.nerf.nerf_fine, chunk=self.batch)
+        if as_camera is not None:
+            gain, bias = self.color_correction()
+            c = _int_key({"as_camera": as_camera}, "as_camera", None, 0, self.train_numb - 1)
+            rgb = gain[c] * rgb + bias[c]
+        return rgb, depth, opacity
 
     @torch.no_grad()
     def _forward_demo(self, img_id):

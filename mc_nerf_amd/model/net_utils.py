@@ -22,6 +22,14 @@ class RAdam(Optimizer):
         defaults = dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay,
                         buffer=[[None, None, None] for _ in range(10)])
         super().__init__(params, defaults)
+        # the cache is keyed by the step count alone, so it belongs to ONE group's betas: a group with betas of its own must not find
+        # the step size of another group's beta1 in it (the one list of `defaults` would be shared by all groups)
+        for group in self.param_groups:
+            group["buffer"] = [[None, None, None] for _ in range(10)]
+
+    def add_param_group(self, param_group):
+        super().add_param_group(param_group)
+        self.param_groups[-1]["buffer"] = [[None, None, None] for _ in range(10)]
 
     @staticmethod
     def _rectification(step, beta1, beta2, degenerate):

@@ -451,6 +451,30 @@ class TrainLossFn(torch.autograd.Function):
         return d_pd, None, d_c, d_f, None, None, None, None
 
 
+class TrainLossCalibFn(torch.autograd.Function):
+    """TrainLossFn with the per-camera colour calibration (csrc/color_calib.hip): value and every gradient, d weights_color
+    included, in ONE launch; backward scales the saved gradients by the upstream scalar on the device (no host sync).  `pd` / `pt_gt`
+    may be None (no reprojection term: get_rgb_loss_calibrated)."""
+
+    @staticmethod
+    def forward(ctx, pd, pt_gt, rgb_c, rgb_f, gt, color_w, seg_cam, seg_start, H, W, normalise, reg):
+        cf = lambda t: None if t is None else t.contiguous().float()
+        pd, pt_gt, rgb_c, rgb_f, gt, color_w = cf(pd), cf(pt_gt), cf(rgb_c), cf(rgb_f), cf(gt), cf(color_w)
+        out, d_pd, d_c, d_f, d_color = ops.train_loss_calib(pd, pt_gt, H, W, normalise, rgb_c, rgb_f, gt, color_w, seg_cam, seg_start, reg)
+        ctx.grads = (d_pd, d_c, d_f, d_color)
+        ctx.parts = out
+        return out[0]
+
+    @staticmethod
+    def backward(ctx, g):
+        d_pd, d_c, d_f, d_color = ctx.grads
+        g = g.contiguous().float().reshape(1)
+        ops.scale3_(d_pd, d_c, d_f, g)
+        ops.scale3_(None, d_color, None, g)
+        ctx.grads = None
+        return d_pd, None, d_c, d_f, None, d_color, None, None, None, None, None, None
+
+
 class ReprojLossFn(torch.autograd.Function):
     """MC_NeRF_Loss.get_reproject_loss (model/loss.py:45-58) as one kernel each way."""
 

@@ -707,6 +707,43 @@ def train_loss(pd: Optional[Tensor], pt_gt: Optional[Tensor], H: int, W: int, no
 TRAIN_LOSS_OUT = 132        # MCNERF_TRAIN_LOSS_OUT
 
 
+TRAIN_LOSS_CALIB_OUT = 8     # MCNERF_TRAIN_LOSS_CALIB_OUT
+TRAIN_LOSS_CALIB_WS = 896    # MCNERF_TRAIN_LOSS_CALIB_WS
+
+
+def train_loss_calib(pd: Optional[Tensor], pt_gt: Optional[Tensor], H: int, W: int, normalise: bool, rgb_c: Tensor, rgb_f: Optional[Tensor],
+                     gt: Tensor, color_w: Tensor, seg_cam, seg_start, reg_lambda: float, out: Optional[Tensor] = None):
+    """`train_loss` with the per-camera colour calibration `color_w` [C,6] (gain - 1, bias) of the cameras `seg_cam` whose rays are the
+    segments `seg_start` (host lists; they travel as kernel arguments), in one launch: -> out [4] = (total, L_intr, L_rgb, L_reg),
+    d_pd | None, d_c, d_f | None, d_color [C,6] (rows of cameras outside the table exactly zero).  `out`: a buffer of
+    TRAIN_LOSS_CALIB_OUT + TRAIN_LOSS_CALIB_WS floats to re-use (its word [4], the kernel's arrival counter, zero on entry: it is
+    zero again on exit); allocated and zeroed when not given."""
+    cams, start, K, n = _seg_arrays(seg_cam, seg_start)
+    if not rgb_c.is_cuda:
+        raise _lib.McnerfError("train_loss_calib needs CUDA/HIP tensors (no CPU fallback; MC_NeRF_Loss keeps the eager formulation for host tensors)")
+    for name, t in (("pd", pd), ("pt_gt", pt_gt), ("rgb_f", rgb_f), ("gt", gt), ("color_w", color_w), ("out", out)):
+        if t is not None and (t.device != rgb_c.device or t.dtype != torch.float32):       # (before anything is allocated or launched)
+            raise _lib.McnerfError(f"train_loss_calib: {name} must be a float32 tensor on {rgb_c.device}, got {t.dtype} on {t.device}")
+    if rgb_c.numel() != 3 * n or gt.numel() != 3 * n or (rgb_f is not None and rgb_f.numel() != 3 * n):
+        raise _lib.McnerfError(f"rgb_c / rgb_f / gt must hold seg_start[-1] = {n} rays of 3 channels")
+    if color_w.dim() != 2 or color_w.shape[1] != 6:
+        raise _lib.McnerfError(f"color_w must be [C,6], got {tuple(color_w.shape)}")
+    dev = rgb_c.device
+    if out is None:
+        out = torch.zeros(TRAIN_LOSS_CALIB_OUT + TRAIN_LOSS_CALIB_WS, dtype=torch.float32, device=dev)
+    elif out.numel() != TRAIN_LOSS_CALIB_OUT + TRAIN_LOSS_CALIB_WS:
+        raise _lib.McnerfError(f"out must hold {TRAIN_LOSS_CALIB_OUT + TRAIN_LOSS_CALIB_WS} floats")
+    np_ = pd.numel() // 2 if pd is not None else 0
+    d_pd = torch.empty_like(pd) if pd is not None else None
+    d_c = torch.empty_like(rgb_c)
+    d_f = torch.empty_like(rgb_f) if rgb_f is not None else None
+    d_color = torch.empty_like(color_w)
+    _lib.call("mcnerf_train_loss_calib", _p(pd), _p(pt_gt), np_, int(H), int(W), int(bool(normalise)), _p(rgb_c), _p(rgb_f), _p(gt), n,
+              _p(color_w), int(color_w.shape[0]), cams, start, K, float(reg_lambda), _p(out), _p(d_pd), _p(d_c), _p(d_f), _p(d_color),
+              _p(out[TRAIN_LOSS_CALIB_OUT:]), _stream())
+    return out[:4], d_pd, d_c, d_f, d_color
+
+
 def scale3_(a: Optional[Tensor], b: Tensor, c: Optional[Tensor], g: Tensor):
     """a, b, c *= g (device scalar) in place, one launch."""
     _lib.call("mcnerf_scale3", _p(a), a.numel() if a is not None else 0, _p(b), b.numel(), _p(c), c.numel() if c is not None else 0, _p(g), _stream())

@@ -282,3 +282,20 @@ def blob_scene_images(pose, K, H, W, chunk=8192):
         d, o = ops.raygen_fwd(pose[i].contiguous(), Kinv[i].contiguous(), allpix, W)
         out.append(torch.cat([blob_scene_render(d[j:j + chunk], o[j:j + chunk]) for j in range(0, H * W, chunk)]))
     return torch.stack(out)
+
+
+def camera_color_response(C: int, seed: int = 0, gain_spread: float = 0.15, bias_spread: float = 0.03):
+    """Per-camera colour responses of a heterogeneous rig: (gain [C,3], bias [C,3]) with camera c observing gain[c] * rgb + bias[c]
+    (exposure / white balance, black level).  Normal draws of the given spreads, then centred per channel: the gains to mean 1 and
+    the biases to mean 0 over the cameras (the rig as a whole is colour-neutral; a common gain could not be told from the scene)."""
+    gen = torch.Generator().manual_seed(seed)
+    g = 1.0 + gain_spread * torch.randn(C, 3, generator=gen)
+    b = bias_spread * torch.randn(C, 3, generator=gen)
+    return g - g.mean(0, keepdim=True) + 1.0, b - b.mean(0, keepdim=True)
+
+
+def apply_color_response(images: torch.Tensor, gain: torch.Tensor, bias: torch.Tensor) -> torch.Tensor:
+    """gain[c] * images[c] + bias[c] for a FLOAT image stack [C, ..., 3].  Nothing is clamped: values may leave [0, 1]; for the
+    uint8 images of a DeviceImageSet the clipping (and what it does to the affine model) is the caller's business."""
+    shape = (images.shape[0],) + (1,) * (images.dim() - 2) + (3,)
+    return gain.to(images).reshape(shape) * images + bias.to(images).reshape(shape)
