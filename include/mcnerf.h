@@ -378,6 +378,42 @@ int mcnerf_train_loss_calib(const float* pd, const float* pt_gt, int np, int H, 
                             const float* color_w, int C, const int32_t* seg_cam, const int32_t* seg_start, int K, float reg_lambda,
                             float* out, float* d_pd, float* d_c, float* d_f, float* d_color, float* partials, void* stream);
 
+/* ---- Error-guided pixel sampling (this build's own sys_param key "pixel_sampler" = "error"; the default, "uniform", runs
+ * mcnerf_sample_perm / the in-kernel draw of mcnerf_ray_batch_fwd as before).  New symbols only: MCNERF_ABI_VERSION stays 7.  The
+ * reference draws uniformly (model/mc_nerf.py:329).
+ *
+ * The map is err [C, Th, Tw] fp32, Th = ceil(H / tile), Tw = ceil(W / tile): a running squared colour error per tile of tile x tile
+ * pixels of each of the C training images (edge tiles are smaller).  The n rays are K segments of consecutive rays, segment k = rays
+ * [seg_start[k], seg_start[k+1]) of camera seg_cam[k]: HOST arrays that travel by value in the kernel arguments, as
+ * mcnerf_ray_batch_fwd's (no host->device copy, no host synchronisation).
+ *
+ * Tile weights are integers, so the CDF does not depend on the order of summation:
+ *   c_t = fminf(fmaxf(E_t, 0), 4) [NaN -> 0, +inf -> 4];  q_t = max(1, (uint64)(c_t * 2^24)) * area_t [area_t = pixels of tile t]
+ * Pixel density is proportional to the clamped error; every tile keeps a non-zero weight; total <= 2^52 is exact in a double.
+ *
+ * mcnerf_errmap_sample: two launches (CDF: one block per segment writes the inclusive uint64 prefix sums of q of camera seg_cam[k]
+ * into cdf[k][0 .. Th*Tw); draw: one thread per ray).  u [n,2] fp32 uniforms, both first clamped into [0, 1 - 2^-24] (NaN -> 0);
+ * ray j of segment k (n_k rays), n_u = (int)((double)uniform_frac * n_k):
+ *   j < n_u    pix = min((int64)((double)u0 * (double)(H W)), H W - 1)                                  (uniform over the image)
+ *   otherwise  target = (uint64)((double)u0 * (double)total_k), tile t = the first with cdf[k][t] > target (clamped to Th*Tw - 1),
+ *              l = min((int)(u1 * (float)area_t), area_t - 1) in fp32, pix = (ty tile + l / tw_t) W + tx tile + l % tw_t
+ * -> pix [n] int64, every id in [0, H W) whatever the inputs.  Draws are WITH replacement.  cdf: a [>= K, Th*Tw] uint64 workspace.
+ *
+ * mcnerf_errmap_update: per ray d = rgb - gt, e = ((d0^2 + d1^2) + d2^2) * 0.333333343f, every step a separately rounded fp32
+ * operation; rays with a non-finite e or pix outside [0, H W) are skipped.  Two launches, mcnerf_voxel_update's protocol: atomicMax
+ * of the order-preserving key of e into scratch[seg_cam[k], tile(pix)]; then every ray exchanges its word with 0 and the one thread
+ * that receives a non-zero key writes E <- fadd_rn(fmul_rn(one_minus_beta, E), fmul_rn(beta, m)) (one_minus_beta formed by the
+ * caller in fp32).  Untouched tiles and cameras outside the table keep their bits; a camera listed in two segments gets the max over
+ * both; deterministic whatever the order of arrival; scratch [C,Th,Tw] uint32 must be all zero on entry and is all zero on exit.
+ *
+ * Refused ahead of any device work: K < 1, K > 64, a camera id outside [0, C), a decreasing seg_start, seg_start[0] != 0,
+ * seg_start[K] != n, tile < 1, H W > 2^26, uniform_frac (beta, one_minus_beta) outside [0, 1] or NaN, a null pointer. */
+int mcnerf_errmap_sample(const float* err, int C, int H, int W, int tile, const int32_t* seg_cam, const int32_t* seg_start, int K,
+                         int n, float uniform_frac, const float* u, uint64_t* cdf, int64_t* pix, void* stream);
+int mcnerf_errmap_update(float* err, uint32_t* scratch, int C, int H, int W, int tile, const int32_t* seg_cam, const int32_t* seg_start,
+                         int K, int n, const int64_t* pix, const float* rgb, const float* gt, float beta, float one_minus_beta,
+                         void* stream);
+
 /* Fused multi-tensor Rectified-Adam step (one launch for all tensors of a param group).
  * Replaces the per-tensor loop of RAdam.step (model/net_utils.py:38-99).  The arrays of n_tensors device
  * pointers / sizes live on the HOST; step_size and `rectified` (N_sma >= 5) are the host-side scalars of the

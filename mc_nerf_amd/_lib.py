@@ -37,6 +37,8 @@ SIGNATURES = {
     "mcnerf_upload_f32": (_I, [_P, _P, _I, _P]),
     "mcnerf_train_loss": (_I, [_P, _P, _I, _I, _I, _I, _P, _P, _P, _I, _P, _P, _P, _P, _P]),
     "mcnerf_train_loss_calib": (_I, [_P, _P, _I, _I, _I, _I, _P, _P, _P, _I, _P, _I, _P, _P, _I, c_float, _P, _P, _P, _P, _P, _P, _P]),
+    "mcnerf_errmap_sample": (_I, [_P, _I, _I, _I, _I, _P, _P, _I, _I, c_float, _P, _P, _P, _P]),
+    "mcnerf_errmap_update": (_I, [_P, _P, _I, _I, _I, _I, _P, _P, _I, _I, _P, _P, _P, c_float, c_float, _P]),
     "mcnerf_scale3": (_I, [_P, _I, _P, _I, _P, _I, _P, _P]),
     "mcnerf_sample_perm": (_I, [_P, ctypes.c_longlong, _I, _P, _P]),
     "mcnerf_mlp_apply": (_I, [_I, _I, _I, _P, _P, _P, _P, _I, _P, _P]),

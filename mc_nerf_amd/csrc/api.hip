@@ -5,6 +5,7 @@
 #include "mcnerf_voxel.h"
 #include "mcnerf_multicam.h"
 #include "mcnerf_colorcal.h"
+#include "mcnerf_errmap.h"
 #include "mcnerf_16.h"
 #include "mcnerf_x3.h"
 #include <stdio.h>
@@ -186,6 +187,28 @@ int mcnerf_train_loss_calib(const float* pd, const float* pt_gt, int np, int H, 
     McnTrainLossCalibArgs a = {pd, pt_gt, np, 1.0f / ((float)W * (float)W), 1.0f / ((float)H * (float)H), normalise, rgb_c, rgb_f, gt, n,
                                color_w, C, reg_lambda, out, d_pd, d_c, d_f, d_color, partials};
     return check("mcnerf_train_loss_calib", mcn_launch_train_loss_calib(a, t, (hipStream_t)stream));
+}
+// The error-guided pixel sampler (errmap.hip): everything is checked before any HIP call, as for mcnerf_ray_batch_fwd.
+int mcnerf_errmap_sample(const float* err, int C, int H, int W, int tile, const int32_t* seg_cam, const int32_t* seg_start, int K,
+                         int n, float uniform_frac, const float* u, uint64_t* cdf, int64_t* pix, void* stream) {
+    REQ(H > 0 && W > 0 && tile >= 1 && (long long)H * W <= (1ll << 26), "mcnerf_errmap_sample");
+    McnSegTable t = {};
+    if (int rc = fill_segments("mcnerf_errmap_sample", t, seg_cam, seg_start, K, C, n, n)) return rc;
+    REQ(uniform_frac >= 0.f && uniform_frac <= 1.f, "mcnerf_errmap_sample");
+    REQ(err && u && cdf && pix, "mcnerf_errmap_sample");
+    McnErrSampleArgs a = {err, mcn_err_geom(C, H, W, tile), uniform_frac, u, n, (unsigned long long*)cdf, (long long*)pix};
+    return check("mcnerf_errmap_sample", mcn_launch_errmap_sample(a, t, (hipStream_t)stream));
+}
+int mcnerf_errmap_update(float* err, uint32_t* scratch, int C, int H, int W, int tile, const int32_t* seg_cam, const int32_t* seg_start,
+                         int K, int n, const int64_t* pix, const float* rgb, const float* gt, float beta, float one_minus_beta,
+                         void* stream) {
+    REQ(H > 0 && W > 0 && tile >= 1 && (long long)H * W <= (1ll << 26), "mcnerf_errmap_update");
+    McnSegTable t = {};
+    if (int rc = fill_segments("mcnerf_errmap_update", t, seg_cam, seg_start, K, C, n, n)) return rc;
+    REQ(beta >= 0.f && beta <= 1.f && one_minus_beta >= 0.f && one_minus_beta <= 1.f, "mcnerf_errmap_update");
+    REQ(err && scratch && pix && rgb && gt, "mcnerf_errmap_update");
+    McnErrUpdateArgs a = {err, scratch, mcn_err_geom(C, H, W, tile), (const long long*)pix, rgb, gt, n, beta, one_minus_beta};
+    return check("mcnerf_errmap_update", mcn_launch_errmap_update(a, t, (hipStream_t)stream));
 }
 int mcnerf_scale3(float* a, int na, float* b, int nb, float* c, int nc, const float* g, void* stream) {
     REQ(g && na >= 0 && nb >= 0 && nc >= 0 && (na == 0 || a) && (nb == 0 || b), "mcnerf_scale3");

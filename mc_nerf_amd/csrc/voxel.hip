@@ -19,6 +19,7 @@
 //   V <- (1 - beta) * V + beta * m      as  __fadd_rn(__fmul_rn(1 - beta, V), __fmul_rn(beta, m)),  1 - beta formed on the host.
 // Untouched cells keep their bits, and the scratch grid is all zero again afterwards.
 #include "mcnerf_voxel.h"
+#include "mcnerf_maxkey.h"
 
 __device__ __forceinline__ int vox_axis(float p, float bmin, float s, int G) {
     const float t = __fmul_rn(__fsub_rn(p, bmin), s);
@@ -81,15 +82,7 @@ hipError_t mcn_launch_voxel_select(const McnVoxelSelectArgs& a, hipStream_t st) 
     return hipGetLastError();
 }
 
-// ------------------------------------------------------------------ update
-// order-preserving key of a float: a < b <=> key(a) < key(b); every finite float's key is > 0 (key(-FLT_MAX) = 0x00800000)
-__device__ __forceinline__ unsigned vox_key(float v) {
-    const unsigned u = __float_as_uint(v);
-    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-__device__ __forceinline__ float vox_unkey(unsigned k) {
-    return __uint_as_float((k & 0x80000000u) ? (k & 0x7FFFFFFFu) : ~k);
-}
+// ------------------------------------------------------------------ update (vox_key / vox_unkey: mcnerf_maxkey.h)
 // Item i of an update: its cell and its sigma.  false: nothing there (beyond the list, a pair outside [N) x [Sc), a non-finite sigma).
 __device__ __forceinline__ bool vox_item(const McnVoxelUpdateArgs& a, long long i, size_t& cell, float& sig) {
     if (a.pts) {

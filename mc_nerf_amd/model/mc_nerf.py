@@ -487,11 +487,21 @@ class MC_Model(nn.Module):
                                       f"in [1, min({ops.MULTICAM_MAXSEG}, batch = {self.batch})]")
         self.last_step_segments = None    # (camera ids, seg_start) of the last multi-camera step
         self.last_step_pix = None         # its pixel ids [batch]
-        self._seg_index = None            # segment of every ray (device int64 [batch]; host float stacks only), built once
+        self._seg_index = None            # segment of every ray (device int64 [batch]), built once: host float stacks, error-map colours
         # "color_calib" / "color_calib_reg" are this build's own keys as well: "none" (the default: today's path, no
         # parameter) or "affine" -- one more parameter weights_color [C,6], camera c is modelled to observe
         # (1 + weights_color[c, 0:3]) * rgb + weights_color[c, 3:6] of the rendered colour, fused into the NeRF stages' loss
         self.color_calib, self.color_calib_reg = color_calib_settings(sys_param)
+        # "pixel_sampler" is this build's own key too: "uniform" (the default: today's draw, nothing allocated) or "error"
+        # -- the NeRF stages draw their pixels in proportion to a running per-tile colour error (ops.ErrorMap).  "error_tile" /
+        # "error_beta" / "error_uniform_frac" are read and validated in "error" mode only; their defaults are starting values, not tuned
+        # (the map's CDF workspace is 512 bytes per tile whatever cams_per_step is: a small error_tile on a large image costs memory)
+        self.pixel_sampler = sys_param.get("pixel_sampler", "uniform")
+        if not isinstance(self.pixel_sampler, str) or self.pixel_sampler not in ("uniform", "error"):
+            raise ValueError(f"pixel_sampler must be 'uniform' or 'error', got {self.pixel_sampler!r}")
+        self._error_map = None            # ops.ErrorMap, allocated on first use ("error" mode only): not a parameter, not a buffer
+        if self.pixel_sampler == "error":
+            self.error_tile, self.error_beta, self.error_uniform_frac = self._error_settings(sys_param)
         self.intr = sys_param["intr_mat"]
         self.intr_inv = sys_param["intr_mat_inv"]
         # the constant intrinsics live on the device from the start (a per-step .to(device) of a host tensor is a
@@ -522,6 +532,73 @@ class MC_Model(nn.Module):
             self.register_parameter(name, nn.Parameter(torch.ones(shape, device=dev), requires_grad=True))
         if self.color_calib == "affine":     # an offset from identity (zeros): weight decay pulls towards "no correction"
             self.register_parameter("weights_color", nn.Parameter(torch.zeros(C, 6, device=dev), requires_grad=True))
+
+    # ------------------------------------------------------------------ error-guided pixel sampling
+    @staticmethod
+    def _error_settings(sys_param):
+        """Reads and validates the keys of "error" mode (a ValueError names the key) -> (error_tile, error_beta, error_uniform_frac)."""
+        def number(key, default):
+            v = sys_param.get(key, default)
+            if isinstance(v, bool) or not isinstance(v, (int, float)) or v != v:
+                raise ValueError(f"{key} must be a number, got {v!r}")
+            return float(v)
+        tile = _int_key(sys_param, "error_tile", 16, 1, 256)
+        beta = number("error_beta", 0.5)
+        if not 0.0 < beta <= 1.0:
+            raise ValueError(f"error_beta must be in (0, 1], got {beta!r}")
+        frac = number("error_uniform_frac", 0.5)
+        if not 0.0 <= frac <= 1.0:
+            raise ValueError(f"error_uniform_frac must be in [0, 1], got {frac!r}")
+        h, w = sys_param["data_img_h"], sys_param["data_img_w"]
+        if h * w > ops.ERRMAP_MAX_PIXELS:
+            raise ValueError(f"pixel_sampler 'error' needs data_img_h * data_img_w <= 2^26, got {h} x {w}")
+        return tile, beta, frac
+
+    def reserve_error_map(self) -> ops.ErrorMap:
+        """The map's buffers (allocated and filled with 1.0 on first use; each rank has its own, learnt from its own shard): call it
+        ahead of the first step so that no timed / synchronised step allocates."""
+        if self.pixel_sampler != "error":
+            raise ops._lib.McnerfError("the error map exists in pixel_sampler = 'error' mode only")
+        if self._error_map is None:
+            self._error_map = ops.ErrorMap(self.train_numb, self.img_h, self.img_w, self.error_tile, self.weights_pose.device)
+        return self._error_map
+
+    def error_map(self, cam=None) -> torch.Tensor:
+        """A detached copy of the running per-tile errors: [Th,Tw] of training camera `cam`, or [C,Th,Tw] of all of them."""
+        err = self.reserve_error_map().err
+        if cam is None:
+            return err.detach().clone()
+        return err[_int_key({"cam": cam}, "cam", None, 0, self.train_numb - 1)].detach().clone()
+
+    def reset_error_map(self):
+        """Refills the map with 1.0: every tile is unvisited again."""
+        self.reserve_error_map().err.fill_(1.0)
+
+    def draw_error_uniforms(self, n):
+        """Hook of "error" mode: the [n,2] fp32 uniforms of the step's draw, or None (the default) = torch.rand from the device
+        generator inside ops.errmap_sample; parity tests replace this method."""
+        return None
+
+    def _draw_error_pixels(self, cams, seg_start):
+        return ops.errmap_sample(self.reserve_error_map(), cams, seg_start, self.error_uniform_frac, self.draw_error_uniforms(seg_start[-1]))
+
+    @torch.no_grad()
+    def _update_error_map(self, cams, seg_start, pix, rgb, gt):
+        """The map learns the step's render: with color_calib = "affine" the colours are first corrected with the detached gain and
+        bias of every ray's camera, so that the map ranks what the loss sees.  The six coefficients per ray are rows of weights_color
+        picked by host camera ids (views) and spread over the segments by the device index of `ops.ray_segment_index`: the same few
+        launches at any K, no host -> device copy and no host synchronisation."""
+        rgb = rgb.detach()
+        if self.color_calib == "affine":
+            w = self.weights_color.detach()
+            if len(cams) == 1:
+                w = w[cams[0]]
+            else:
+                if self._seg_index is None:
+                    self._seg_index = ops.ray_segment_index(self.batch, len(cams), rgb.device)
+                w = torch.stack([w[c] for c in cams])[self._seg_index]
+            rgb = (1.0 + w[..., :3]) * rgb + w[..., 3:]
+        ops.errmap_update(self.reserve_error_map(), cams, seg_start, pix, rgb.contiguous(), gt.detach().float().contiguous(), self.error_beta)
 
     def color_correction(self):
         """(gain [C,3], bias [C,3]) of the training cameras, detached: camera c observes gain[c] * rgb + bias[c]."""
@@ -560,13 +637,17 @@ class MC_Model(nn.Module):
             kinv = self.intr_inv_adj[cam] if self.intr_inv_adj is not None else \
                 self.inverse_intrinsic(self.intr_adj[cam:cam + 1])[0]
             # pixel subset first (same device randperm as :329), rays only for those pixels
-            rand_idx = self.sample_pixels(self.img_h * self.img_w)
+            error = self.pixel_sampler == "error"        # (with replacement: always `batch` rays)
+            rand_idx = self._draw_error_pixels([cam], [0, self.batch]) if error else self.sample_pixels(self.img_h * self.img_w)
             rays_d, rays_o = RaygenFn.apply(self.pose_adj[cam], kinv, rand_idx, self.img_w)
             rgbs_c, rgbs_f = self.nerf(rays_d, rays_o, epoch, cur_ratio if joint else 1)
             gt = images.gather(cam, rand_idx) if images is not None else gt_rgbs.reshape(-1, 3)[rand_idx]
             loss_dict["rgb"] = [rgbs_c, rgbs_f, gt]
             if self.color_calib == "affine":
                 loss_dict["color"] = [self.weights_color, [cam], [0, int(rgbs_c.shape[0])]]
+            if error:
+                self.last_step_segments, self.last_step_pix = ([cam], [0, self.batch]), rand_idx
+                self._update_error_map([cam], [0, self.batch], rand_idx, rgbs_f, gt)
             self.opt_idx = 1 if joint else 2
         # validation rays of the same index, every step, as the reference (:97-99)
         with torch.no_grad():
@@ -595,6 +676,8 @@ class MC_Model(nn.Module):
         kinv_all = self.intr_inv_adj if self.intr_inv_adj is not None else self.inverse_intrinsic(self.intr_adj)
         seg_start = ops.ray_segments(self.batch, K)
         pix_in = self.sample_pixels_multi(self.img_h * self.img_w, seg_start)
+        if pix_in is None and self.pixel_sampler == "error":      # (an injected draw still wins)
+            pix_in = self._draw_error_pixels(cams, seg_start)
         pix, rays_d, rays_o, gt = RayBatchFn.apply(self.pose_adj, kinv_all, cams, seg_start, self.img_h, self.img_w,
                                                    images.images if images is not None else None, pix_in)
         rgbs_c, rgbs_f = self.nerf(rays_d, rays_o, epoch, cur_ratio if joint else 1)
@@ -607,6 +690,8 @@ class MC_Model(nn.Module):
             loss_dict["color"] = [self.weights_color, cams, seg_start]
         self.opt_idx = 1 if joint else 2
         self.last_step_segments, self.last_step_pix = (cams, seg_start), pix
+        if self.pixel_sampler == "error":
+            self._update_error_map(cams, seg_start, pix, rgbs_f, gt)
 
     def sample_pixels_multi(self, npix, seg_start):
         """Hook of the multi-camera step: pixel ids [batch] to inject (segment k's at [seg_start[k], seg_start[k+1])), or None (the

@@ -624,6 +624,59 @@ def voxel_update_points(grid: VoxelGrid, xyz: Tensor, sigma: Tensor, beta: float
               M, _stream())
 
 
+# --------------------------------------------------------------------------- error-guided pixel sampling (include/mcnerf.h: mcnerf_errmap_*)
+ERRMAP_MAX_PIXELS = 1 << 26     # H * W of one image at most: the integer tile weights then sum to <= 2^52, exact in a double
+
+
+class ErrorMap:
+    """The three device buffers of `pixel_sampler = "error"` and the map's geometry: err [C,Th,Tw] fp32 (running squared colour error
+    per tile of tile x tile pixels, Th = ceil(H / tile), Tw = ceil(W / tile), edge tiles smaller; filled with 1.0 -- optimistic: a tile
+    nobody has drawn from outranks every trained tile until it is visited), scratch [C,Th,Tw] int32 (the update kernels' uint32 words,
+    all zero between calls), cdf [MULTICAM_MAXSEG, Th*Tw] int64 (the sampler's workspace: always all 64 rows, 512 bytes per tile --
+    1.3 MB at 800 x 800 with tile 16, 327 MB with tile 1)."""
+
+    def __init__(self, C: int, H: int, W: int, tile: int, device):
+        self.C, self.H, self.W, self.tile = int(C), int(H), int(W), int(tile)
+        if self.C < 1 or self.H < 1 or self.W < 1 or self.tile < 1 or self.H * self.W > ERRMAP_MAX_PIXELS:
+            raise _lib.McnerfError(f"ErrorMap needs C, H, W, tile >= 1 and H * W <= 2^26, got C = {C}, H = {H}, W = {W}, tile = {tile}")
+        self.Th, self.Tw = -(-self.H // self.tile), -(-self.W // self.tile)
+        self.err = torch.full((self.C, self.Th, self.Tw), 1.0, dtype=torch.float32, device=device)
+        self.scratch = torch.zeros((self.C, self.Th, self.Tw), dtype=torch.int32, device=device)
+        self.cdf = torch.empty((MULTICAM_MAXSEG, self.Th * self.Tw), dtype=torch.int64, device=device)
+
+    @property
+    def geom(self):
+        return self.C, self.H, self.W, self.tile
+
+
+def errmap_sample(emap: ErrorMap, seg_cam, seg_start, uniform_frac: float, u: Optional[Tensor] = None) -> Tensor:
+    """-> pix [n] int64 in [0, H * W): the first int(uniform_frac * n_k) rays of segment k = rays [seg_start[k], seg_start[k+1]) of
+    camera seg_cam[k] uniform over the image, the others with density proportional to the camera's clamped tile errors (tile by an
+    integer CDF, then uniform inside the tile).  With replacement.  `u` [n,2] fp32 are the draws (torch.rand from the device generator
+    when not given).  Two launches, no host synchronisation."""
+    cams, start, K, n = _seg_arrays(seg_cam, seg_start)
+    dev = emap.err.device
+    if u is None and emap.err.is_cuda:
+        u = torch.rand(n, 2, dtype=torch.float32, device=dev)
+    if u is not None and u.numel() != 2 * n:
+        raise _lib.McnerfError(f"errmap_sample: u must be [seg_start[-1] = {n}, 2], got {tuple(u.shape)}")
+    pix = torch.empty(n, dtype=torch.int64, device=dev)
+    _lib.call("mcnerf_errmap_sample", _p(emap.err), *emap.geom, cams, start, K, n, float(uniform_frac), _p(u), _p(emap.cdf, torch.int64),
+              _p(pix, torch.int64), _stream())
+    return pix
+
+
+def errmap_update(emap: ErrorMap, seg_cam, seg_start, pix: Tensor, rgb: Tensor, gt: Tensor, beta: float) -> None:
+    """Per tile touched by the rays (pix [n] of the segments' cameras, rgb / gt [n,3]): E <- (1 - beta) E + beta max(mean squared
+    colour error of a ray in the tile), deterministic in the order of arrival; rays with a non-finite error or a pixel outside the
+    image are skipped, other tiles keep their bits, emap.scratch is all zero again afterwards.  Two launches."""
+    cams, start, K, n = _seg_arrays(seg_cam, seg_start)
+    if pix.numel() != n or rgb.numel() != 3 * n or gt.numel() != 3 * n:
+        raise _lib.McnerfError(f"errmap_update: pix / rgb / gt must hold seg_start[-1] = {n} rays, got {tuple(pix.shape)}, {tuple(rgb.shape)}, {tuple(gt.shape)}")
+    _lib.call("mcnerf_errmap_update", _p(emap.err), _p(emap.scratch, torch.int32), *emap.geom, cams, start, K, n, _p(pix, torch.int64),
+              _p(rgb), _p(gt), *voxel_blend(beta), _stream())
+
+
 def cap_gather(idx: Tensor, perm: Tensor, keep: int):
     idx2 = torch.empty(keep, 2, dtype=torch.int32, device=idx.device)
     count = torch.empty(1, dtype=torch.int32, device=idx.device)
