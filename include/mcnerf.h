@@ -316,6 +316,28 @@ int mcnerf_ray_batch_bwd(const float* pose, const float* kinv, int C, const int3
                          int n, int W, const int64_t* pix, const float* d_rays_d, const float* d_rays_o,
                          float* d_pose, float* d_kinv, void* stream);
 
+/* ---- The same preamble with per-camera radial lens distortion (`lens_model` = "radial", a sys_param key of this build; the default,
+ * "pinhole", runs the entry points above as before).  New symbols only: MCNERF_ABI_VERSION stays 7.  The reference has no lens model.
+ *
+ * lens [C,2] = (k1, k2) per training camera: OpenCV's two-coefficient radial model, (x_d, y_d) = (1 + k1 r^2 + k2 r^4) (x_u, y_u) with
+ * r^2 = x_u^2 + y_u^2 on the normalised image plane.  A pixel's ray needs the inverse: cam = Kinv [u + 1/2, v + 1/2, 1]^T as
+ * mcnerf_raygen_fwd forms it, (x_d, y_d) = cam[0..1], r_d = |(x_d, y_d)|, then eight safeguarded Newton steps on the radius from r = r_d,
+ *   q = r^2;  f' = 1 + q (3 k1 + 5 k2 q);  r <- r - (r (1 + q (k1 + k2 q)) - r_d) / max(f', 0.25);  r <- min(max(r, 0), 2 r_d)
+ * and cam <- (s x_d, s y_d, cam[2]), s = r / r_d (1 at r_d = 0), rotated and normalised as mcnerf_raygen_fwd does (csrc/mcnerf_lens.h
+ * states the model in full).  Every output is finite for any finite k; at k = 0 every output has the bits of mcnerf_ray_batch_fwd.
+ *
+ * mcnerf_lens_ray_batch_fwd: mcnerf_ray_batch_fwd plus `lens`; ONE launch; pixels (the same draw from the same seed word) and ground
+ *   truth exactly as mcnerf_ray_batch_fwd.  K = 1 is a one-segment table.
+ * mcnerf_lens_ray_batch_bwd: mcnerf_ray_batch_bwd plus `lens` and d_lens [C,2]; ACCUMULATES into d_pose, d_kinv, d_lens (caller zeroes
+ *   them).  The root is differentiated implicitly at the final radius, not through the iterations.
+ * Both refuse, before any device work, everything mcnerf_ray_batch_fwd / _bwd refuse and a null lens / d_lens. */
+int mcnerf_lens_ray_batch_fwd(const float* pose, const float* kinv, const float* lens, int C, const int32_t* seg_cam, const int32_t* seg_start,
+                              int K, int n, int H, int W, const int64_t* pix_in, const uint32_t* seed, const uint8_t* images, int channels,
+                              int64_t* pix_out, float* rays_d, float* rays_o, float* gt, void* stream);
+int mcnerf_lens_ray_batch_bwd(const float* pose, const float* kinv, const float* lens, int C, const int32_t* seg_cam, const int32_t* seg_start,
+                              int K, int n, int W, const int64_t* pix, const float* d_rays_d, const float* d_rays_o,
+                              float* d_pose, float* d_kinv, float* d_lens, void* stream);
+
 /* Fused camera parametrisation of all C cameras.
  * Replaces add_weights2intr / add_weights2pose / add_weights2calib_pose / se3_to_SE3 / taylor_A,B,C /
  * inverse_intrinsic (model/mc_nerf.py:171-210, 269-316) and the calibration reprojection branch get_reproject_pixels /

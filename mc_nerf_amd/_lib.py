@@ -70,6 +70,8 @@ SIGNATURES = {
     "mcnerf_gather_gt": (_I, [_P, _I, _P, _I, _P, _P]),
     "mcnerf_ray_batch_fwd": (_I, [_P, _P, _I, _P, _P, _I, _I, _I, _I, _P, _P, _P, _I, _P, _P, _P, _P, _P]),
     "mcnerf_ray_batch_bwd": (_I, [_P, _P, _I, _P, _P, _I, _I, _I, _P, _P, _P, _P, _P, _P]),
+    "mcnerf_lens_ray_batch_fwd": (_I, [_P, _P, _P, _I, _P, _P, _I, _I, _I, _I, _P, _P, _P, _I, _P, _P, _P, _P, _P]),
+    "mcnerf_lens_ray_batch_bwd": (_I, [_P, _P, _P, _I, _P, _P, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P]),
     "mcnerf_camera_fwd": (_I, [_P, _P, _P, _P, _P, _P, _I, _I, _I, _P, _P, _P, _P, _P, _P, _I, _P, _P, _P]),
     "mcnerf_camera_bwd": (_I, [_P, _P, _P, _P, _P, _P, _I, _I, _I, _P, _P, _P, _P, _P, _P, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     "mcnerf_reproj_loss_fwd": (_I, [_P, _P, _I, _I, _I, _P, _P]),

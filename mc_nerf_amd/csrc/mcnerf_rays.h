@@ -50,6 +50,50 @@ __device__ __forceinline__ void mcn_ray_of_pixel(const float* P, const float* K,
     for (int c = 0; c < 3; ++c) { rays_d[i * 3 + c] = d[c] / nrm; rays_o[i * 3 + c] = o[c]; }
 }
 
+// mcn_ray_of_pixel in two halves, for a caller that changes `cam` between the lift and the rotation (the lens model of
+// mcnerf_lens.h).  Each half repeats the expressions of mcn_ray_of_pixel above term for term: called back to back with `cam`
+// unchanged they give its bits.
+__device__ __forceinline__ void mcn_cam_of_pixel(const float* K, long long pid, int W, float* cam) {
+    const float u = (float)(pid % W) + 0.5f, v = (float)(pid / W) + 0.5f;
+#pragma unroll
+    for (int r = 0; r < 3; ++r) cam[r] = __fadd_rn(__fadd_rn(__fmul_rn(u, K[r * 3]), __fmul_rn(v, K[r * 3 + 1])), K[r * 3 + 2]);
+}
+__device__ __forceinline__ void mcn_ray_of_cam(const float* P, const float* cam, float* rays_d, float* rays_o, int i) {
+    float d[3], o[3];
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+        const float ti = -(__fadd_rn(__fadd_rn(__fmul_rn(P[0 * 4 + c], P[3]), __fmul_rn(P[1 * 4 + c], P[7])), __fmul_rn(P[2 * 4 + c], P[11])));
+        const float w = __fadd_rn(__fadd_rn(__fadd_rn(__fmul_rn(cam[0], P[0 * 4 + c]), __fmul_rn(cam[1], P[1 * 4 + c])), __fmul_rn(cam[2], P[2 * 4 + c])), ti);
+        o[c] = ti;
+        d[c] = __fsub_rn(w, ti);
+    }
+    const float nrm = sqrtf(d[0] * d[0] + d[1] * d[1] + d[2] * d[2]);
+#pragma unroll
+    for (int c = 0; c < 3; ++c) { rays_d[i * 3 + c] = d[c] / nrm; rays_o[i * 3 + c] = o[c]; }
+}
+
+// The part of mcn_raygen_bwd_ray below that depends on the lifted `cam` only, for the same caller: the direction's terms
+// acc[0..8] dR[j][c] are accumulated and gcam [3], the gradient arriving at `cam`, is handed back (the caller turns it into the
+// dKinv terms acc[9..17] and adds the origin gradients acc[18..20] itself).  The expressions are those of mcn_raygen_bwd_ray.
+__device__ __forceinline__ void mcn_raygen_bwd_cam(const float* P, const float* cam, const float* d_rays_d, int i, float* gcam, float* acc) {
+    float q[3];
+#pragma unroll
+    for (int c = 0; c < 3; ++c) q[c] = cam[0] * P[c] + cam[1] * P[4 + c] + cam[2] * P[8 + c];
+    const float inv = 1.f / sqrtf(q[0] * q[0] + q[1] * q[1] + q[2] * q[2]);
+    const float gd[3] = {d_rays_d[i * 3], d_rays_d[i * 3 + 1], d_rays_d[i * 3 + 2]};
+    const float dn[3] = {q[0] * inv, q[1] * inv, q[2] * inv};
+    const float dot = dn[0] * gd[0] + dn[1] * gd[1] + dn[2] * gd[2];
+    float gq[3];
+#pragma unroll
+    for (int c = 0; c < 3; ++c) gq[c] = (gd[c] - dn[c] * dot) * inv;
+#pragma unroll
+    for (int j = 0; j < 3; ++j) {
+        gcam[j] = P[j * 4] * gq[0] + P[j * 4 + 1] * gq[1] + P[j * 4 + 2] * gq[2];
+#pragma unroll
+        for (int c = 0; c < 3; ++c) acc[j * 3 + c] += cam[j] * gq[c];        // dR[j][c] from the direction
+    }
+}
+
 // One ray's terms of the backward: acc[0..8] dR[j][c] from the direction, acc[9..17] dKinv[j][k], acc[18..20] the sum of the
 // origin gradients (turned into pose terms once per block by mcn_raygen_bwd_flush).  Ray i of pix / d_rays_d / d_rays_o.
 __device__ __forceinline__ void mcn_raygen_bwd_ray(const float* P, const float* K, const long long* pix, int W, const float* d_rays_d,

@@ -22,9 +22,10 @@ import torch.distributed as dist
 
 from .. import ops
 from ..data import DeviceImageSet
+from ..lens import distort_pixels, lens_model_setting
 from .loss import color_calib_settings
 from .net_block import CorseFine_NeRF, SinCosEmbedding
-from .render import CameraFn, RayBatchFn, RaygenFn, Rays, RenderCall, RenderSettings, RenderTrainFn, SamplePass, _pool, render_test, run_pass
+from .render import CameraFn, LensRayBatchFn, RayBatchFn, RaygenFn, Rays, RenderCall, RenderSettings, RenderTrainFn, SamplePass, _pool, render_test, run_pass
 
 
 def _rank():
@@ -499,6 +500,10 @@ class MC_Model(nn.Module):
         self.pixel_sampler = sys_param.get("pixel_sampler", "uniform")
         if not isinstance(self.pixel_sampler, str) or self.pixel_sampler not in ("uniform", "error"):
             raise ValueError(f"pixel_sampler must be 'uniform' or 'error', got {self.pixel_sampler!r}")
+        # "lens_model" is this build's own key as well: "pinhole" (the default: today's path, no parameter) or "radial" --
+        # one more parameter weights_lens [C,2] = (k1, k2) per training camera, OpenCV's two-coefficient radial model, undistorted inside
+        # the NeRF stages' ray kernel (LensRayBatchFn) and applied in closed form to the calibration-tag reprojection
+        self.lens_model = lens_model_setting(sys_param)
         self._error_map = None            # ops.ErrorMap, allocated on first use ("error" mode only): not a parameter, not a buffer
         if self.pixel_sampler == "error":
             self.error_tile, self.error_beta, self.error_uniform_frac = self._error_settings(sys_param)
@@ -532,6 +537,8 @@ class MC_Model(nn.Module):
             self.register_parameter(name, nn.Parameter(torch.ones(shape, device=dev), requires_grad=True))
         if self.color_calib == "affine":     # an offset from identity (zeros): weight decay pulls towards "no correction"
             self.register_parameter("weights_color", nn.Parameter(torch.zeros(C, 6, device=dev), requires_grad=True))
+        if self.lens_model == "radial":      # an offset from "no distortion" (zeros), as weights_color
+            self.register_parameter("weights_lens", nn.Parameter(torch.zeros(C, 2, device=dev), requires_grad=True))
 
     # ------------------------------------------------------------------ error-guided pixel sampling
     @staticmethod
@@ -607,6 +614,31 @@ class MC_Model(nn.Module):
         w = self.weights_color.detach()
         return 1.0 + w[:, :3], w[:, 3:].clone()
 
+    # ------------------------------------------------------------------ radial lens distortion
+    def lens_coefficients(self):
+        """(k1, k2) of the training cameras [C,2], detached."""
+        if self.lens_model != "radial":
+            raise ValueError("lens_coefficients() needs lens_model = 'radial'")
+        return self.weights_lens.detach().clone()
+
+    @torch.no_grad()
+    def train_camera_rays(self, cam):
+        """All H*W rays (rays_d, rays_o) of training camera `cam` through its learnt pose, K and lens."""
+        if self.lens_model != "radial":
+            raise ValueError("train_camera_rays() needs lens_model = 'radial'")
+        cam = _int_key({"cam": cam}, "cam", None, 0, self.train_numb - 1)
+        keep = (self.intr_inv_adj, getattr(self, "_reproj", [None, None]))      # (a step's cached camera outputs stay as they were)
+        intr_adj, pose_adj, _ = self.add_weights2param(True, True, False)
+        kinv = self.intr_inv_adj if self.intr_inv_adj is not None else self.inverse_intrinsic(intr_adj)
+        self.intr_inv_adj, self._reproj = keep
+        npix = self.img_h * self.img_w
+        if getattr(self, "_all_pix", None) is None:
+            self._all_pix = torch.arange(npix, device=self.device)
+        _, rays_d, rays_o, _ = ops.lens_ray_batch_fwd(pose_adj.contiguous().float(), kinv.contiguous().float(),
+                                                      self.weights_lens.detach().contiguous(), [cam], [0, npix], self.img_h, self.img_w,
+                                                      pix=self._all_pix)
+        return rays_d, rays_o
+
     # ------------------------------------------------------------------ forward (:58-122)
     def forward(self, *args):
         if self.sys_param["mode"] == 0:
@@ -639,9 +671,16 @@ class MC_Model(nn.Module):
             # pixel subset first (same device randperm as :329), rays only for those pixels
             error = self.pixel_sampler == "error"        # (with replacement: always `batch` rays)
             rand_idx = self._draw_error_pixels([cam], [0, self.batch]) if error else self.sample_pixels(self.img_h * self.img_w)
-            rays_d, rays_o = RaygenFn.apply(self.pose_adj[cam], kinv, rand_idx, self.img_w)
+            if self.lens_model == "radial":              # the fused kernel on a one-segment table; the draw above is its pix_in
+                kinv_all = self.intr_inv_adj if self.intr_inv_adj is not None else self.inverse_intrinsic(self.intr_adj)
+                _, rays_d, rays_o, gt = LensRayBatchFn.apply(self.pose_adj, kinv_all, self.weights_lens, [cam], [0, int(rand_idx.shape[0])],
+                                                             self.img_h, self.img_w, images.images if images is not None else None, rand_idx)
+            else:
+                rays_d, rays_o = RaygenFn.apply(self.pose_adj[cam], kinv, rand_idx, self.img_w)
+                gt = None
             rgbs_c, rgbs_f = self.nerf(rays_d, rays_o, epoch, cur_ratio if joint else 1)
-            gt = images.gather(cam, rand_idx) if images is not None else gt_rgbs.reshape(-1, 3)[rand_idx]
+            if gt is None:
+                gt = images.gather(cam, rand_idx) if images is not None else gt_rgbs.reshape(-1, 3)[rand_idx]
             loss_dict["rgb"] = [rgbs_c, rgbs_f, gt]
             if self.color_calib == "affine":
                 loss_dict["color"] = [self.weights_color, [cam], [0, int(rgbs_c.shape[0])]]
@@ -678,8 +717,12 @@ class MC_Model(nn.Module):
         pix_in = self.sample_pixels_multi(self.img_h * self.img_w, seg_start)
         if pix_in is None and self.pixel_sampler == "error":      # (an injected draw still wins)
             pix_in = self._draw_error_pixels(cams, seg_start)
-        pix, rays_d, rays_o, gt = RayBatchFn.apply(self.pose_adj, kinv_all, cams, seg_start, self.img_h, self.img_w,
-                                                   images.images if images is not None else None, pix_in)
+        if self.lens_model == "radial":
+            pix, rays_d, rays_o, gt = LensRayBatchFn.apply(self.pose_adj, kinv_all, self.weights_lens, cams, seg_start, self.img_h, self.img_w,
+                                                           images.images if images is not None else None, pix_in)
+        else:
+            pix, rays_d, rays_o, gt = RayBatchFn.apply(self.pose_adj, kinv_all, cams, seg_start, self.img_h, self.img_w,
+                                                       images.images if images is not None else None, pix_in)
         rgbs_c, rgbs_f = self.nerf(rays_d, rays_o, epoch, cur_ratio if joint else 1)
         if gt is None:                     # host float stack [K,H,W,3] / [K,H*W,3]: item k is the image of segment k
             if self._seg_index is None:
@@ -823,7 +866,10 @@ class MC_Model(nn.Module):
     def _reproject(self, tag_wpts, intr_adj, pose_adj, which):
         """The pixels the fused camera kernel already produced (GPU), else the tensor-op restatement."""
         got = getattr(self, "_reproj", [None, None])[which]
-        return got if got is not None else self.get_reproject_pixels(tag_wpts, intr_adj, pose_adj)
+        pix = got if got is not None else self.get_reproject_pixels(tag_wpts, intr_adj, pose_adj)
+        if self.lens_model == "radial":      # the tags of a distorted camera are observed at distorted pixels (closed form, eager)
+            pix = distort_pixels(pix, intr_adj, self.weights_lens)
+        return pix
 
     def get_reproject_pixels(self, tag_wpts, intr_adj, pose_adj):
         """Projects calibration points [B,C,P,3] through [R|t] and K -> pixel coords [B,C,P,2]."""

@@ -407,6 +407,31 @@ class RayBatchFn(torch.autograd.Function):
         return d_pose, d_kinv, None, None, None, None, None, None, None
 
 
+class LensRayBatchFn(torch.autograd.Function):
+    """RayBatchFn with per-camera radial lens distortion (`lens_model` = "radial": ops.lens_ray_batch_fwd, one launch):
+    pix, rays_d, rays_o, gt = f(pose[C,3,4], kinv[C,3,3], lens[C,2]).  Differentiable wrt pose, kinv and lens; `pix` and `gt` are
+    non-differentiable outputs."""
+
+    @staticmethod
+    def forward(ctx, pose, kinv, lens, seg_cam, seg_start, H, W, images=None, pix=None, seed=None):
+        pose = pose.contiguous().float()
+        kinv = kinv.contiguous().float()
+        lens = lens.contiguous().float()
+        pix, d, o, gt = ops.lens_ray_batch_fwd(pose, kinv, lens, seg_cam, seg_start, H, W, images=images,
+                                               pix=None if pix is None else pix.contiguous(), seed=seed)
+        ctx.save_for_backward(pose, kinv, lens, pix)
+        ctx.table = (list(seg_cam), list(seg_start), W)
+        ctx.mark_non_differentiable(*(t for t in (pix, gt) if t is not None))
+        return pix, d, o, gt
+
+    @staticmethod
+    def backward(ctx, _g_pix, g_d, g_o, _g_gt):
+        pose, kinv, lens, pix = ctx.saved_tensors
+        seg_cam, seg_start, W = ctx.table
+        d_pose, d_kinv, d_lens = ops.lens_ray_batch_bwd(pose, kinv, lens, seg_cam, seg_start, W, pix, g_d.contiguous(), g_o.contiguous())
+        return d_pose, d_kinv, d_lens, None, None, None, None, None, None, None
+
+
 class CameraFn(torch.autograd.Function):
     """K, Kinv, pose, calib_pose, pix_intr, pix_extr = f(weights_pose, weights_pose_intr, weights_fx, weights_fy, weights_ux,
     weights_uy; calibration world points) for all cameras in one fused kernel each way (reference: model/mc_nerf.py:171-210,

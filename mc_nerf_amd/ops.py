@@ -383,6 +383,55 @@ def ray_batch_bwd(pose: Tensor, kinv: Tensor, seg_cam, seg_start, W: int, pix: T
     return d_pose, d_kinv
 
 
+def _lens_arg(lens: Tensor, C: int) -> Tensor:
+    if not lens.is_cuda:
+        raise _lib.McnerfError("the lens ray-batch ops need CUDA/HIP tensors (no CPU fallback)")
+    if lens.dim() != 2 or tuple(lens.shape) != (C, 2):
+        raise _lib.McnerfError(f"lens must be [C = {C}, 2] (k1, k2), got {tuple(lens.shape)}")
+    return lens
+
+
+def lens_ray_batch_fwd(pose: Tensor, kinv: Tensor, lens: Tensor, seg_cam, seg_start, H: int, W: int, images: Optional[Tensor] = None,
+                       pix: Optional[Tensor] = None, seed: Optional[Tensor] = None):
+    """`ray_batch_fwd` with per-camera radial lens distortion (`lens_model` = "radial"): lens [C,2] = (k1, k2); every
+    ray's lifted pixel is undistorted by eight safeguarded Newton steps before the rotation (csrc/mcnerf_lens.h).  Pixels (the same
+    draw from the same seed word) and ground truth as `ray_batch_fwd`; at lens = 0 every output has its bits.
+    -> (pix [n] int64, rays_d [n,3], rays_o [n,3], gt [n,3] | None)"""
+    cams, start, K, n = _seg_arrays(seg_cam, seg_start)
+    dev = pose.device
+    lens = _lens_arg(lens, int(pose.shape[0]))
+    if pix is None and seed is None:
+        seed = torch.randint(0, 2 ** 31 - 1, (1,), dtype=torch.int32, device=dev)
+    if pix is not None and pix.numel() != n:
+        raise _lib.McnerfError(f"pix must hold seg_start[-1] = {n} ids, got {pix.numel()}")
+    if images is not None and (images.dim() != 3 or images.shape[0] != pose.shape[0] or images.shape[1] != H * W):
+        raise _lib.McnerfError(f"images must be [C = {pose.shape[0]}, H*W = {H * W}, channels], got {tuple(images.shape)}")
+    pix_out = torch.empty(n, dtype=torch.int64, device=dev)
+    d = torch.empty(n, 3, dtype=torch.float32, device=dev)
+    o = torch.empty_like(d)
+    gt = torch.empty_like(d) if images is not None else None
+    _lib.call("mcnerf_lens_ray_batch_fwd", _p(pose), _p(kinv), _p(lens), int(pose.shape[0]), cams, start, K, n, int(H), int(W),
+              _p(pix, torch.int64), _p(seed, torch.int32), _p(images, torch.uint8), int(images.shape[-1]) if images is not None else 0,
+              _p(pix_out, torch.int64), _p(d), _p(o), _p(gt), _stream())
+    return pix_out, d, o, gt
+
+
+def lens_ray_batch_bwd(pose: Tensor, kinv: Tensor, lens: Tensor, seg_cam, seg_start, W: int, pix: Tensor, d_d: Tensor,
+                       d_o: Tensor) -> Tuple[Tensor, Tensor, Tensor]:
+    """Backward of `lens_ray_batch_fwd`: -> (d_pose [C,3,4], d_kinv [C,3,3], d_lens [C,2]); rows of cameras not in the table are
+    exactly zero, a camera listed twice receives the sum."""
+    cams, start, K, n = _seg_arrays(seg_cam, seg_start)
+    C = int(pose.shape[0])
+    lens = _lens_arg(lens, C)
+    z = torch.zeros(C * 23, dtype=torch.float32, device=pose.device)     # (one fill for the three accumulation targets)
+    d_pose, d_kinv, d_lens = z[:C * 12].view(C, 3, 4), z[C * 12:C * 21].view(C, 3, 3), z[C * 21:].view(C, 2)
+    if pix.numel() != n or d_d.numel() != 3 * n or d_o.numel() != 3 * n:
+        raise _lib.McnerfError(f"pix / d_rays_d / d_rays_o must hold seg_start[-1] = {n} rays")
+    _lib.call("mcnerf_lens_ray_batch_bwd", _p(pose), _p(kinv), _p(lens), C, cams, start, K, n, int(W), _p(pix, torch.int64),
+              _p(d_d), _p(d_o), _p(d_pose), _p(d_kinv), _p(d_lens), _stream())
+    return d_pose, d_kinv, d_lens
+
+
 def upload_f32(host_vals: Tensor, device) -> Tensor:
     """A small fp32 host tensor (<= 16 values) as a fresh device tensor, stream-ordered and without a host-device copy
     (the values travel as kernel arguments): the host never waits for the kernels already queued."""

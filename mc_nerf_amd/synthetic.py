@@ -195,15 +195,20 @@ def se3_log(pose: torch.Tensor) -> torch.Tensor:
     return torch.stack(out).float()
 
 
-def calibration_points(pose: torch.Tensor, K: torch.Tensor, seed: int = 0):
+def calibration_points(pose: torch.Tensor, K: torch.Tensor, seed: int = 0, lens=None):
     """Five world points per camera (tag centre + corners on a unit cube face) and their GT pixel
-    projections: the inputs of the reprojection branch (data/data_read.py:72-75 layout)."""
+    projections: the inputs of the reprojection branch (data/data_read.py:72-75 layout).  `lens` [C,2] = (k1, k2) per camera
+    (lens_distortion): the pixels are those a radially distorted camera observes (the closed-form forward model, in fp64)."""
     g = torch.Generator().manual_seed(seed)
     C = pose.shape[0]
     base = torch.tensor([[0, 0, 0.5], [-0.4, -0.4, 0.5], [0.4, -0.4, 0.5], [0.4, 0.4, 0.5], [-0.4, 0.4, 0.5]])
     wpts = base.unsqueeze(0).repeat(C, 1, 1) + 0.01 * torch.randn(C, 5, 3, generator=g)
     cam = torch.cat([wpts, torch.ones(C, 5, 1)], -1) @ pose.transpose(-2, -1)
     pix = cam @ K.transpose(-2, -1)
+    if lens is not None:
+        from .lens import distort_pixels
+        pinhole = (pix[..., :2] / pix[..., 2:]).double()
+        return wpts.unsqueeze(0), distort_pixels(pinhole, K.double(), lens.double()).float().unsqueeze(0)
     return wpts.unsqueeze(0), (pix[..., :2] / pix[..., 2:]).unsqueeze(0)
 
 
@@ -272,14 +277,41 @@ def blob_scene_render(rays_d, rays_o, near=1.0, far=8.0, n_quad=384):
 
 
 @torch.no_grad()
-def blob_scene_images(pose, K, H, W, chunk=8192):
-    """[C, H*W, 3] ground-truth images of the blob scene for world->cam poses [C,3,4] and intrinsics [C,3,3] (on their device)."""
+def lens_rays(pose, K, lens, H, W):
+    """All H*W rays (rays_d, rays_o [H*W,3] fp32) of ONE radially distorted camera (pose [3,4], K [3,3], lens [2] = (k1, k2)), built in
+    fp64 on the host: pixel centre -> normalised observed coordinates -> undistorted (the root to convergence) -> rotated, normalised."""
+    from .lens import undistort_normalised
+    P, Kinv, lens = pose.double().cpu(), torch.linalg.inv(K.double().cpu()), lens.double().cpu()
+    pid = torch.arange(H * W)
+    p = torch.stack([(pid % W).double() + 0.5, torch.div(pid, W, rounding_mode="floor").double() + 0.5, torch.ones(H * W, dtype=torch.float64)], -1)
+    cam = p @ Kinv.T
+    cam = torch.cat([undistort_normalised(cam[:, :2], lens.expand(H * W, 2)), cam[:, 2:]], -1)
+    q = cam @ P[:, :3]                                        # R^T cam
+    d = q / q.norm(dim=-1, keepdim=True)
+    o = -(P[:, :3].T @ P[:, 3])
+    return d.float(), o.float().expand(H * W, 3).contiguous()
+
+
+def lens_distortion(C: int, seed: int = 0, k1_spread: float = 0.05, k2_spread: float = 0.005):
+    """Per-camera radial distortion of a rig of cheap lenses: lens [C,2] = (k1, k2), OpenCV's meaning and sign; normal draws of the
+    given spreads (not centred: a common distortion is observable, unlike a common colour gain)."""
+    gen = torch.Generator().manual_seed(seed)
+    return torch.stack([k1_spread * torch.randn(C, generator=gen), k2_spread * torch.randn(C, generator=gen)], -1)
+
+
+@torch.no_grad()
+def blob_scene_images(pose, K, H, W, chunk=8192, lens=None):
+    """[C, H*W, 3] ground-truth images of the blob scene for world->cam poses [C,3,4] and intrinsics [C,3,3] (on their device).
+    `lens` [C,2] (lens_distortion): the images radially distorted cameras observe, from fp64 undistorted rays (lens_rays)."""
     from . import ops
     Kinv = torch.linalg.inv(K)
     allpix = torch.arange(H * W, device=pose.device)
     out = []
     for i in range(pose.shape[0]):
-        d, o = ops.raygen_fwd(pose[i].contiguous(), Kinv[i].contiguous(), allpix, W)
+        if lens is not None:
+            d, o = (t.to(pose.device) for t in lens_rays(pose[i], K[i], lens[i], H, W))
+        else:
+            d, o = ops.raygen_fwd(pose[i].contiguous(), Kinv[i].contiguous(), allpix, W)
         out.append(torch.cat([blob_scene_render(d[j:j + chunk], o[j:j + chunk]) for j in range(0, H * W, chunk)]))
     return torch.stack(out)
 
