@@ -124,49 +124,48 @@ static int fill_segments(const char* name, McnSegTable& t, const int32_t* seg_ca
     return 0;
 }
 
+// The ray-batch pair (rays.hip) and the pair with per-camera radial lens distortion (lens.hip) behind one binding per direction:
+// `name` is the entry point's, for the error text; `with_lens` says that lens (and d_lens) must be there.
+static int ray_batch_fwd(const char* name, bool with_lens, const float* pose, const float* kinv, const float* lens, int C, const int32_t* seg_cam,
+                         const int32_t* seg_start, int K, int n, int H, int W, const int64_t* pix_in, const uint32_t* seed, const uint8_t* images,
+                         int channels, int64_t* pix_out, float* rays_d, float* rays_o, float* gt, void* stream) {
+    REQ(H > 0 && W > 0 && (long long)H * W <= (1ll << 31), name);
+    McnSegTable t = {};
+    if (int rc = fill_segments(name, t, seg_cam, seg_start, K, C, n, pix_in ? (long long)n : (long long)H * W)) return rc;
+    REQ(!images || channels == 3 || channels == 4, name);
+    REQ(pose && kinv && (lens || !with_lens) && pix_out && rays_d && rays_o && (pix_in || seed) && (!images || gt), name);
+    const McnRayBatchArgs a = {pose, kinv, (const long long*)pix_in, seed, images, channels, n, H, W, (long long*)pix_out, rays_d, rays_o, gt};
+    return check(name, with_lens ? mcn_launch_lens_ray_batch_fwd({a, lens}, t, (hipStream_t)stream) : mcn_launch_ray_batch_fwd(a, t, (hipStream_t)stream));
+}
+static int ray_batch_bwd(const char* name, bool with_lens, const float* pose, const float* kinv, const float* lens, int C, const int32_t* seg_cam,
+                         const int32_t* seg_start, int K, int n, int W, const int64_t* pix, const float* d_rays_d, const float* d_rays_o,
+                         float* d_pose, float* d_kinv, float* d_lens, void* stream) {
+    REQ(W > 0, name);
+    McnSegTable t = {};
+    if (int rc = fill_segments(name, t, seg_cam, seg_start, K, C, n, n)) return rc;
+    REQ(pose && kinv && pix && d_rays_d && d_rays_o && d_pose && d_kinv && ((lens && d_lens) || !with_lens), name);
+    const McnRayBatchBwdArgs a = {pose, kinv, (const long long*)pix, W, d_rays_d, d_rays_o, d_pose, d_kinv};
+    return check(name, with_lens ? mcn_launch_lens_ray_batch_bwd({a, lens, d_lens}, t, (hipStream_t)stream) : mcn_launch_ray_batch_bwd(a, t, (hipStream_t)stream));
+}
 int mcnerf_ray_batch_fwd(const float* pose, const float* kinv, int C, const int32_t* seg_cam, const int32_t* seg_start, int K,
                          int n, int H, int W, const int64_t* pix_in, const uint32_t* seed, const uint8_t* images, int channels,
                          int64_t* pix_out, float* rays_d, float* rays_o, float* gt, void* stream) {
-    REQ(H > 0 && W > 0 && (long long)H * W <= (1ll << 31), "mcnerf_ray_batch_fwd");
-    McnSegTable t = {};
-    if (int rc = fill_segments("mcnerf_ray_batch_fwd", t, seg_cam, seg_start, K, C, n, pix_in ? (long long)n : (long long)H * W)) return rc;
-    REQ(!images || channels == 3 || channels == 4, "mcnerf_ray_batch_fwd");
-    REQ(pose && kinv && pix_out && rays_d && rays_o && (pix_in || seed) && (!images || gt), "mcnerf_ray_batch_fwd");
-    McnRayBatchArgs a = {pose, kinv, (const long long*)pix_in, seed, images, channels, n, H, W, (long long*)pix_out, rays_d, rays_o, gt};
-    return check("mcnerf_ray_batch_fwd", mcn_launch_ray_batch_fwd(a, t, (hipStream_t)stream));
+    return ray_batch_fwd("mcnerf_ray_batch_fwd", false, pose, kinv, nullptr, C, seg_cam, seg_start, K, n, H, W, pix_in, seed, images, channels, pix_out, rays_d, rays_o, gt, stream);
 }
 int mcnerf_ray_batch_bwd(const float* pose, const float* kinv, int C, const int32_t* seg_cam, const int32_t* seg_start, int K,
                          int n, int W, const int64_t* pix, const float* d_rays_d, const float* d_rays_o,
                          float* d_pose, float* d_kinv, void* stream) {
-    REQ(W > 0, "mcnerf_ray_batch_bwd");
-    McnSegTable t = {};
-    if (int rc = fill_segments("mcnerf_ray_batch_bwd", t, seg_cam, seg_start, K, C, n, n)) return rc;
-    REQ(pose && kinv && pix && d_rays_d && d_rays_o && d_pose && d_kinv, "mcnerf_ray_batch_bwd");
-    McnRayBatchBwdArgs a = {pose, kinv, (const long long*)pix, W, d_rays_d, d_rays_o, d_pose, d_kinv};
-    return check("mcnerf_ray_batch_bwd", mcn_launch_ray_batch_bwd(a, t, (hipStream_t)stream));
+    return ray_batch_bwd("mcnerf_ray_batch_bwd", false, pose, kinv, nullptr, C, seg_cam, seg_start, K, n, W, pix, d_rays_d, d_rays_o, d_pose, d_kinv, nullptr, stream);
 }
-
-// The ray-batch pair with per-camera radial lens distortion (lens.hip): the checks of mcnerf_ray_batch_fwd / _bwd and the lens pointers.
 int mcnerf_lens_ray_batch_fwd(const float* pose, const float* kinv, const float* lens, int C, const int32_t* seg_cam, const int32_t* seg_start,
                               int K, int n, int H, int W, const int64_t* pix_in, const uint32_t* seed, const uint8_t* images, int channels,
                               int64_t* pix_out, float* rays_d, float* rays_o, float* gt, void* stream) {
-    REQ(H > 0 && W > 0 && (long long)H * W <= (1ll << 31), "mcnerf_lens_ray_batch_fwd");
-    McnSegTable t = {};
-    if (int rc = fill_segments("mcnerf_lens_ray_batch_fwd", t, seg_cam, seg_start, K, C, n, pix_in ? (long long)n : (long long)H * W)) return rc;
-    REQ(!images || channels == 3 || channels == 4, "mcnerf_lens_ray_batch_fwd");
-    REQ(pose && kinv && lens && pix_out && rays_d && rays_o && (pix_in || seed) && (!images || gt), "mcnerf_lens_ray_batch_fwd");
-    McnLensRayBatchArgs a = {{pose, kinv, (const long long*)pix_in, seed, images, channels, n, H, W, (long long*)pix_out, rays_d, rays_o, gt}, lens};
-    return check("mcnerf_lens_ray_batch_fwd", mcn_launch_lens_ray_batch_fwd(a, t, (hipStream_t)stream));
+    return ray_batch_fwd("mcnerf_lens_ray_batch_fwd", true, pose, kinv, lens, C, seg_cam, seg_start, K, n, H, W, pix_in, seed, images, channels, pix_out, rays_d, rays_o, gt, stream);
 }
 int mcnerf_lens_ray_batch_bwd(const float* pose, const float* kinv, const float* lens, int C, const int32_t* seg_cam, const int32_t* seg_start,
                               int K, int n, int W, const int64_t* pix, const float* d_rays_d, const float* d_rays_o,
                               float* d_pose, float* d_kinv, float* d_lens, void* stream) {
-    REQ(W > 0, "mcnerf_lens_ray_batch_bwd");
-    McnSegTable t = {};
-    if (int rc = fill_segments("mcnerf_lens_ray_batch_bwd", t, seg_cam, seg_start, K, C, n, n)) return rc;
-    REQ(pose && kinv && lens && pix && d_rays_d && d_rays_o && d_pose && d_kinv && d_lens, "mcnerf_lens_ray_batch_bwd");
-    McnLensRayBatchBwdArgs a = {{pose, kinv, (const long long*)pix, W, d_rays_d, d_rays_o, d_pose, d_kinv}, lens, d_lens};
-    return check("mcnerf_lens_ray_batch_bwd", mcn_launch_lens_ray_batch_bwd(a, t, (hipStream_t)stream));
+    return ray_batch_bwd("mcnerf_lens_ray_batch_bwd", true, pose, kinv, lens, C, seg_cam, seg_start, K, n, W, pix, d_rays_d, d_rays_o, d_pose, d_kinv, d_lens, stream);
 }
 
 int mcnerf_mlp_fwd(int depth, int width, int skip, const float* params, const float* packed,

@@ -132,10 +132,8 @@ __global__ __launch_bounds__(256) void train_loss_calib_kernel(McnTrainLossCalib
 }
 
 hipError_t mcn_launch_train_loss_calib(const McnTrainLossCalibArgs& a, const McnSegTable& t, hipStream_t st) {
-    int longest = 0;
-    for (int k = 0; k < t.K; ++k) longest = t.start[k + 1] - t.start[k] > longest ? t.start[k + 1] - t.start[k] : longest;
     const int cap = MCN_CALIB_BLOCKS / t.K > 1 ? MCN_CALIB_BLOCKS / t.K : 1;       // K * blocks <= MCN_CALIB_BLOCKS (K <= 64)
-    int blocks = (longest + 255) / 256;
+    int blocks = (mcn_longest_segment(t) + 255) / 256;
     if (blocks > cap) blocks = cap;
     if (blocks < 1) blocks = 1;
     hipLaunchKernelGGL(train_loss_calib_kernel, dim3(blocks, t.K), dim3(256), 0, st, a, t);

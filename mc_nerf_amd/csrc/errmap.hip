@@ -26,13 +26,6 @@
 
 #define ERR_CDF_ITEMS 8             // consecutive tiles a thread sums serially: one block scan covers 256 * 8 tiles
 
-// the segment of ray i, as ray_batch_fwd_kernel finds it: the last segment that starts at or before i (empty segments are passed over)
-__device__ __forceinline__ int err_segment(const McnSegTable& t, int i) {
-    int k = 0;
-    for (int s = 1; s < t.K; ++s)
-        if (i >= t.start[s]) k = s;
-    return k;
-}
 // rows and columns of tile (ty, tx): `tile`, or what is left of the image at its lower / right edge
 __device__ __forceinline__ int err_tile_h(const McnErrGeom& g, int ty) { return min(g.tile, g.H - ty * g.tile); }
 __device__ __forceinline__ int err_tile_w(const McnErrGeom& g, int tx) { return min(g.tile, g.W - tx * g.tile); }
@@ -83,7 +76,7 @@ __global__ __launch_bounds__(256) void errmap_draw_kernel(McnErrSampleArgs a, Mc
     const int i = blockIdx.x * 256 + threadIdx.x;
     if (i >= a.n) return;
     const McnErrGeom& g = a.g;
-    const int k = err_segment(t, i);
+    const int k = mcn_segment_of_ray(t, i).k;              // (this kernel takes the number only and indexes the table with it, as it always did)
     const int j = i - t.start[k], nk = t.start[k + 1] - t.start[k];
     const int n_u = (int)((double)a.uniform_frac * (double)nk);
     const float u0 = err_unit(a.u[(size_t)i * 2]), u1 = err_unit(a.u[(size_t)i * 2 + 1]);
@@ -126,7 +119,7 @@ __device__ __forceinline__ bool err_item(const McnErrUpdateArgs& a, const McnSeg
     const float d0 = __fsub_rn(c[0], w[0]), d1 = __fsub_rn(c[1], w[1]), d2 = __fsub_rn(c[2], w[2]);
     e = __fmul_rn(__fadd_rn(__fadd_rn(__fmul_rn(d0, d0), __fmul_rn(d1, d1)), __fmul_rn(d2, d2)), 0.333333343f);
     const int y = (int)(p / g.W), x = (int)(p - (long long)y * g.W);
-    cell = (size_t)t.cam[err_segment(t, i)] * g.T + (size_t)(y / g.tile) * g.Tw + (size_t)(x / g.tile);
+    cell = (size_t)t.cam[mcn_segment_of_ray(t, i).k] * g.T + (size_t)(y / g.tile) * g.Tw + (size_t)(x / g.tile);
     return (__float_as_uint(e) & 0x7F800000u) != 0x7F800000u;
 }
 __global__ __launch_bounds__(256) void errmap_max_kernel(McnErrUpdateArgs a, McnSegTable t) {

@@ -1,5 +1,6 @@
 // Per-camera radial lens distortion of the training cameras (`lens_model` = "radial"): the device arithmetic of the
-// undistortion and the launcher interface of lens.hip.  A header of its own, as mcnerf_multicam.h: mcnerf_kernels.h and
+// undistortion, forward and backward, and the launcher interface of lens.hip.  The ray arithmetic around it is mcnerf_rays.h's, which
+// calls these functions where its LENS option is on.  A header of its own, as mcnerf_multicam.h: mcnerf_kernels.h and
 // mcnerf_common.h are part of the digest that ties the recorded MLP-kernel traffic to the sources.
 //
 // THE MODEL.  lens [C,2] = (k1, k2) per training camera, OpenCV's two-coefficient radial model with its meaning and sign.  With
@@ -7,10 +8,10 @@
 //     r_u^2 = x_u^2 + y_u^2,   D(r) = 1 + k1 r^2 + k2 r^4,   (x_d, y_d) = D(r_u) (x_u, y_u)            world -> pixel: closed form
 // Pixel -> ray needs the inverse: a FIXED-COUNT safeguarded Newton iteration on the radius (no data-dependent exit: the wave stays
 // uniform):
-//     cam = Kinv [u + 1/2, v + 1/2, 1]^T          the three rounded expressions of mcn_ray_of_pixel; x_d = cam[0], y_d = cam[1]
+//     cam = Kinv [u + 1/2, v + 1/2, 1]^T          mcn_cam_of_pixel; x_d = cam[0], y_d = cam[1]
 //     r_d = sqrtf(x_d^2 + y_d^2);  r <- r_d
 //     8 times:  q = r^2;  f' = 1 + q (3 k1 + 5 k2 q);  r <- r - (r (1 + q (k1 + k2 q)) - r_d) / max(f', 0.25);  r <- min(max(r, 0), 2 r_d)
-//     s = r_d > 0 ? r / r_d : 1;   cam <- (s x_d, s y_d, cam[2])        then rotate, subtract the origin, normalise as mcn_ray_of_pixel
+//     s = r_d > 0 ? r / r_d : 1;   cam <- (s x_d, s y_d, cam[2])        then mcn_ray_of_cam: rotate, subtract the origin, normalise
 // The distortion acts on cam[0], cam[1]: the normalised image plane whenever Kinv's last row is (0, 0, 1).  At k1 = k2 = 0 r never
 // moves and s = 1 exactly: the rays are the bits of the pinhole kernels.  The floor on f' and the clamp keep every output finite for
 // any finite k; outside the region where r D(r) is monotone the result is defined by the iteration above and nothing more.
@@ -58,6 +59,19 @@ __device__ __forceinline__ void mcn_lens_ds(float s, float r, float k1, float k2
     ds[0] = -(sf * q);
     ds[1] = -(sf * (q * q));
     ds[2] = -(sf * (s * s) * (2.f * k1 + (4.f * k2) * q));
+}
+
+// The backward of mcn_lens_undistort_cam at the observed point (xd, yd), with its s and r: d_k [2] += h (ds/dk1, ds/dk2), and gcam,
+// the gradient arriving at the undistorted cam, becomes the gradient at the observed one (gcam[2] passes through).
+__device__ __forceinline__ void mcn_lens_undistort_bwd(float xd, float yd, float s, float r, float k1, float k2, float* gcam, float* d_k) {
+    float ds[3];
+    mcn_lens_ds(s, r, k1, k2, ds);
+    const float h = gcam[0] * xd + gcam[1] * yd;
+    d_k[0] += h * ds[0];
+    d_k[1] += h * ds[1];
+    const float hx = h * ds[2];
+    gcam[0] = gcam[0] * s + hx * xd;
+    gcam[1] = gcam[1] * s + hx * yd;
 }
 
 struct McnLensRayBatchArgs {

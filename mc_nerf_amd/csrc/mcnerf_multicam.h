@@ -11,6 +11,29 @@ struct McnSegTable {
     int cam[MCN_MULTICAM_MAXSEG];
     int start[MCN_MULTICAM_MAXSEG + 1];
 };
+// The segment k of ray i, its camera and its first ray `lo`: the last segment that starts at or before i (empty segments are passed
+// over; the host checked that start is monotone from 0 to n).  Every table word is a wave-uniform scalar load and the three results
+// are carried through the scan: indexing the by-value table with a per-lane k afterwards can push it into scratch.
+struct McnSegment { int k, cam, lo; };
+__device__ __forceinline__ McnSegment mcn_segment_of_ray(const McnSegTable& t, int i) {
+    int k = 0, cam = t.cam[0], lo = 0;
+    for (int s = 1; s < t.K; ++s) {
+        const int st = t.start[s];
+        if (i >= st) { k = s; cam = t.cam[s]; lo = st; }
+    }
+    return {k, cam, lo};
+}
+inline int mcn_longest_segment(const McnSegTable& t) {
+    int longest = 0;
+    for (int k = 0; k < t.K; ++k) longest = t.start[k + 1] - t.start[k] > longest ? t.start[k + 1] - t.start[k] : longest;
+    return longest;
+}
+// The grid of a backward over the table: blockIdx.y = segment, 256 threads grid-striding over the longest segment in at most 512
+// blocks in x.  x = 0: every segment is empty, nothing to launch.
+inline dim3 mcn_segment_grid(const McnSegTable& t) {
+    const int gx = (mcn_longest_segment(t) + 255) / 256;
+    return dim3(gx > 512 ? 512 : gx, t.K);
+}
 struct McnRayBatchArgs {
     const float* pose;        // [C,3,4] world->cam of all cameras
     const float* kinv;        // [C,3,3]

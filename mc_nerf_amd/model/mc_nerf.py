@@ -25,7 +25,7 @@ from ..data import DeviceImageSet
 from ..lens import distort_pixels, lens_model_setting
 from .loss import color_calib_settings
 from .net_block import CorseFine_NeRF, SinCosEmbedding
-from .render import CameraFn, LensRayBatchFn, RayBatchFn, RaygenFn, Rays, RenderCall, RenderSettings, RenderTrainFn, SamplePass, _pool, render_test, run_pass
+from .render import CameraFn, RayBatchFn, RaygenFn, Rays, RenderCall, RenderSettings, RenderTrainFn, SamplePass, _pool, render_test, run_pass
 
 
 def _rank():
@@ -37,6 +37,15 @@ def _int_key(sys_param, key, default, lo, hi=None, text=None):
     v = sys_param.get(key, default)
     if isinstance(v, bool) or not isinstance(v, int) or v < lo or (hi is not None and v > hi):
         raise ValueError(f"{key} must be an integer {text or (f'>= {lo}' if hi is None else f'in [{lo}, {hi}]')}, got {v!r}")
+    return v
+
+
+def _number_key(sys_param, key, default, finite):
+    """sys_param[key] (`default` without one) when it is an int or a float, not a bool and not NaN, and with `finite` not an
+    infinity; else a ValueError that names the key."""
+    v = sys_param.get(key, default)
+    if isinstance(v, bool) or not isinstance(v, (int, float)) or v != v or (finite and v in (float("inf"), float("-inf"))):
+        raise ValueError(f"{key} must be a {'finite ' if finite else ''}number, got {v!r}")
     return v
 
 
@@ -122,11 +131,7 @@ class NeRF_Model(nn.Module):
     # ------------------------------------------------------------------ voxel sigma cache (:859-867)
     def _voxel_settings(self, sys_param):
         """Reads and validates the keys of "voxel" mode (a ValueError names the key) -> the RenderSettings fields."""
-        def number(key, default):
-            v = sys_param.get(key, default)
-            if isinstance(v, bool) or not isinstance(v, (int, float)) or v != v or v in (float("inf"), float("-inf")):
-                raise ValueError(f"{key} must be a finite number, got {v!r}")
-            return v
+        number = lambda key, default: _number_key(sys_param, key, default, finite=True)
         G = _int_key(sys_param, "grid_nerf", None, 2, 1024)
         bmin, bmax = number("boader_min", None), number("boader_max", None)
         if not bmin < bmax:
@@ -502,7 +507,7 @@ class MC_Model(nn.Module):
             raise ValueError(f"pixel_sampler must be 'uniform' or 'error', got {self.pixel_sampler!r}")
         # "lens_model" is this build's own key as well: "pinhole" (the default: today's path, no parameter) or "radial" --
         # one more parameter weights_lens [C,2] = (k1, k2) per training camera, OpenCV's two-coefficient radial model, undistorted inside
-        # the NeRF stages' ray kernel (LensRayBatchFn) and applied in closed form to the calibration-tag reprojection
+        # the NeRF stages' ray kernel (RayBatchFn with its lens input) and applied in closed form to the calibration-tag reprojection
         self.lens_model = lens_model_setting(sys_param)
         self._error_map = None            # ops.ErrorMap, allocated on first use ("error" mode only): not a parameter, not a buffer
         if self.pixel_sampler == "error":
@@ -544,11 +549,7 @@ class MC_Model(nn.Module):
     @staticmethod
     def _error_settings(sys_param):
         """Reads and validates the keys of "error" mode (a ValueError names the key) -> (error_tile, error_beta, error_uniform_frac)."""
-        def number(key, default):
-            v = sys_param.get(key, default)
-            if isinstance(v, bool) or not isinstance(v, (int, float)) or v != v:
-                raise ValueError(f"{key} must be a number, got {v!r}")
-            return float(v)
+        number = lambda key, default: float(_number_key(sys_param, key, default, finite=False))
         tile = _int_key(sys_param, "error_tile", 16, 1, 256)
         beta = number("error_beta", 0.5)
         if not 0.0 < beta <= 1.0:
@@ -653,41 +654,18 @@ class MC_Model(nn.Module):
             t if isinstance(t, DeviceImageSet) or i == 1 else t.to(self.device) for i, t in enumerate(data)]
         loss_dict = {}
         emb = self.nerf.emmbedding_xyz
-        if self.cams_per_step > 1 and epoch_type != "CAM_PARAM_EPOCH":
-            self._forward_train_multi(data, images, gt_rgbs, intr_wpts, intr_pts, epoch, epoch_type, cur_ratio, loss_dict)
-        elif epoch_type == "CAM_PARAM_EPOCH":
+        if epoch_type == "CAM_PARAM_EPOCH":         # (always one camera, whatever cams_per_step)
             emb.barf_mode = False
             self.intr_adj, self.pose_adj, self.calib_pose_adj = self.add_weights2param(True, True, True, intr_wpts, extr_wpts)
             loss_dict["intr"] = [self._reproject(intr_wpts, self.intr_adj, self.calib_pose_adj, 0), intr_pts]
             loss_dict["extr"] = [self._reproject(extr_wpts, self.intr_adj, self.pose_adj, 1), extr_pts]
             self.opt_idx = 0
         else:
-            joint = epoch_type == "GLOBAL_OPTIM_EPOCH"
-            emb.barf_mode = joint                                   # :74 / :86
-            self.intr_adj, self.pose_adj, self.calib_pose_adj = self.add_weights2param(True, joint, True, intr_wpts, None)
-            loss_dict["intr"] = [self._reproject(intr_wpts, self.intr_adj, self.calib_pose_adj, 0), intr_pts]
-            kinv = self.intr_inv_adj[cam] if self.intr_inv_adj is not None else \
-                self.inverse_intrinsic(self.intr_adj[cam:cam + 1])[0]
-            # pixel subset first (same device randperm as :329), rays only for those pixels
-            error = self.pixel_sampler == "error"        # (with replacement: always `batch` rays)
-            rand_idx = self._draw_error_pixels([cam], [0, self.batch]) if error else self.sample_pixels(self.img_h * self.img_w)
-            if self.lens_model == "radial":              # the fused kernel on a one-segment table; the draw above is its pix_in
-                kinv_all = self.intr_inv_adj if self.intr_inv_adj is not None else self.inverse_intrinsic(self.intr_adj)
-                _, rays_d, rays_o, gt = LensRayBatchFn.apply(self.pose_adj, kinv_all, self.weights_lens, [cam], [0, int(rand_idx.shape[0])],
-                                                             self.img_h, self.img_w, images.images if images is not None else None, rand_idx)
-            else:
-                rays_d, rays_o = RaygenFn.apply(self.pose_adj[cam], kinv, rand_idx, self.img_w)
-                gt = None
-            rgbs_c, rgbs_f = self.nerf(rays_d, rays_o, epoch, cur_ratio if joint else 1)
-            if gt is None:
-                gt = images.gather(cam, rand_idx) if images is not None else gt_rgbs.reshape(-1, 3)[rand_idx]
-            loss_dict["rgb"] = [rgbs_c, rgbs_f, gt]
-            if self.color_calib == "affine":
-                loss_dict["color"] = [self.weights_color, [cam], [0, int(rgbs_c.shape[0])]]
-            if error:
-                self.last_step_segments, self.last_step_pix = ([cam], [0, self.batch]), rand_idx
-                self._update_error_map([cam], [0, self.batch], rand_idx, rgbs_f, gt)
-            self.opt_idx = 1 if joint else 2
+            K = self.cams_per_step
+            cams = [cam] if K == 1 else [int(c) for c in data[1].reshape(-1).tolist()]
+            if len(cams) != K:
+                raise ValueError(f"cams_per_step = {K}: data[1] must hold exactly {K} camera ids, got {len(cams)}")
+            self._forward_train_nerf(cams, images, gt_rgbs, intr_wpts, intr_pts, epoch, epoch_type, cur_ratio, loss_dict)
         # validation rays of the same index, every step, as the reference (:97-99)
         with torch.no_grad():
             rays_dv, rays_ov = self.get_rays(self.valid_pose, cam, self.intr_val_inv)
@@ -697,34 +675,45 @@ class MC_Model(nn.Module):
         self.last_epoch_type = epoch_type
         return loss_dict, intr_show, pose_show, rays_valid
 
-    def _forward_train_multi(self, data, images, gt_rgbs, intr_wpts, intr_pts, epoch, epoch_type, cur_ratio, loss_dict):
-        """The NeRF-stage step of `cams_per_step` = K > 1: `data[1]` holds K camera ids (duplicates allowed); the batch is K segments
-        of consecutive rays (`ops.ray_segments`), segment k of camera k, and pixels, rays and ground truth of all of them come from
-        ONE launch (RayBatchFn) that reads `pose_adj [C,3,4]` / `intr_inv_adj [C,3,3]` of all cameras as CameraFn left them.  The
-        renderer and the loss see an ordinary [batch] ray set."""
-        K = self.cams_per_step
-        cams = [int(c) for c in data[1].reshape(-1).tolist()]
-        if len(cams) != K:
-            raise ValueError(f"cams_per_step = {K}: data[1] must hold exactly {K} camera ids, got {len(cams)}")
+    def _forward_train_nerf(self, cams, images, gt_rgbs, intr_wpts, intr_pts, epoch, epoch_type, cur_ratio, loss_dict):
+        """The NeRF-stage step over K = len(cams) cameras (duplicates allowed): the batch is K segments of consecutive rays
+        (`ops.ray_segments`), segment k of camera cams[k]; the renderer and the loss see an ordinary [batch] ray set.  K = 1 is the
+        one-segment table.  Where the rays come from is all that differs:
+          K = 1, pinhole: the pixels of `sample_pixels` (or the error draw), RaygenFn on that camera's matrices, the ground truth
+                  gathered afterwards (the default step: a launch each);
+          otherwise: ONE launch (RayBatchFn: pixels, rays, ground truth) that reads `pose_adj [C,3,4]` / `intr_inv_adj [C,3,3]` (and
+                  `weights_lens [C,2]`) of all cameras as CameraFn left them.  K = 1 injects the same draw as above; K > 1 injects the
+                  `sample_pixels_multi` hook's ids, else the error draw, else every segment draws in the kernel."""
+        K, npix = len(cams), self.img_h * self.img_w
         if intr_wpts.shape[0] == K:        # a loader that batches K items stacks the (identical) calibration tensors K times
             intr_wpts, intr_pts = intr_wpts[:1], intr_pts[:1]
         joint = epoch_type == "GLOBAL_OPTIM_EPOCH"
-        self.nerf.emmbedding_xyz.barf_mode = joint
+        self.nerf.emmbedding_xyz.barf_mode = joint                  # :74 / :86
         self.intr_adj, self.pose_adj, self.calib_pose_adj = self.add_weights2param(True, joint, True, intr_wpts, None)
         loss_dict["intr"] = [self._reproject(intr_wpts, self.intr_adj, self.calib_pose_adj, 0), intr_pts]
-        kinv_all = self.intr_inv_adj if self.intr_inv_adj is not None else self.inverse_intrinsic(self.intr_adj)
+        error, radial = self.pixel_sampler == "error", self.lens_model == "radial"
         seg_start = ops.ray_segments(self.batch, K)
-        pix_in = self.sample_pixels_multi(self.img_h * self.img_w, seg_start)
-        if pix_in is None and self.pixel_sampler == "error":      # (an injected draw still wins)
-            pix_in = self._draw_error_pixels(cams, seg_start)
-        if self.lens_model == "radial":
-            pix, rays_d, rays_o, gt = LensRayBatchFn.apply(self.pose_adj, kinv_all, self.weights_lens, cams, seg_start, self.img_h, self.img_w,
-                                                           images.images if images is not None else None, pix_in)
+        if K == 1:      # pixel subset first (same device randperm as :329), rays only for those pixels
+            pix = self._draw_error_pixels(cams, seg_start) if error else self.sample_pixels(npix)
+            seg_start = [0, int(pix.shape[0])]                      # (`sample_pixels` returns min(batch, npix) ids)
         else:
+            pix = self.sample_pixels_multi(npix, seg_start)
+            if pix is None and error:                               # (an injected draw still wins)
+                pix = self._draw_error_pixels(cams, seg_start)
+        if K == 1 and not radial:
+            cam = cams[0]
+            kinv = self.intr_inv_adj[cam] if self.intr_inv_adj is not None else self.inverse_intrinsic(self.intr_adj[cam:cam + 1])[0]
+            rays_d, rays_o = RaygenFn.apply(self.pose_adj[cam], kinv, pix, self.img_w)
+            gt = None
+        else:
+            kinv_all = self.intr_inv_adj if self.intr_inv_adj is not None else self.inverse_intrinsic(self.intr_adj)
             pix, rays_d, rays_o, gt = RayBatchFn.apply(self.pose_adj, kinv_all, cams, seg_start, self.img_h, self.img_w,
-                                                       images.images if images is not None else None, pix_in)
+                                                       images.images if images is not None else None, pix, None,
+                                                       self.weights_lens if radial else None)
         rgbs_c, rgbs_f = self.nerf(rays_d, rays_o, epoch, cur_ratio if joint else 1)
-        if gt is None:                     # host float stack [K,H,W,3] / [K,H*W,3]: item k is the image of segment k
+        if gt is None and K == 1:
+            gt = images.gather(cams[0], pix) if images is not None else gt_rgbs.reshape(-1, 3)[pix]
+        elif gt is None:                   # host float stack [K,H,W,3] / [K,H*W,3]: item k is the image of segment k
             if self._seg_index is None:
                 self._seg_index = ops.ray_segment_index(self.batch, K, pix.device)
             gt = gt_rgbs.reshape(K, -1, 3)[self._seg_index, pix]
@@ -732,8 +721,9 @@ class MC_Model(nn.Module):
         if self.color_calib == "affine":
             loss_dict["color"] = [self.weights_color, cams, seg_start]
         self.opt_idx = 1 if joint else 2
-        self.last_step_segments, self.last_step_pix = (cams, seg_start), pix
-        if self.pixel_sampler == "error":
+        if K > 1 or error:
+            self.last_step_segments, self.last_step_pix = (cams, seg_start), pix
+        if error:
             self._update_error_map(cams, seg_start, pix, rgbs_f, gt)
 
     def sample_pixels_multi(self, npix, seg_start):

@@ -6,7 +6,8 @@ optional (ray, sample) list over a prefilled output, the saved-operand set of a 
 ops.composite_fwd), ``pass_backward`` differentiates it (composite bwd -> dX chain -> dW).  ``coarse_pass`` and ``fine_pass`` build the
 two passes of a render; ``RenderTrainFn`` (ONE differentiable op for NeRF_Model.render_rays_train, with that hand-written backward
 instead of autograd through ~900 ATen ops), ``render_test`` and NeRF_Model._inference run what they return.  ``RaygenFn`` is the
-same kind of op for MC_Model.get_rays on selected pixels.
+same kind of op for MC_Model.get_rays on selected pixels of one camera, ``RayBatchFn`` for a batch that spans cameras and for the
+radial lens model (its ``lens`` input; None = pinhole), ``CameraFn`` for the camera parametrisation.
 
 What a sampler setting changes in its pass:
   fine_sampler "threshold" (the reference): the list ops.select_fine compacts from the coarse selection weights, over the
@@ -384,52 +385,37 @@ class RaygenFn(torch.autograd.Function):
 
 
 class RayBatchFn(torch.autograd.Function):
-    """pix, rays_d, rays_o, gt = f(pose[C,3,4], kinv[C,3,3]) for a batch of K segments of consecutive rays, segment k of camera
-    seg_cam[k] (`cams_per_step` > 1: ops.ray_batch_fwd, one launch).  Differentiable wrt pose and kinv; `pix` (injected, or drawn on
-    the device when None) and `gt` (from `images` [C, H*W, 3|4] uint8, None without) are non-differentiable outputs."""
+    """pix, rays_d, rays_o, gt = f(pose[C,3,4], kinv[C,3,3]; lens[C,2] | None) for a batch of K segments of consecutive rays, segment k
+    of camera seg_cam[k], in one launch: ops.ray_batch_fwd (`cams_per_step` > 1), or with `lens` ops.lens_ray_batch_fwd, the same with
+    per-camera radial lens distortion (`lens_model` = "radial", any K).  Differentiable wrt pose, kinv and lens; `pix` (injected, or
+    drawn on the device when None) and `gt` (from `images` [C, H*W, 3|4] uint8, None without) are non-differentiable outputs.
+    `lens` is the last input: without it the argument list is the pinhole op's."""
 
     @staticmethod
-    def forward(ctx, pose, kinv, seg_cam, seg_start, H, W, images=None, pix=None, seed=None):
+    def forward(ctx, pose, kinv, seg_cam, seg_start, H, W, images=None, pix=None, seed=None, lens=None):
         pose = pose.contiguous().float()
         kinv = kinv.contiguous().float()
-        pix, d, o, gt = ops.ray_batch_fwd(pose, kinv, seg_cam, seg_start, H, W, images=images,
-                                          pix=None if pix is None else pix.contiguous(), seed=seed)
-        ctx.save_for_backward(pose, kinv, pix)
+        kw = dict(images=images, pix=None if pix is None else pix.contiguous(), seed=seed)
+        if lens is None:
+            pix, d, o, gt = ops.ray_batch_fwd(pose, kinv, seg_cam, seg_start, H, W, **kw)
+            ctx.save_for_backward(pose, kinv, pix)
+        else:
+            lens = lens.contiguous().float()
+            pix, d, o, gt = ops.lens_ray_batch_fwd(pose, kinv, lens, seg_cam, seg_start, H, W, **kw)
+            ctx.save_for_backward(pose, kinv, pix, lens)
         ctx.table = (list(seg_cam), list(seg_start), W)
         ctx.mark_non_differentiable(*(t for t in (pix, gt) if t is not None))
         return pix, d, o, gt
 
     @staticmethod
     def backward(ctx, _g_pix, g_d, g_o, _g_gt):
-        pose, kinv, pix = ctx.saved_tensors
+        pose, kinv, pix, *lens = ctx.saved_tensors
         seg_cam, seg_start, W = ctx.table
-        d_pose, d_kinv = ops.ray_batch_bwd(pose, kinv, seg_cam, seg_start, W, pix, g_d.contiguous(), g_o.contiguous())
-        return d_pose, d_kinv, None, None, None, None, None, None, None
-
-
-class LensRayBatchFn(torch.autograd.Function):
-    """RayBatchFn with per-camera radial lens distortion (`lens_model` = "radial": ops.lens_ray_batch_fwd, one launch):
-    pix, rays_d, rays_o, gt = f(pose[C,3,4], kinv[C,3,3], lens[C,2]).  Differentiable wrt pose, kinv and lens; `pix` and `gt` are
-    non-differentiable outputs."""
-
-    @staticmethod
-    def forward(ctx, pose, kinv, lens, seg_cam, seg_start, H, W, images=None, pix=None, seed=None):
-        pose = pose.contiguous().float()
-        kinv = kinv.contiguous().float()
-        lens = lens.contiguous().float()
-        pix, d, o, gt = ops.lens_ray_batch_fwd(pose, kinv, lens, seg_cam, seg_start, H, W, images=images,
-                                               pix=None if pix is None else pix.contiguous(), seed=seed)
-        ctx.save_for_backward(pose, kinv, lens, pix)
-        ctx.table = (list(seg_cam), list(seg_start), W)
-        ctx.mark_non_differentiable(*(t for t in (pix, gt) if t is not None))
-        return pix, d, o, gt
-
-    @staticmethod
-    def backward(ctx, _g_pix, g_d, g_o, _g_gt):
-        pose, kinv, lens, pix = ctx.saved_tensors
-        seg_cam, seg_start, W = ctx.table
-        d_pose, d_kinv, d_lens = ops.lens_ray_batch_bwd(pose, kinv, lens, seg_cam, seg_start, W, pix, g_d.contiguous(), g_o.contiguous())
-        return d_pose, d_kinv, d_lens, None, None, None, None, None, None, None
+        if lens:
+            d_pose, d_kinv, d_lens = ops.lens_ray_batch_bwd(pose, kinv, lens[0], seg_cam, seg_start, W, pix, g_d.contiguous(), g_o.contiguous())
+        else:
+            d_pose, d_kinv, d_lens = (*ops.ray_batch_bwd(pose, kinv, seg_cam, seg_start, W, pix, g_d.contiguous(), g_o.contiguous()), None)
+        return d_pose, d_kinv, None, None, None, None, None, None, None, d_lens
 
 
 class CameraFn(torch.autograd.Function):

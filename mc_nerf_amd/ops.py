@@ -345,44 +345,6 @@ def _seg_arrays(seg_cam, seg_start):
     return (ctypes.c_int32 * len(cams))(*cams), (ctypes.c_int32 * len(start))(*start), len(cams), start[-1]
 
 
-def ray_batch_fwd(pose: Tensor, kinv: Tensor, seg_cam, seg_start, H: int, W: int, images: Optional[Tensor] = None,
-                  pix: Optional[Tensor] = None, seed: Optional[Tensor] = None):
-    """The ray preamble of a multi-camera step in one launch.  pose [C,3,4], kinv [C,3,3]; segment k = rays
-    [seg_start[k], seg_start[k+1]) of camera seg_cam[k] (host lists; they travel as kernel arguments).  `pix` [n] int64 injects the
-    pixels; otherwise segment k draws the permutation of `sample_perm` keyed by seed + k * 0x9E3779B9 (`seed`: a device int32 word,
-    drawn from torch's device generator when not given, as `sample_perm` does).  `images` [C, H*W, 3|4] uint8 on the device gives the
-    ground truth.  -> (pix [n] int64, rays_d [n,3], rays_o [n,3], gt [n,3] | None)"""
-    cams, start, K, n = _seg_arrays(seg_cam, seg_start)
-    dev = pose.device
-    if pix is None and seed is None and pose.is_cuda:
-        seed = torch.randint(0, 2 ** 31 - 1, (1,), dtype=torch.int32, device=dev)
-    if pix is not None and pix.numel() != n:
-        raise _lib.McnerfError(f"pix must hold seg_start[-1] = {n} ids, got {pix.numel()}")
-    if images is not None and (images.dim() != 3 or images.shape[0] != pose.shape[0] or images.shape[1] != H * W):
-        raise _lib.McnerfError(f"images must be [C = {pose.shape[0]}, H*W = {H * W}, channels], got {tuple(images.shape)}")
-    pix_out = torch.empty(n, dtype=torch.int64, device=dev)
-    d = torch.empty(n, 3, dtype=torch.float32, device=dev)
-    o = torch.empty_like(d)
-    gt = torch.empty_like(d) if images is not None else None
-    _lib.call("mcnerf_ray_batch_fwd", _p(pose), _p(kinv), int(pose.shape[0]), cams, start, K, n, int(H), int(W),
-              _p(pix, torch.int64), _p(seed, torch.int32), _p(images, torch.uint8), int(images.shape[-1]) if images is not None else 0,
-              _p(pix_out, torch.int64), _p(d), _p(o), _p(gt), _stream())
-    return pix_out, d, o, gt
-
-
-def ray_batch_bwd(pose: Tensor, kinv: Tensor, seg_cam, seg_start, W: int, pix: Tensor, d_d: Tensor, d_o: Tensor) -> Tuple[Tensor, Tensor]:
-    """Backward of `ray_batch_fwd`: -> (d_pose [C,3,4], d_kinv [C,3,3]); rows of cameras not in the table are exactly zero."""
-    cams, start, K, n = _seg_arrays(seg_cam, seg_start)
-    C = int(pose.shape[0])
-    z = torch.zeros(C * 21, dtype=torch.float32, device=pose.device)     # (one fill for both accumulation targets)
-    d_pose, d_kinv = z[:C * 12].view(C, 3, 4), z[C * 12:].view(C, 3, 3)
-    if pix.numel() != n or d_d.numel() != 3 * n or d_o.numel() != 3 * n:
-        raise _lib.McnerfError(f"pix / d_rays_d / d_rays_o must hold seg_start[-1] = {n} rays")
-    _lib.call("mcnerf_ray_batch_bwd", _p(pose), _p(kinv), C, cams, start, K, n, int(W), _p(pix, torch.int64),
-              _p(d_d), _p(d_o), _p(d_pose), _p(d_kinv), _stream())
-    return d_pose, d_kinv
-
-
 def _lens_arg(lens: Tensor, C: int) -> Tensor:
     if not lens.is_cuda:
         raise _lib.McnerfError("the lens ray-batch ops need CUDA/HIP tensors (no CPU fallback)")
@@ -391,16 +353,13 @@ def _lens_arg(lens: Tensor, C: int) -> Tensor:
     return lens
 
 
-def lens_ray_batch_fwd(pose: Tensor, kinv: Tensor, lens: Tensor, seg_cam, seg_start, H: int, W: int, images: Optional[Tensor] = None,
-                       pix: Optional[Tensor] = None, seed: Optional[Tensor] = None):
-    """`ray_batch_fwd` with per-camera radial lens distortion (`lens_model` = "radial", DESIGN.md 4f): lens [C,2] = (k1, k2); every
-    ray's lifted pixel is undistorted by eight safeguarded Newton steps before the rotation (csrc/mcnerf_lens.h).  Pixels (the same
-    draw from the same seed word) and ground truth as `ray_batch_fwd`; at lens = 0 every output has its bits.
-    -> (pix [n] int64, rays_d [n,3], rays_o [n,3], gt [n,3] | None)"""
+def _ray_batch_fwd(symbol: str, pose: Tensor, kinv: Tensor, lens: Optional[Tensor], seg_cam, seg_start, H: int, W: int,
+                   images: Optional[Tensor], pix: Optional[Tensor], seed: Optional[Tensor], draw_seed: bool):
+    """Both forwards: `symbol` with `lens` [C,2] behind kinv, or without it (None).  draw_seed: the key word is still to be drawn."""
     cams, start, K, n = _seg_arrays(seg_cam, seg_start)
     dev = pose.device
-    lens = _lens_arg(lens, int(pose.shape[0]))
-    if pix is None and seed is None:
+    lens_args = () if lens is None else (_p(_lens_arg(lens, int(pose.shape[0]))),)
+    if draw_seed:
         seed = torch.randint(0, 2 ** 31 - 1, (1,), dtype=torch.int32, device=dev)
     if pix is not None and pix.numel() != n:
         raise _lib.McnerfError(f"pix must hold seg_start[-1] = {n} ids, got {pix.numel()}")
@@ -410,26 +369,58 @@ def lens_ray_batch_fwd(pose: Tensor, kinv: Tensor, lens: Tensor, seg_cam, seg_st
     d = torch.empty(n, 3, dtype=torch.float32, device=dev)
     o = torch.empty_like(d)
     gt = torch.empty_like(d) if images is not None else None
-    _lib.call("mcnerf_lens_ray_batch_fwd", _p(pose), _p(kinv), _p(lens), int(pose.shape[0]), cams, start, K, n, int(H), int(W),
+    _lib.call(symbol, _p(pose), _p(kinv), *lens_args, int(pose.shape[0]), cams, start, K, n, int(H), int(W),
               _p(pix, torch.int64), _p(seed, torch.int32), _p(images, torch.uint8), int(images.shape[-1]) if images is not None else 0,
               _p(pix_out, torch.int64), _p(d), _p(o), _p(gt), _stream())
     return pix_out, d, o, gt
+
+
+def _ray_batch_bwd(symbol: str, pose: Tensor, kinv: Tensor, lens: Optional[Tensor], seg_cam, seg_start, W: int, pix: Tensor, d_d: Tensor,
+                   d_o: Tensor):
+    """Both backwards -> (d_pose [C,3,4], d_kinv [C,3,3]) and, with `lens`, d_lens [C,2]: views of one zero-filled buffer."""
+    cams, start, K, n = _seg_arrays(seg_cam, seg_start)
+    C = int(pose.shape[0])
+    lens_args = () if lens is None else (_p(_lens_arg(lens, C)),)
+    z = torch.zeros(C * (21 if lens is None else 23), dtype=torch.float32, device=pose.device)     # (one fill for every accumulation target)
+    outs = (z[:C * 12].view(C, 3, 4), z[C * 12:C * 21].view(C, 3, 3)) + (() if lens is None else (z[C * 21:].view(C, 2),))
+    if pix.numel() != n or d_d.numel() != 3 * n or d_o.numel() != 3 * n:
+        raise _lib.McnerfError(f"pix / d_rays_d / d_rays_o must hold seg_start[-1] = {n} rays")
+    _lib.call(symbol, _p(pose), _p(kinv), *lens_args, C, cams, start, K, n, int(W), _p(pix, torch.int64),
+              _p(d_d), _p(d_o), *(_p(g) for g in outs), _stream())
+    return outs
+
+
+def ray_batch_fwd(pose: Tensor, kinv: Tensor, seg_cam, seg_start, H: int, W: int, images: Optional[Tensor] = None,
+                  pix: Optional[Tensor] = None, seed: Optional[Tensor] = None):
+    """The ray preamble of a multi-camera step in one launch.  pose [C,3,4], kinv [C,3,3]; segment k = rays
+    [seg_start[k], seg_start[k+1]) of camera seg_cam[k] (host lists; they travel as kernel arguments).  `pix` [n] int64 injects the
+    pixels; otherwise segment k draws the permutation of `sample_perm` keyed by seed + k * 0x9E3779B9 (`seed`: a device int32 word,
+    drawn from torch's device generator when not given, as `sample_perm` does).  `images` [C, H*W, 3|4] uint8 on the device gives the
+    ground truth.  -> (pix [n] int64, rays_d [n,3], rays_o [n,3], gt [n,3] | None)"""
+    return _ray_batch_fwd("mcnerf_ray_batch_fwd", pose, kinv, None, seg_cam, seg_start, H, W, images, pix, seed,
+                          draw_seed=pix is None and seed is None and pose.is_cuda)
+
+
+def ray_batch_bwd(pose: Tensor, kinv: Tensor, seg_cam, seg_start, W: int, pix: Tensor, d_d: Tensor, d_o: Tensor) -> Tuple[Tensor, Tensor]:
+    """Backward of `ray_batch_fwd`: -> (d_pose [C,3,4], d_kinv [C,3,3]); rows of cameras not in the table are exactly zero."""
+    return _ray_batch_bwd("mcnerf_ray_batch_bwd", pose, kinv, None, seg_cam, seg_start, W, pix, d_d, d_o)
+
+
+def lens_ray_batch_fwd(pose: Tensor, kinv: Tensor, lens: Tensor, seg_cam, seg_start, H: int, W: int, images: Optional[Tensor] = None,
+                       pix: Optional[Tensor] = None, seed: Optional[Tensor] = None):
+    """`ray_batch_fwd` with per-camera radial lens distortion (`lens_model` = "radial", DESIGN.md 4f): lens [C,2] = (k1, k2); every
+    ray's lifted pixel is undistorted by eight safeguarded Newton steps before the rotation (csrc/mcnerf_lens.h).  Pixels (the same
+    draw from the same seed word) and ground truth as `ray_batch_fwd`; at lens = 0 every output has its bits.  CUDA/HIP tensors only.
+    -> (pix [n] int64, rays_d [n,3], rays_o [n,3], gt [n,3] | None)"""
+    return _ray_batch_fwd("mcnerf_lens_ray_batch_fwd", pose, kinv, lens, seg_cam, seg_start, H, W, images, pix, seed,
+                          draw_seed=pix is None and seed is None)
 
 
 def lens_ray_batch_bwd(pose: Tensor, kinv: Tensor, lens: Tensor, seg_cam, seg_start, W: int, pix: Tensor, d_d: Tensor,
                        d_o: Tensor) -> Tuple[Tensor, Tensor, Tensor]:
     """Backward of `lens_ray_batch_fwd`: -> (d_pose [C,3,4], d_kinv [C,3,3], d_lens [C,2]); rows of cameras not in the table are
     exactly zero, a camera listed twice receives the sum."""
-    cams, start, K, n = _seg_arrays(seg_cam, seg_start)
-    C = int(pose.shape[0])
-    lens = _lens_arg(lens, C)
-    z = torch.zeros(C * 23, dtype=torch.float32, device=pose.device)     # (one fill for the three accumulation targets)
-    d_pose, d_kinv, d_lens = z[:C * 12].view(C, 3, 4), z[C * 12:C * 21].view(C, 3, 3), z[C * 21:].view(C, 2)
-    if pix.numel() != n or d_d.numel() != 3 * n or d_o.numel() != 3 * n:
-        raise _lib.McnerfError(f"pix / d_rays_d / d_rays_o must hold seg_start[-1] = {n} rays")
-    _lib.call("mcnerf_lens_ray_batch_bwd", _p(pose), _p(kinv), _p(lens), C, cams, start, K, n, int(W), _p(pix, torch.int64),
-              _p(d_d), _p(d_o), _p(d_pose), _p(d_kinv), _p(d_lens), _stream())
-    return d_pose, d_kinv, d_lens
+    return _ray_batch_bwd("mcnerf_lens_ray_batch_bwd", pose, kinv, lens, seg_cam, seg_start, W, pix, d_d, d_o)
 
 
 def upload_f32(host_vals: Tensor, device) -> Tensor:

@@ -8,7 +8,7 @@ The radiance-field loop is tests/test_y_convergence_gpu._field_run, imported and
 four configurations:
   A  clean rig, pinhole rays (`_field_run` itself);
   B  the training images rendered through synthetic.lens_distortion (k1 spread 0.05, k2 spread 0.005), pinhole rays;
-  C  the images of B, the rays through LensRayBatchFn with a zero [C,2] parameter of its own in the optimiser, in a GROUP OF ITS OWN
+  C  the images of B, the rays through RayBatchFn with a zero [C,2] parameter of its own in the optimiser, in a GROUP OF ITS OWN
      (lr, betas below: the parameter is row-sparse, as weights_color is -- only the step's camera has a gradient);
   D  as C with the parameter in the loop's single default group (its lr 2e-3, betas (0.9, 0.999)), for comparison.
 The held-out PSNR is what the loop returns: the pinhole render of the held-out cameras (they have no lens parameter) against their
@@ -45,13 +45,13 @@ def rig():
 
 def field_run_with(dev, lens_true=None, learn=False, own_group=True, seed=0, steps=STEPS, lr_lens=LR_LENS, betas_lens=BETAS_LENS):
     """`_field_run(dev, PRECISION, steps, seed)` with the TRAINING cameras' images rendered through `lens_true` [C,2] (the held-out
-    ones stay clean) and, with `learn`, the training rays through LensRayBatchFn on a zero [C,2] parameter that joins the loop's
+    ones stay clean) and, with `learn`, the training rays through RayBatchFn on a zero [C,2] parameter that joins the loop's
     optimiser (`own_group`: as a second group with `lr_lens`, `betas_lens`; otherwise inside the loop's one group).  The loop's camera
     of every step is its own host-side draw, repeated here.  -> (held-out PSNR against the clean images, the parameter | None)."""
     import test_y_convergence_gpu as Y
     import mc_nerf_amd.model as M
     from mc_nerf_amd import ops, synthetic as S
-    from mc_nerf_amd.model.render import LensRayBatchFn
+    from mc_nerf_amd.model.render import RayBatchFn
     pose, K, train_ids, test_ids = rig()
     C, H, W = pose.shape[0], Y.H, Y.W
     order = torch.randint(len(train_ids), (steps,), generator=torch.Generator().manual_seed(seed)).tolist()
@@ -72,7 +72,7 @@ def field_run_with(dev, lens_true=None, learn=False, own_group=True, seed=0, ste
             return plain_raygen(pose_i, kinv_i, pix, W_)
         cam = train_ids[order[state["step"]]]
         state["step"] += 1
-        _, d, o, _ = LensRayBatchFn.apply(pose_d, kinv_d, state["w"], [cam], [0, int(pix.shape[0])], H, W, None, pix)
+        _, d, o, _ = RayBatchFn.apply(pose_d, kinv_d, [cam], [0, int(pix.shape[0])], H, W, None, pix, None, state["w"])
         return d, o
 
     class RAdamWithLens(M.RAdam):

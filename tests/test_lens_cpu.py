@@ -161,7 +161,7 @@ def test_entry_points_refuse_bad_scalars_without_a_gpu():
 def test_ops_refuse_cpu_tensors():
     from mc_nerf_amd import ops
     from mc_nerf_amd._lib import McnerfError
-    from mc_nerf_amd.model.render import LensRayBatchFn
+    from mc_nerf_amd.model.render import RayBatchFn
     s = R.make_case("b3")
     a = (s["pose"], s["kinv"], s["lens"], s["cams"], s["seg"])
     with pytest.raises(McnerfError):
@@ -169,7 +169,7 @@ def test_ops_refuse_cpu_tensors():
     with pytest.raises(McnerfError):
         ops.lens_ray_batch_bwd(*a, s["W"], s["pix"], s["g_d"], s["g_o"])
     with pytest.raises(McnerfError):
-        LensRayBatchFn.apply(*a, s["H"], s["W"], None, s["pix"])
+        RayBatchFn.apply(s["pose"], s["kinv"], s["cams"], s["seg"], s["H"], s["W"], None, s["pix"], None, s["lens"])
     with pytest.raises(McnerfError):
         ops.lens_ray_batch_fwd(s["pose"], s["kinv"], s["lens"], s["cams"], s["seg"][:-1], s["H"], s["W"], pix=s["pix"])     # K + 1 entries
 

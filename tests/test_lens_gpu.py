@@ -197,10 +197,10 @@ def test_backward_at_zero_lens_is_the_pinhole_backward(scenes, case):
 # ------------------------------------------------------------------------------------------------------------------ 5 autograd
 def test_lens_ray_batch_fn_is_differentiable_in_pose_kinv_and_lens(scenes):
     from mc_nerf_amd import ops
-    from mc_nerf_amd.model.render import LensRayBatchFn
+    from mc_nerf_amd.model.render import RayBatchFn
     _, s = scenes["a3"]
     pose, kinv, lens = (s[k].clone().requires_grad_(True) for k in ("pose", "kinv", "lens"))
-    pix, d, o, gt = LensRayBatchFn.apply(pose, kinv, lens, s["cams"], s["seg"], s["H"], s["W"], s["images"], s["pix"])
+    pix, d, o, gt = RayBatchFn.apply(pose, kinv, s["cams"], s["seg"], s["H"], s["W"], s["images"], s["pix"], None, lens)
     assert d.requires_grad and o.requires_grad and not pix.requires_grad and not gt.requires_grad
     ((d * s["g_d"]).sum() + (o * s["g_o"]).sum()).backward()
     dp, dk, dl = ops.lens_ray_batch_bwd(s["pose"], s["kinv"], s["lens"], s["cams"], s["seg"], s["W"], s["pix"], s["g_d"], s["g_o"])
@@ -212,14 +212,14 @@ def test_lens_ray_batch_fn_is_differentiable_in_pose_kinv_and_lens(scenes):
 # ------------------------------------------------------------------------------------------------------------------ 6 recovery
 def test_lens_is_recovered_from_rays_without_a_field(scenes, gpu_device):
     """The fp64 rays of a distorted camera are the target; weights start at zero, pose and K stay at the truth; Adam on the mean
-    squared direction error through LensRayBatchFn.  The same loop on the restatement in fp64 sets the bar: the GPU loop must end
+    squared direction error through RayBatchFn.  The same loop on the restatement in fp64 sets the bar: the GPU loop must end
     within twice its final error plus 1e-4."""
-    from mc_nerf_amd.model.render import LensRayBatchFn
+    from mc_nerf_amd.model.render import RayBatchFn
     h, s = scenes[R.RECOVERY_CASE]
     cam = h["cams"][0]
     target = R.rays(h["pose"], h["kinv"], h["lens"], h["cams"], h["seg"], h["pix"], h["W"])[0]
     cpu = R.recovery_loop(lambda l: R.rays(h["pose"], h["kinv"], l, h["cams"], h["seg"], h["pix"], h["W"])[0], target, h["C"])
-    gpu = R.recovery_loop(lambda l: LensRayBatchFn.apply(s["pose"], s["kinv"], l, s["cams"], s["seg"], s["H"], s["W"], None, s["pix"])[1],
+    gpu = R.recovery_loop(lambda l: RayBatchFn.apply(s["pose"], s["kinv"], s["cams"], s["seg"], s["H"], s["W"], None, s["pix"], None, l)[1],
                           target.float().to(gpu_device), h["C"], dtype=torch.float32, device=gpu_device).cpu()
     k1 = float(h["lens"][cam, 0])
     e_cpu, e_gpu = abs(float(cpu[cam, 0]) - k1), abs(float(gpu[cam, 0]) - k1)

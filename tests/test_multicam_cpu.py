@@ -187,3 +187,145 @@ def test_fp64_reference_on_a_camera_checked_by_hand():
     assert torch.equal(dp[2, :, 3], -torch.ones(3, dtype=torch.float64))                # d o / d t = -R
     u8 = torch.tensor([[[255, 0, 51, 51]]], dtype=torch.uint8)
     assert torch.allclose(R.gt_from_u8(u8, 0, torch.tensor([0])), torch.tensor([[1.0, 0.8, 0.84]]))
+
+
+# ------------------------------------------------------------------------------------------------------------------ one definition
+def _csrc():
+    from mc_nerf_amd import build
+    return {f: open(os.path.join(build.CSRC, f)).read() for f in sorted(os.listdir(build.CSRC))}
+
+
+@pytest.mark.parametrize("what, text", [
+    ("the lift through the inverse intrinsics", "__fmul_rn(u, K[r * 3])"),
+    ("the pose-inverse row of mcn_ray_of_cam", "__fmul_rn(P[0 * 4 + c], P[3])"),
+    ("the rotation of mcn_ray_of_cam", "__fmul_rn(cam[0], P[0 * 4 + c])"),
+    ("the segment scan", "for (int s = 1; s < t.K; ++s)"),
+    ("the longest-segment loop", "for (int k = 0; k < t.K; ++k) longest ="),
+    ("the dKinv accumulation", "acc[9 + j * 3 + k] +="),
+])
+def test_ray_preamble_expressions_are_written_once(what, text):
+    """The pinhole and the lens path share one definition: each of these occurs in exactly one file of csrc/, once."""
+    hits = {f: s.count(text) for f, s in _csrc().items() if text in s}
+    assert len(hits) == 1 and sum(hits.values()) == 1, (what, hits)
+
+
+def test_ray_batch_entry_points_stay_in_their_files_as_thin_kernels():
+    src = _csrc()
+    for f, names in (("rays.hip", ("ray_batch_fwd_kernel", "ray_batch_bwd_kernel")), ("lens.hip", ("lens_ray_batch_fwd_kernel", "lens_ray_batch_bwd_kernel"))):
+        for name in names:
+            m = re.search(r"__global__ __launch_bounds__\(256\) void " + name + r"\(([^)]*)\) \{\n(.*?)\n\}\n", src[f], flags=re.S)
+            assert m and len(m.group(2).split("\n")) <= 3 and "_body<" in m.group(2), (f, name)
+            assert sum(("void " + name + "(") in s for s in src.values()) == 1, name
+    assert "err_segment" not in src["errmap.hip"] and "mcn_segment_of_ray(" in src["errmap.hip"] and "mcn_segment_of_ray(" in src["mcnerf_rays.h"]
+
+
+def test_ops_reach_each_ray_batch_symbol_from_one_function_body():
+    import ast
+    import inspect
+    from mc_nerf_amd import ops
+    tree = ast.parse(inspect.getsource(ops))
+    text = inspect.getsource(ops)
+    owners, calls_with_symbol = {}, []
+    for fn in [n for n in tree.body if isinstance(n, ast.FunctionDef)]:
+        for node in ast.walk(fn):
+            if isinstance(node, ast.Constant) and isinstance(node.value, str) and re.fullmatch(r"mcnerf_(lens_)?ray_batch_(fwd|bwd)", node.value):
+                owners.setdefault(node.value, []).append(fn.name)
+            if isinstance(node, ast.Call) and ast.unparse(node.func) == "_lib.call" and ast.unparse(node.args[0]) == "symbol":
+                calls_with_symbol.append(fn.name)
+    assert owners == {"mcnerf_ray_batch_fwd": ["ray_batch_fwd"], "mcnerf_ray_batch_bwd": ["ray_batch_bwd"],
+                      "mcnerf_lens_ray_batch_fwd": ["lens_ray_batch_fwd"], "mcnerf_lens_ray_batch_bwd": ["lens_ray_batch_bwd"]}
+    assert sorted(calls_with_symbol) == ["_ray_batch_bwd", "_ray_batch_fwd"]            # the two private ops are the only callers
+    assert text.count("_ray_batch_fwd(\"mcnerf_") == 2 and text.count("_ray_batch_bwd(\"mcnerf_") == 2
+
+
+# ------------------------------------------------------------------------------------------------------------------ one step
+STEP_CONFIGS = [(1, "pinhole", "uniform", 16), (1, "radial", "uniform", 16), (1, "radial", "uniform", 100), (1, "pinhole", "error", 16),
+                (1, "radial", "error", 16), (2, "pinhole", "uniform", 16), (2, "radial", "uniform", 16), (2, "pinhole", "error", 16),
+                (2, "pinhole", "hook", 16), (2, "radial", "hook+error", 16)]
+
+
+@pytest.mark.parametrize("K, lens, sampler, batch", STEP_CONFIGS)
+@pytest.mark.parametrize("stage", ["GLOBAL_OPTIM_EPOCH", "FINE_TUNE_EPOCH"])
+def test_nerf_stage_step_routes_every_configuration(monkeypatch, K, lens, sampler, batch, stage):
+    """The one NeRF-stage step on a CPU model with the HIP ops stubbed: which ray op each configuration reaches and with what
+    arguments, and what the step leaves behind (8 x 8 images: batch = 100 draws all 64 pixels)."""
+    import mc_nerf_amd.model.mc_nerf as M
+    error = "error" in sampler
+    m, sp = _model(batch=batch, cams_per_step=K, lens_model=lens, color_calib="affine", **({"pixel_sampler": "error"} if error else {}))
+    S.init_cameras_near_gt(m)
+    cams = [3, 1][:K]
+    calls = []
+
+    class Raygen:
+        @staticmethod
+        def apply(pose, kinv, pix, W):
+            calls.append(("raygen", pose, kinv, pix, W))
+            return torch.zeros(pix.shape[0], 3), torch.ones(pix.shape[0], 3)
+
+    class RayBatch:
+        @staticmethod
+        def apply(pose, kinv, seg_cam, seg_start, H, W, images=None, pix=None, seed=None, lens_w=None):
+            calls.append(("ray_batch", pose, kinv, lens_w, seg_cam, seg_start, H, W, images, pix))
+            out = torch.arange(seg_start[-1]) % (H * W) if pix is None else pix.clone()
+            return out, torch.zeros(seg_start[-1], 3), torch.ones(seg_start[-1], 3), None
+    monkeypatch.setattr(M, "RaygenFn", Raygen)
+    monkeypatch.setattr(M, "RayBatchFn", RayBatch)
+    rgb_c, rgb_f = torch.rand(min(batch, 64), 3), torch.rand(min(batch, 64), 3)
+    m.nerf.forward = lambda d, o, epoch, ratio: (calls.append(("nerf", d, o, ratio)) or (rgb_c, rgb_f))
+    m.get_rays = lambda pose, img_id, intr_inv: (torch.zeros(64, 3), torch.zeros(64, 3))
+    drawn = torch.randint(0, 64, (batch,))
+    m._draw_error_pixels = lambda c, s: (calls.append(("error_draw", c, s)) or drawn)
+    m._update_error_map = lambda *a: calls.append(("error_update",) + a)
+    hooked = torch.randint(0, 64, (batch,))
+    if "hook" in sampler:
+        m.sample_pixels_multi = lambda npix, seg: hooked
+    data = _cpu_data(sp, cams)
+    joint = stage == "GLOBAL_OPTIM_EPOCH"
+    loss_dict, *_ = m(data, 20, stage, 0.5)
+
+    n = min(batch, 64)
+    seg = [0, n] if K == 1 else [0, batch // 2, batch]
+    names = [c[0] for c in calls]
+    ray = "raygen" if (K, lens) == (1, "pinhole") else "ray_batch"
+    draws = ["error_draw"] if error and sampler != "hook+error" else []          # (an injected draw wins over the error draw)
+    assert names == draws + [ray, "nerf"] + (["error_update"] if error else [])
+    op = calls[len(draws)]
+    if ray == "raygen":
+        pix = op[3]
+        assert torch.equal(op[1], m.pose_adj[cams[0]]) and op[4] == 8 and pix.shape == (n,)
+    else:
+        _, pose, kinv, lens_w, seg_cam, seg_start, H, W, images, pix_in = op
+        assert pose is m.pose_adj and kinv.shape == (sp["data_numb"][0], 3, 3) and (H, W) == (8, 8) and images is None
+        assert (lens_w is m.weights_lens) if lens == "radial" else lens_w is None
+        assert seg_cam == cams and seg_start == seg
+        want_in = hooked if "hook" in sampler else drawn if error else None
+        if K == 1 and not error:        # the step's own uniform draw, without replacement
+            assert pix_in.shape == (n,) and len(set(pix_in.tolist())) == n
+        else:
+            assert pix_in is want_in
+        pix = pix_in if pix_in is not None else torch.arange(batch) % 64
+    if error and not draws == []:
+        assert calls[0][1:] == (cams, [0, batch] if K == 1 else seg) and torch.equal(pix, drawn)
+    nerf = calls[len(draws) + 1]
+    assert nerf[1].shape == (n, 3) and nerf[3] == (0.5 if joint else 1)
+    want_gt = data[0].reshape(-1, 3)[pix] if K == 1 else data[0].reshape(K, -1, 3)[torch.arange(batch) // (batch // 2), pix]
+    assert loss_dict["rgb"][0] is rgb_c and loss_dict["rgb"][1] is rgb_f and torch.equal(loss_dict["rgb"][2], want_gt)
+    assert loss_dict["color"][0] is m.weights_color and loss_dict["color"][1:] == [cams, seg] and set(loss_dict) == {"intr", "rgb", "color"}
+    assert m.opt_idx == (1 if joint else 2) and m.nerf.emmbedding_xyz.barf_mode is joint
+    if K > 1 or error:
+        assert m.last_step_segments == (cams, seg) and torch.equal(m.last_step_pix, pix)
+    else:
+        assert m.last_step_segments is None and m.last_step_pix is None
+    if error:
+        upd = calls[-1]
+        assert upd[1:3] == (cams, seg) and torch.equal(upd[3], pix) and upd[4] is rgb_f and torch.equal(upd[5], want_gt)      # the fine colours
+
+
+def test_camera_only_stage_takes_the_single_camera_branch_at_any_cams_per_step(monkeypatch):
+    import mc_nerf_amd.model.mc_nerf as M
+    m, sp = _model(cams_per_step=2, lens_model="radial")
+    S.init_cameras_near_gt(m)
+    monkeypatch.setattr(M.MC_Model, "_forward_train_nerf", lambda *a, **k: pytest.fail("the NeRF-stage step ran in the camera-only stage"))
+    m.get_rays = lambda pose, img_id, intr_inv: (torch.zeros(64, 3), torch.zeros(64, 3))
+    loss_dict, *_ = m(_cpu_data(sp, [3, 1]), 1, "CAM_PARAM_EPOCH", 0.0)
+    assert set(loss_dict) == {"intr", "extr"} and m.opt_idx == 0 and m.nerf.emmbedding_xyz.barf_mode is False

@@ -5,7 +5,8 @@ The fixture was recorded on an MI355X from the library of the commit before the 
 (tests/golden/make_ray_preamble.py, which also holds the cases: they exist once); the single- and the multi-camera kernels had their
 own copy of it then.  Equality with that recording is what says that sharing the functions changed no bit.  No tolerance anywhere
 except where the order of float atomics is not fixed (below).  The integer path is pinned by arithmetic as well: a uint32 restatement
-of the Feistel walk in numpy."""
+of the Feistel walk in numpy.  The two lens kernels (csrc/lens.hip) are held the same way to tests/golden/ray_preamble_lens.npz (at the
+end of the file)."""
 import importlib.util
 import os
 
@@ -120,3 +121,64 @@ def test_ray_batch_bwd(got, recorded):
     assert err <= 16.0 * 2.0 ** -24 * big
     unused = [c for c in range(cases.C) if c not in cases.SEG_CAMS["shared"]]
     assert np.abs(new[unused]).max() == 0.0 and np.abs(recorded["ray_batch_bwd.shared.d_kinv"][shared]).max() > 0
+
+
+# ------------------------------------------------------------------------------------------------------------------ with the lens
+# The two lens kernels against tests/golden/ray_preamble_lens.npz: the same batch with a fixed non-zero lens [7,2] (|k1| <= 0.08,
+# |k2| <= 0.01), recorded on an MI355X from the library of the commit before the pinhole and the lens kernels became one body with a
+# lens option (tests/golden/make_ray_preamble_lens.py; its recorder refused an inert lens: every non-empty segment's directions differ
+# from the pinhole kernel's and every camera that owns rays has a non-zero d_lens row).
+_spec = importlib.util.spec_from_file_location("make_ray_preamble_lens", os.path.join(GOLDEN, "make_ray_preamble_lens.py"))
+lens_cases = importlib.util.module_from_spec(_spec)
+_spec.loader.exec_module(lens_cases)
+
+
+@pytest.fixture(scope="module")
+def lens_recorded(recorded):
+    z = load_golden("ray_preamble_lens")
+    z.update({k: v for k, v in recorded.items() if k.startswith("in.b_")})
+    return z
+
+
+@pytest.fixture(scope="module")
+def lens_got(lens_recorded, gpu_device):
+    """Every lens case, run once."""
+    return lens_cases.run(lens_recorded, gpu_device)
+
+
+def test_lens_ray_batch_fwd(lens_got, lens_recorded, recorded):
+    """The cases of test_ray_batch_fwd at k != 0: bit equality; the pixels and origins are the pinhole kernel's, the directions are not."""
+    _same(lens_got, lens_recorded, "lens_ray_batch_fwd.", 2 * (4 + 3))
+    lens = lens_recorded["in.lens"]
+    assert lens.shape == (cases.C, 2) and np.abs(lens[:, 0]).max() <= 0.08 and np.abs(lens[:, 1]).max() <= 0.01 and np.all(lens != 0)
+    for draw in ("injected", "drawn"):
+        for key in ("pix", "o", "gt"):
+            for images in ("images", "no_images")[:1 if key == "gt" else 2]:
+                assert np.array_equal(lens_recorded[f"lens_ray_batch_fwd.{draw}.{images}.{key}"], recorded[f"ray_batch_fwd.{draw}.{images}.{key}"])
+        d, d0 = lens_recorded[f"lens_ray_batch_fwd.{draw}.images.d"], recorded[f"ray_batch_fwd.{draw}.images.d"]
+        for lo, hi in zip(cases.SEG_START, cases.SEG_START[1:]):
+            assert hi == lo or not np.array_equal(d[lo:hi], d0[lo:hi]), (draw, lo, hi)
+
+
+def test_lens_ray_batch_bwd(lens_got, lens_recorded):
+    """As test_ray_batch_bwd, with d_lens: distinct cameras, bit equality throughout.  Camera 5 in two segments: a word of d_kinv or
+    d_lens receives ONE value from each of two workgroups onto a zeroed word, which commutes: bit equality; that camera's 12 d_pose
+    words receive four to six values in an order that is not fixed: the gate of test_ray_batch_bwd, 16 * 2^-24 of the tensor's
+    largest entry; every other camera's rows bit-equal, unused cameras exactly zero."""
+    _same(lens_got, lens_recorded, "lens_ray_batch_bwd.distinct.", 3)
+    _same(lens_got, lens_recorded, "lens_ray_batch_bwd.shared.d_kinv", 1)
+    _same(lens_got, lens_recorded, "lens_ray_batch_bwd.shared.d_lens", 1)
+    new, old = lens_got["lens_ray_batch_bwd.shared.d_pose"], lens_recorded["lens_ray_batch_bwd.shared.d_pose"]
+    shared = cases.SEG_CAMS["shared"][0]
+    others = [c for c in range(cases.C) if c != shared]
+    assert np.array_equal(new[others], old[others])
+    err, big = float(np.abs(new[shared] - old[shared]).max()), float(np.abs(old).max())
+    print(f"[lens_ray_batch_bwd, camera in two segments] d_pose rows of that camera: max |new - recorded| {err:.3e}, max|recorded| {big:.3e}, "
+          f"bit-equal: {np.array_equal(new[shared], old[shared])}")
+    assert err <= 16.0 * 2.0 ** -24 * big
+    for table, cams in cases.SEG_CAMS.items():
+        unused = [c for c in range(cases.C) if c not in cams]
+        for key in ("d_pose", "d_kinv", "d_lens"):
+            assert np.abs(lens_got[f"lens_ray_batch_bwd.{table}.{key}"][unused]).max() == 0.0, (table, key)
+        owners = sorted({c for c, lo, hi in zip(cams, cases.SEG_START, cases.SEG_START[1:]) if hi > lo})
+        assert np.all(lens_recorded[f"lens_ray_batch_bwd.{table}.d_lens"][owners] != 0), table
