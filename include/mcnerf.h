@@ -451,6 +451,24 @@ int mcnerf_radam_step(int n_tensors, float* const* params, const float* const* g
                       float* const* exp_avg_sq, const long long* sizes, float lr, float beta1, float beta2, float eps,
                       float weight_decay, float step_size, int rectified, uint32_t* guard, int phase, void* stream);
 
+/* Row-lazy Rectified Adam (`"lazy_rows": True` param groups of RAdam): tensor i is n_rows[i] rows of row_len[i]
+ * elements, and every row is an optimiser of its own that steps only when it is visited.  One launch per 64 tensors, one wave per row.
+ *   visited    any element of the gradient row compares != 0.0f (-0.0 does not count, a denormal does)
+ *   unvisited  parameter, both moments and row_step[i][r] keep their bits
+ *   visited    t = row_step[i][r] + 1 is stored back;  v = beta2 v + (1-beta2) g g;  m = beta1 m + (1-beta1) g;  then the update of
+ *              mcnerf_radam_step, expression for expression, with (rectified, step_size) = table[min(max(t, 1), T) - 1]: `table` is a
+ *              DEVICE array [T,2] fp32 whose entry t - 1 holds (1.0 if N_sma(t) >= 5 else 0.0, step_size(t)), filled by the host from the
+ *              formula of the reference's step-size cache.  The caller keeps T >= every t, so the clamp never acts.
+ * The arrays of n_tensors device pointers / sizes live on the HOST.  guard (device uint32[2], or NULL) as mcnerf_radam_step's: with
+ * guard[0] raised nothing is touched (row_step included), and with count_skip the call's last launch adds 1 to guard[1].  A step that
+ * spans dense and lazy groups checks every gradient first (mcnerf_radam_step phase 2 on the flat sizes n_rows * row_len) and updates
+ * afterwards.  Deterministic: a wave owns its row, nothing is atomic.
+ * Refused ahead of any device work: a null pointer (guard excepted), n_tensors < 0, n_rows < 1 (or > 2^24), row_len < 1, T < 1. */
+int mcnerf_radam_rows_step(int n_tensors, float* const* params, const float* const* grads, float* const* exp_avg,
+                           float* const* exp_avg_sq, int32_t* const* row_step, const long long* n_rows, const long long* row_len,
+                           float lr, float beta1, float beta2, float eps, float weight_decay, const float* table, int T,
+                           uint32_t* guard, int count_skip, void* stream);
+
 /* Finish of the data-parallel step's ONE gradient all-reduce (mc_nerf_amd/distributed.py; replaces the bucketed reducer of
  * DistributedDataParallel, /root/reference main.py:60-62): `arena` = [n_grad summed gradient floats | n_flags summed flags]
  * after the SUM all-reduce.  One launch divides the gradients by `world` (DDP's average) and adds 1 to *asym when some rank's

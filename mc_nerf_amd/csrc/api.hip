@@ -7,6 +7,7 @@
 #include "mcnerf_colorcal.h"
 #include "mcnerf_lens.h"
 #include "mcnerf_errmap.h"
+#include "mcnerf_optim_rows.h"
 #include "mcnerf_16.h"
 #include "mcnerf_x3.h"
 #include <stdio.h>
@@ -547,6 +548,35 @@ int mcnerf_radam_step(int n_tensors, float* const* params, const float* const* g
             const int rc = check("mcnerf_radam_step", mcn_launch_radam(t, blocks, guard, ph, (hipStream_t)stream));
             if (rc) return rc;
         }
+    }
+    return 0;
+}
+
+int mcnerf_radam_rows_step(int n_tensors, float* const* params, const float* const* grads, float* const* exp_avg,
+                           float* const* exp_avg_sq, int32_t* const* row_step, const long long* n_rows, const long long* row_len,
+                           float lr, float beta1, float beta2, float eps, float weight_decay, const float* table, int T,
+                           uint32_t* guard, int count_skip, void* stream) {
+    const char* name = "mcnerf_radam_rows_step";
+    REQ(n_tensors >= 0 && params && grads && exp_avg && exp_avg_sq && row_step && n_rows && row_len && table && T >= 1, name);
+    for (int i = 0; i < n_tensors; ++i) {
+        REQ(params[i] && grads[i] && exp_avg[i] && exp_avg_sq[i] && row_step[i], name);
+        REQ(n_rows[i] >= 1 && n_rows[i] <= (1ll << 24) && row_len[i] >= 1, name);         // (64 tensors' rows fit first_row and the grid)
+    }
+    for (int t0 = 0; t0 < n_tensors; t0 += MCN_RADAM_MAXT) {               // 64 tensors per launch
+        McnRadamRowsTable t;
+        t.n_tensors = n_tensors - t0 < MCN_RADAM_MAXT ? n_tensors - t0 : MCN_RADAM_MAXT;
+        t.T = T; t.lr = lr; t.beta1 = beta1; t.beta2 = beta2; t.eps = eps; t.wd = weight_decay; t.table = table;
+        long long rows = 0;
+        for (int i = 0; i < t.n_tensors; ++i) {
+            t.p[i] = params[t0 + i]; t.g[i] = grads[t0 + i]; t.m[i] = exp_avg[t0 + i]; t.v[i] = exp_avg_sq[t0 + i];
+            t.row_step[i] = row_step[t0 + i]; t.row_len[i] = row_len[t0 + i];
+            t.first_row[i] = (int)rows;
+            rows += n_rows[t0 + i];
+        }
+        t.total_rows = rows;
+        const bool last = t0 + MCN_RADAM_MAXT >= n_tensors;
+        const int rc = check(name, mcn_launch_radam_rows(t, guard, last && count_skip ? 1 : 0, (hipStream_t)stream));
+        if (rc) return rc;
     }
     return 0;
 }

@@ -545,6 +545,15 @@ class MC_Model(nn.Module):
         if self.lens_model == "radial":      # an offset from "no distortion" (zeros), as weights_color
             self.register_parameter("weights_lens", nn.Parameter(torch.zeros(C, 2, device=dev), requires_grad=True))
 
+    def optimizer_groups(self, lazy_cameras=True):
+        """The two param groups of a row-lazy optimiser, each in `named_parameters` order: the radiance-field tensors,
+        and every per-camera tensor registered above ([C, ...]: a row per training camera) with `"lazy_rows": lazy_cameras`, so that
+        RAdam steps a camera's rows only when the camera has a gradient.  Callers add `lr` etc. to the dicts; `RAdam(model.parameters())`
+        stays the dense optimiser of the reference."""
+        named = list(self.named_parameters())
+        return [{"params": [p for n, p in named if n.startswith("nerf.")]},
+                {"params": [p for n, p in named if not n.startswith("nerf.")], "lazy_rows": bool(lazy_cameras)}]
+
     # ------------------------------------------------------------------ error-guided pixel sampling (DESIGN.md 4e)
     @staticmethod
     def _error_settings(sys_param):

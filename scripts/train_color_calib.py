@@ -1,7 +1,10 @@
 """Convergence experiment of the per-camera colour calibration: does the calibrated loss undo per-camera exposure /
 white-balance / black-level differences that would otherwise be baked into the field?
 
-    python scripts/train_color_calib.py [--steps 500] [--runs N] [--lr-color LR] [--beta1-color B] [--reg LAMBDA] [--out profiles/color_calib_convergence.txt]
+    python scripts/train_color_calib.py [--steps 500] [--runs N] [--lr-color LR] [--beta1-color B] [--reg LAMBDA] [--out profiles/color_calib_convergence.txt] [dense|lazy]
+
+The trailing `lazy` makes the colour group row-lazy (`"lazy_rows": True`): a camera's row steps only when the camera is the
+step's; `dense` (the default) is the experiment as it was recorded.
 
 The radiance-field loop is tests/test_y_convergence_gpu._field_run, imported and run as it is (procedural blob scene, 110-camera Ball
 rig, 100 x 100 float images, 4096 rays per step, f16x3h, one seed); three runs:
@@ -45,10 +48,10 @@ def rig_split():
     return C, [i for i in range(C) if i not in test_ids], test_ids
 
 
-def field_run_with(dev, response=None, calibrate=False, seed=0, steps=STEPS, lr_color=LR_COLOR, reg=None, betas_color=BETAS_COLOR):
+def field_run_with(dev, response=None, calibrate=False, seed=0, steps=STEPS, lr_color=LR_COLOR, reg=None, betas_color=BETAS_COLOR, lazy=False):
     """`_field_run(dev, PRECISION, steps, seed)` with the ground truth of every TRAINING step passed through its camera's colour response
     (`response` = (gain, bias) [C,3] on `dev`) and, with `calibrate`, the loss replaced by get_rgb_loss_calibrated on a zero [C,6]
-    parameter that joins the loop's optimiser as a second group (`lr_color`, `betas_color`; `reg` None: the default "color_calib_reg").  The loop's
+    parameter that joins the loop's optimiser as a second group (`lr_color`, `betas_color`, `lazy`: a row-lazy group; `reg` None: the default "color_calib_reg").  The loop's
     camera of every step is its own host-side draw, repeated here (no device read-back).  -> (held-out PSNR against the clean
     images, the [C,6] parameter | None)."""
     import test_y_convergence_gpu as Y
@@ -74,6 +77,8 @@ def field_run_with(dev, response=None, calibrate=False, seed=0, steps=STEPS, lr_
             group = {"params": [state["w"]], "lr": lr_color}
             if betas_color is not None:
                 group["betas"] = tuple(betas_color)
+            if lazy:
+                group["lazy_rows"] = True
             super().__init__([{"params": list(params)}, group], **kw)
 
     with mock.patch.object(M.MC_NeRF_Loss, "get_rgb_loss", rgb_loss), mock.patch.object(M, "RAdam", RAdamWithColour if calibrate else M.RAdam):
@@ -82,7 +87,7 @@ def field_run_with(dev, response=None, calibrate=False, seed=0, steps=STEPS, lr_
     return psnr, state["w"]
 
 
-def experiment(dev, steps=STEPS, lr_color=LR_COLOR, reg=None, seed=0, betas_color=BETAS_COLOR):
+def experiment(dev, steps=STEPS, lr_color=LR_COLOR, reg=None, seed=0, betas_color=BETAS_COLOR, lazy=False):
     """The three runs -> dict(psnr_a, psnr_b, psnr_c, gain_ratio, text)."""
     from mc_nerf_amd import synthetic as S
     from mc_nerf_amd.model.loss import COLOR_CALIB_REG
@@ -91,13 +96,13 @@ def experiment(dev, steps=STEPS, lr_color=LR_COLOR, reg=None, seed=0, betas_colo
     response = (gain.to(dev), bias.to(dev))
     psnr_a, _ = field_run_with(dev, seed=seed, steps=steps)
     psnr_b, _ = field_run_with(dev, response, seed=seed, steps=steps)
-    psnr_c, w = field_run_with(dev, response, calibrate=True, seed=seed, steps=steps, lr_color=lr_color, reg=reg, betas_color=betas_color)
+    psnr_c, w = field_run_with(dev, response, calibrate=True, seed=seed, steps=steps, lr_color=lr_color, reg=reg, betas_color=betas_color, lazy=lazy)
     g_hat, g_true = (1.0 + w.detach()[train_ids, :3]).cpu().double(), gain[train_ids].double()
     rel = lambda g: g / g.mean(0, keepdim=True)
     rms = lambda x: float((x ** 2).mean().sqrt())
     ratio = rms(rel(g_hat) - rel(g_true)) / rms(1.0 - rel(g_true))
     text = (f"procedural scene 100x100, 4096 rays x {steps} steps, {PRECISION}, gain spread {GAIN_SPREAD}, bias spread {BIAS_SPREAD}, "
-            f"color_calib_reg {COLOR_CALIB_REG if reg is None else reg:g} (not tuned), colour group lr {lr_color:g} betas {tuple(betas_color)}: held-out PSNR against the clean "
+            f"color_calib_reg {COLOR_CALIB_REG if reg is None else reg:g} (not tuned), colour group lr {lr_color:g} betas {tuple(betas_color)}{' lazy rows' if lazy else ''}: held-out PSNR against the clean "
             f"images A (clean, off) {psnr_a:.2f} dB, B (perturbed, off) {psnr_b:.2f} dB, C (perturbed, on) {psnr_c:.2f} dB; "
             f"rms error of the relative gains / identity's {ratio:.3f}")
     return dict(psnr_a=psnr_a, psnr_b=psnr_b, psnr_c=psnr_c, gain_ratio=ratio, text=text)
@@ -119,10 +124,12 @@ if __name__ == "__main__":
     ap.add_argument("--reg", type=float, default=None)
     ap.add_argument("--runs", type=int, default=1)
     ap.add_argument("--out", default=None)
+    ap.add_argument("camera_group", nargs="?", choices=["dense", "lazy"], default="dense")
     args = ap.parse_args()
     lines = []
     for run in range(args.runs):
-        r = experiment(torch.device("cuda:0"), steps=args.steps, lr_color=args.lr_color, reg=args.reg, betas_color=(args.beta1_color, BETAS_COLOR[1]))
+        r = experiment(torch.device("cuda:0"), steps=args.steps, lr_color=args.lr_color, reg=args.reg, betas_color=(args.beta1_color, BETAS_COLOR[1]),
+                       lazy=args.camera_group == "lazy")
         lines.append(f"run {run + 1}: " + r["text"])
         print(lines[-1], flush=True)
     record(lines, args.out)

@@ -1,8 +1,9 @@
 """Joint camera + radiance-field optimisation (the GLOBAL_OPTIM stage of MC-NeRF, BARF mask on) on the procedural scene of
 train_procedural.py, through MC_Model: device-resident uint8 images, fused camera kernels, HIP renderer, fused RAdam.
 Cameras start from the ground truth perturbed by `noise` in se(3) (rad / scene units); reports camera errors and PSNR.
-Usage (GPU box):  python scripts/train_joint.py [f32|f16x3] [steps] [noise] [cams_per_step]
+Usage (GPU box):  python scripts/train_joint.py [f32|f16x3] [steps] [noise] [cams_per_step] [dense|lazy]
 `cams_per_step` (default 1): cameras whose rays share one step (the multi-camera step of DESIGN.md 4c); the batch stays N rays.
+`lazy`: the camera group of the optimiser is row-lazy (`MC_Model.optimizer_groups`); `dense` (the default) is today's step.
 """
 import math, os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -15,6 +16,9 @@ precision = sys.argv[1] if len(sys.argv) > 1 else "f16x3"
 steps = int(sys.argv[2]) if len(sys.argv) > 2 else 3000
 noise = float(sys.argv[3]) if len(sys.argv) > 3 else 0.02
 cams_per_step = int(sys.argv[4]) if len(sys.argv) > 4 else 1
+camera_group = sys.argv[5] if len(sys.argv) > 5 else "dense"
+if camera_group not in ("dense", "lazy"):
+    sys.exit(f"the fifth argument is 'dense' or 'lazy', got {camera_group!r}")
 dev = torch.device("cuda:0")
 H = W = 200
 N = 8192
@@ -56,7 +60,11 @@ S.init_cameras_near_gt(model, noise=noise, seed=3)
 loss_fn = MC_NeRF_Loss(sp)
 cam_params = [p for n, p in model.named_parameters() if not n.startswith("nerf.")]
 nerf_params = [p for n, p in model.named_parameters() if n.startswith("nerf.")]
-opt = RAdam([{"params": nerf_params, "lr": 5e-4}, {"params": cam_params, "lr": 1e-3}], weight_decay=0.0)
+if camera_group == "lazy":
+    nerf_group, cam_group = model.optimizer_groups(lazy_cameras=True)
+    opt = RAdam([{**nerf_group, "lr": 5e-4}, {**cam_group, "lr": 1e-3}], weight_decay=0.0)
+else:
+    opt = RAdam([{"params": nerf_params, "lr": 5e-4}, {"params": cam_params, "lr": 1e-3}], weight_decay=0.0)
 wpts, pts = S.calibration_points(sp["gt_pose"], sp["intr_mat"][0])
 wpts, pts = wpts.to(dev), pts.to(dev)
 
@@ -81,7 +89,7 @@ def report(tag):
           f"{float((c_e - c_g).norm(dim=-1).mean()):.4f}, focal error {float(foc) * 100:.2f} %, PSNR {sum(ps) / len(ps):.2f} dB")
 
 
-print(f"precision {precision}, {C} cameras {H}x{W}, se(3) noise {noise}, {N} rays/step over {cams_per_step} camera(s), GLOBAL_OPTIM (BARF 0.1 -> 0.5 of the run)")
+print(f"precision {precision}, {C} cameras {H}x{W}, se(3) noise {noise}, {N} rays/step over {cams_per_step} camera(s), camera group {camera_group}, GLOBAL_OPTIM (BARF 0.1 -> 0.5 of the run)")
 report("step     0")
 t0 = time.time()
 sp_b = (sp["barf_start"], sp["barf_end"])
