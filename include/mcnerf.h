@@ -208,7 +208,9 @@ int mcnerf_composite_fwd(const float* sig_rgb, const float* rays_d, const float*
                          const float* eps, const float* eps_sel, int N, int S, int white_back,
                          float* rgb, float* depth, float* opacity, float* w_sel, uint32_t* wmax_bits, void* stream);
 /* Backward of the rgb composite: d_rgb [N,3] -> d_sig_rgb [N,S,4].  gmax_bits (or NULL): max |d_sig_rgb| of the
- * launch as float bits, max-reduced into a caller-zeroed word (the gradient scale of mcnerf_mlp_bwd_16). */
+ * launch as float bits, max-reduced into a caller-zeroed word (the gradient scale of mcnerf_mlp_bwd_16).
+ * S <= 2048: a workgroup stages 5 floats per sample for each of its 4 rays in LDS, 160 KiB at S = 2048 (more is refused as an
+ * invalid argument).  N = 0 is a no-op in both calls (the arrays may then be null pointers). */
 int mcnerf_composite_bwd(const float* sig_rgb, const float* zgrid, int z_stride, const float* jitter, const float* eps,
                          const float* d_rgb, int N, int S, int white_back, float* d_sig_rgb, uint32_t* gmax_bits,
                          void* stream);

@@ -403,7 +403,9 @@ int mcnerf_mlp_dw_16(int depth, int width, int skip, int dtype, const int32_t* c
 int mcnerf_composite_fwd(const float* sig_rgb, const float* rays_d, const float* zgrid, int z_stride, const float* jitter,
                          const float* eps, const float* eps_sel, int N, int S, int white_back,
                          float* rgb, float* depth, float* opacity, float* w_sel, uint32_t* wmax_bits, void* stream) {
-    REQ(sig_rgb && rays_d && zgrid && eps && rgb && N >= 0 && S > 0, "mcnerf_composite_fwd");
+    REQ(N >= 0 && S > 0, "mcnerf_composite_fwd");
+    if (N == 0) return 0;                 // no rays: nothing is read or written (the empty arrays of a caller may be null pointers)
+    REQ(sig_rgb && rays_d && zgrid && eps && rgb, "mcnerf_composite_fwd");
     REQ((depth == nullptr) == (opacity == nullptr), "mcnerf_composite_fwd");
     REQ(!eps_sel || w_sel, "mcnerf_composite_fwd");
     REQ(z_ok(z_stride, S), "mcnerf_composite_fwd");
@@ -412,8 +414,10 @@ int mcnerf_composite_fwd(const float* sig_rgb, const float* rays_d, const float*
 }
 int mcnerf_composite_bwd(const float* sig_rgb, const float* zgrid, int z_stride, const float* jitter, const float* eps,
                          const float* d_rgb, int N, int S, int white_back, float* d_sig_rgb, uint32_t* gmax_bits, void* stream) {
-    REQ(sig_rgb && zgrid && eps && d_rgb && d_sig_rgb && N >= 0 && S > 0, "mcnerf_composite_bwd");
+    REQ(N >= 0 && S > 0, "mcnerf_composite_bwd");
     REQ((size_t)4 * 5 * S * sizeof(float) <= 160 * 1024, "mcnerf_composite_bwd");
+    if (N == 0) return 0;                 // (as mcnerf_composite_fwd)
+    REQ(sig_rgb && zgrid && eps && d_rgb && d_sig_rgb, "mcnerf_composite_bwd");
     REQ(z_ok(z_stride, S), "mcnerf_composite_bwd");
     McnCompositeBwdArgs a = {sig_rgb, zgrid, jitter, eps, d_rgb, N, S, white_back, d_sig_rgb, gmax_bits, z_stride};
     return check("mcnerf_composite_bwd", mcn_launch_composite_bwd(a, (hipStream_t)stream));

@@ -125,6 +125,7 @@ def test_composite_fwd_bwd(gpu_device, S):
     assert maxerr(op, opac) < 2e-6
     assert maxerr(ws, w2) < 2e-6
     assert abs(wmax.view(torch.float32).item() - float(w2.max())) < 1e-6
+    assert wmax.view(torch.float32).item() == float(ws.max())        # exactly the largest weight written: a maximum does not round
     grgb = torch.randn(N, 3, generator=g)
     (rgb * grgb).sum().backward()
     dsr = ops.composite_bwd(sig_rgb.to(dev), zg.to(dev), jd, eps.to(dev), grgb.to(dev), True)
