@@ -212,10 +212,12 @@ int mcnerf_train_loss_calib(const float* pd, const float* pt_gt, int np, int H, 
                                color_w, C, reg_lambda, out, d_pd, d_c, d_f, d_color, partials};
     return check("mcnerf_train_loss_calib", mcn_launch_train_loss_calib(a, t, (hipStream_t)stream));
 }
+// the error map's geometry (as vox_ok for the voxel grid): a tile of at least one pixel, an image of at most 2^26 pixels
+static bool err_ok(int H, int W, int tile) { return H > 0 && W > 0 && tile >= 1 && (long long)H * W <= (1ll << 26); }
 // The error-guided pixel sampler (errmap.hip): everything is checked before any HIP call, as for mcnerf_ray_batch_fwd.
 int mcnerf_errmap_sample(const float* err, int C, int H, int W, int tile, const int32_t* seg_cam, const int32_t* seg_start, int K,
                          int n, float uniform_frac, const float* u, uint64_t* cdf, int64_t* pix, void* stream) {
-    REQ(H > 0 && W > 0 && tile >= 1 && (long long)H * W <= (1ll << 26), "mcnerf_errmap_sample");
+    REQ(err_ok(H, W, tile), "mcnerf_errmap_sample");
     McnSegTable t = {};
     if (int rc = fill_segments("mcnerf_errmap_sample", t, seg_cam, seg_start, K, C, n, n)) return rc;
     REQ(uniform_frac >= 0.f && uniform_frac <= 1.f, "mcnerf_errmap_sample");
@@ -226,7 +228,7 @@ int mcnerf_errmap_sample(const float* err, int C, int H, int W, int tile, const 
 int mcnerf_errmap_update(float* err, uint32_t* scratch, int C, int H, int W, int tile, const int32_t* seg_cam, const int32_t* seg_start,
                          int K, int n, const int64_t* pix, const float* rgb, const float* gt, float beta, float one_minus_beta,
                          void* stream) {
-    REQ(H > 0 && W > 0 && tile >= 1 && (long long)H * W <= (1ll << 26), "mcnerf_errmap_update");
+    REQ(err_ok(H, W, tile), "mcnerf_errmap_update");
     McnSegTable t = {};
     if (int rc = fill_segments("mcnerf_errmap_update", t, seg_cam, seg_start, K, C, n, n)) return rc;
     REQ(beta >= 0.f && beta <= 1.f && one_minus_beta >= 0.f && one_minus_beta <= 1.f, "mcnerf_errmap_update");

@@ -16,11 +16,9 @@
 //          otherwise: target = (uint64)((double)u0 * (double)total), tile = first t with cdf[k][t] > target, pixel
 //          l = min((int)(u1 * (float)area_t), area_t - 1) of that tile in row-major order.  Draws are WITH replacement.
 //
-// UPDATE, voxel.hip's protocol, deterministic whatever the order of arrival: per ray e = ((d0^2 + d1^2) + d2^2) * (1/3 in fp32),
-// d = rgb - gt, every step a separately rounded fp32 operation; (1) atomicMax of the order-preserving key of e into
-// scratch[cam, tile(pix)]; (2) every ray atomicExch'es its word with 0 and the one thread that receives a non-zero key writes
-//   E <- (1 - beta) * E + beta * m     as  __fadd_rn(__fmul_rn(1 - beta, E), __fmul_rn(beta, m)),  1 - beta formed on the host.
-// Rays with a non-finite e or a pixel outside the image are skipped; untouched tiles keep their bits; scratch is all zero again.
+// UPDATE: the "max per cell, single writer" protocol of mcnerf_maxkey.h on the map, the cell of a ray being [cam, tile(pix)] and its
+// value e = ((d0^2 + d1^2) + d2^2) * (1/3 in fp32), d = rgb - gt, every step a separately rounded fp32 operation.  Rays with a
+// non-finite e or a pixel outside the image are skipped.
 #include "mcnerf_errmap.h"
 #include "mcnerf_maxkey.h"
 
@@ -123,16 +121,10 @@ __device__ __forceinline__ bool err_item(const McnErrUpdateArgs& a, const McnSeg
     return (__float_as_uint(e) & 0x7F800000u) != 0x7F800000u;
 }
 __global__ __launch_bounds__(256) void errmap_max_kernel(McnErrUpdateArgs a, McnSegTable t) {
-    size_t cell; float e;
-    if (!err_item(a, t, blockIdx.x * 256 + threadIdx.x, cell, e)) return;
-    atomicMax(&a.scratch[cell], vox_key(e));
+    mcn_cell_max(a.scratch, [&](int i, size_t& cell, float& e) { return err_item(a, t, i, cell, e); });
 }
 __global__ __launch_bounds__(256) void errmap_blend_kernel(McnErrUpdateArgs a, McnSegTable t) {
-    size_t cell; float e;
-    if (!err_item(a, t, blockIdx.x * 256 + threadIdx.x, cell, e)) return;
-    const unsigned k = atomicExch(&a.scratch[cell], 0u);
-    if (k == 0u) return;                                    // another ray of this tile is its writer
-    a.err[cell] = __fadd_rn(__fmul_rn(a.one_minus_beta, a.err[cell]), __fmul_rn(a.beta, vox_unkey(k)));
+    mcn_cell_blend(a.err, a.scratch, a.beta, a.one_minus_beta, [&](int i, size_t& cell, float& e) { return err_item(a, t, i, cell, e); });
 }
 hipError_t mcn_launch_errmap_update(const McnErrUpdateArgs& a, const McnSegTable& t, hipStream_t st) {
     if (a.n <= 0) return hipSuccess;

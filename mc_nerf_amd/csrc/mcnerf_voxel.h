@@ -3,9 +3,6 @@
 #pragma once
 #include "mcnerf_kernels.h"
 
-// the scan alone: ray_counts [N] -> exclusive ray_offsets [N], total -> *count (reads N, ray_counts, ray_offsets, count of `a`)
-hipError_t mcn_launch_select_scan(const McnSelectArgs& a, hipStream_t st);
-
 // ---- voxel sigma cache (voxel.hip): the grid is vox [G,G,G] over [bmin, bmin + G / s]^3, s = G / (bmax - bmin) formed on the host
 struct McnVoxelSelectArgs {
     const float* vox;         // [G,G,G] running raw sigma

@@ -1,13 +1,8 @@
 // Fused multi-tensor Rectified-Adam step for gfx950: ONE launch updates every parameter tensor of a
 // param group (46 MLP tensors + 6 camera tensors in MC-NeRF), replacing the reference's per-tensor Python
 // loop of ~10 ATen ops each (model/net_utils.py:38-99).  Pure streaming: 16 B/element read + 12 B written.
-//
-// Semantics per element (reference :62-63, 88-99), with the scalar step size / N_sma computed on the host
-// exactly like the reference's 10-slot cache (:67-86):
-//   v = beta2 v + (1-beta2) g^2 ;  m = beta1 m + (1-beta1) g
-//   rectified (N_sma >= 5):  p -= wd*lr*p ;  p -= step_size*lr * m / (sqrt(v) + eps)
-//   otherwise (step_size>0): p -= wd*lr*p ;  p -= step_size*lr * m
-#include "mcnerf_kernels.h"
+// The update of one element is mcn_radam_element (mcnerf_optim_rows.h), shared with the row-lazy kernel.
+#include "mcnerf_optim_rows.h"
 
 // Overflow guard: the 16-bit precision modes carry range limits (f16 operands saturate to inf, which the fp32
 // accumulators turn into NaN gradients); one non-finite gradient would poison the flat parameter buffers for good.
@@ -42,21 +37,8 @@ __global__ __launch_bounds__(256) void radam_kernel(McnRadamTable t, unsigned* g
     float* __restrict__ v = t.v[ti];
     const long long n = t.n[ti];
     const float b1 = t.beta1, b2 = t.beta2, decay = t.wd * t.lr, ss = t.step_size * t.lr;
-    for (long long i = base + threadIdx.x; i < base + MCN_RADAM_CHUNK && i < n; i += 256) {
-        const float gi = g[i];
-        const float vi = b2 * v[i] + (1.f - b2) * gi * gi;
-        const float mi = b1 * m[i] + (1.f - b1) * gi;
-        v[i] = vi; m[i] = mi;
-        float pi = p[i];
-        if (t.rectified) {
-            pi += -decay * pi;
-            pi += -ss * (mi / (sqrtf(vi) + t.eps));
-        } else if (t.step_size > 0.f) {
-            pi += -decay * pi;
-            pi += -ss * mi;
-        }
-        p[i] = pi;
-    }
+    for (long long i = base + threadIdx.x; i < base + MCN_RADAM_CHUNK && i < n; i += 256)
+        mcn_radam_element(p, g, m, v, i, b1, b2, decay, ss, t.eps, t.rectified != 0, t.step_size);
 }
 
 // phase bits (include/mcnerf.h): 1 = clear guard[0] first, 2 = check the gradients, 4 = update, 8 = this launch counts a refused step

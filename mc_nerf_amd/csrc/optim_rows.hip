@@ -5,8 +5,8 @@
 //
 // One wave per row, four rows per block.  The lanes stride over the row's L elements twice: once to vote whether the row is visited
 // (a wave vote: the branch is wave-uniform), once to update it.  The wave owns the row, so nothing is atomic and the result does not
-// depend on the order of anything.  The element arithmetic is radam_kernel's, expression for expression (the build has
-// -ffp-contract=off): a group whose rows are all visited on every step gets the bits of the dense kernel.
+// depend on the order of anything.  The element arithmetic is mcn_radam_element, the function radam_kernel calls: a group whose
+// rows are all visited on every step gets the bits of the dense kernel.
 #include "mcnerf_optim_rows.h"
 
 __global__ __launch_bounds__(256) void radam_rows_kernel(McnRadamRowsTable t, unsigned* guard, int count_skip) {
@@ -37,21 +37,7 @@ __global__ __launch_bounds__(256) void radam_rows_kernel(McnRadamRowsTable t, un
     const bool rectified = t.table[2 * e] != 0.f;
     const float step_size = t.table[2 * e + 1];
     const float b1 = t.beta1, b2 = t.beta2, decay = t.wd * t.lr, ss = step_size * t.lr;
-    for (long long i = lane; i < L; i += 64) {
-        const float gi = g[i];
-        const float vi = b2 * v[i] + (1.f - b2) * gi * gi;
-        const float mi = b1 * m[i] + (1.f - b1) * gi;
-        v[i] = vi; m[i] = mi;
-        float pi = p[i];
-        if (rectified) {
-            pi += -decay * pi;
-            pi += -ss * (mi / (sqrtf(vi) + t.eps));
-        } else if (step_size > 0.f) {
-            pi += -decay * pi;
-            pi += -ss * mi;
-        }
-        p[i] = pi;
-    }
+    for (long long i = lane; i < L; i += 64) mcn_radam_element(p, g, m, v, i, b1, b2, decay, ss, t.eps, rectified, step_size);
     if (lane == 0) row_step[r] = step;
 }
 

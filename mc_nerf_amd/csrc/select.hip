@@ -1,37 +1,23 @@
 // What the fine pass needs between the coarse weights and the fine MLP, entirely on the device:
-// (1) Weight-threshold fine-sample selection + compaction (count / scan / write): replaces nonzero / expand / arithmetic / index_put
-//     of model/mc_nerf.py:623-629, 692-694 and removes the reference's host syncs (.item(), nonzero).  The scan also serves voxel.hip.
+// (1) Weight-threshold fine-sample selection (model/mc_nerf.py:623-629, 692-694, without the reference's host syncs .item(), nonzero): the
+//     fine list's predicate over the shared compaction of mcnerf_compact.h, and the exclusive scan of every caller of it (voxel.hip too).
 // (2) The random cap of the selected list (model/mc_nerf.py:630-632): cap_gather replays a given permutation, cap_random draws the
 //     subset on the device.
 // (3) The stand-alone positional encoding and its backward, and upload_f32 (small host values as kernel arguments).
-#include "mcnerf_kernels.h"
-#include "mcnerf_voxel.h"
+#include "mcnerf_compact.h"
 #include "mcnerf_hash.h"
 
 // ------------------------------------------------------------------ selection
-__device__ __forceinline__ float sel_threshold(const McnSelectArgs& a) {
-    // min(weight_thresh, weights.max()) (model/mc_nerf.py:623)
-    return fminf(a.thresh, __uint_as_float(*a.wmax_bits));
-}
-
+// min(weight_thresh, weights.max()) (model/mc_nerf.py:623)
+__device__ __forceinline__ float sel_threshold(const McnSelectArgs& a) { return fminf(a.thresh, __uint_as_float(*a.wmax_bits)); }
+struct SelectPred {             // (built behind the bounds check of the shared bodies: a wave beyond the batch does not read the word)
+    const McnSelectArgs& a;
+    const float thr;
+    __device__ __forceinline__ SelectPred(const McnSelectArgs& a) : a(a), thr(sel_threshold(a)) {}
+    __device__ __forceinline__ bool operator()(int n, int j) const { return a.w_sel[(size_t)n * a.Sc + j] >= thr; }
+};
 __global__ __launch_bounds__(256) void select_count_kernel(McnSelectArgs a) {
-    const int lane = threadIdx.x & 63;
-    const int n = blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (n >= a.N) return;
-    const float thr = sel_threshold(a);
-    int cnt = 0;
-    for (int base = 0; base < a.Sc; base += 64) {
-        const int j = base + lane;
-        const bool sel = j < a.Sc && a.w_sel[(size_t)n * a.Sc + j] >= thr;
-        cnt += __popcll(__ballot(sel));
-    }
-    if (lane == 0) a.ray_counts[n] = cnt * a.scale;
-    if (a.out_f) {      // defaults for never-evaluated fine samples (model/mc_nerf.py:692-694)
-        const int Sf = a.Sc * a.scale;
-        f32x4 d; d[0] = a.sigma_default; d[1] = 1.f; d[2] = 1.f; d[3] = 1.f;
-        f32x4* o = reinterpret_cast<f32x4*>(a.out_f) + (size_t)n * Sf;
-        for (int j = lane; j < Sf; j += 64) o[j] = d;
-    }
+    mcn_compact_count<SelectPred>(a.N, a.Sc, a.scale, a.sigma_default, a.ray_counts, a.out_f, a);
 }
 
 // Exclusive scan of ray_counts -> ray_offsets, total -> *count.  One workgroup; N is at most ~1e6.  Every thread owns one
@@ -99,35 +85,15 @@ __global__ __launch_bounds__(1024) void select_scan_kernel(McnSelectArgs a) {
 }
 
 __global__ __launch_bounds__(256) void select_write_kernel(McnSelectArgs a) {
-    const int lane = threadIdx.x & 63;
-    const int n = blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (n >= a.N) return;
-    const float thr = sel_threshold(a);
-    int pos = a.ray_offsets[n];
-    for (int base = 0; base < a.Sc; base += 64) {
-        const int j = base + lane;
-        const bool sel = j < a.Sc && a.w_sel[(size_t)n * a.Sc + j] >= thr;
-        const unsigned long long m = __ballot(sel);
-        if (sel) {
-            const int rank = __popcll(m & ((1ull << lane) - 1ull));
-            int2* dst = a.idx + pos + rank * a.scale;
-            for (int r = 0; r < a.scale; ++r) dst[r] = make_int2(n, j * a.scale + r);
-        }
-        pos += __popcll(m) * a.scale;
-    }
+    mcn_compact_write<SelectPred>(a.N, a.Sc, a.scale, a.ray_offsets, a.idx, a);
 }
 
 hipError_t mcn_launch_select(const McnSelectArgs& a, hipStream_t st) {
-    if (a.N <= 0) return hipSuccess;
-    const dim3 g((a.N + 3) / 4), b(256);
-    hipLaunchKernelGGL(select_count_kernel, g, b, 0, st, a);
-    hipLaunchKernelGGL(select_scan_kernel, dim3(1), dim3(1024), 0, st, a);
-    hipLaunchKernelGGL(select_write_kernel, g, b, 0, st, a);
-    return hipGetLastError();
+    return mcn_launch_compact<McnSelectArgs, select_count_kernel, select_write_kernel>(a, st);
 }
-// the scan for a caller with its own count and write kernels (voxel.hip)
-hipError_t mcn_launch_select_scan(const McnSelectArgs& a, hipStream_t st) {
-    if (a.N <= 0) return hipSuccess;
+hipError_t mcn_launch_select_scan(int N, int* ray_counts, int* ray_offsets, int* count, hipStream_t st) {
+    McnSelectArgs a = {};       // (the scan reads these four fields alone)
+    a.N = N; a.ray_counts = ray_counts; a.ray_offsets = ray_offsets; a.count = count;
     hipLaunchKernelGGL(select_scan_kernel, dim3(1), dim3(1024), 0, st, a);
     return hipGetLastError();
 }

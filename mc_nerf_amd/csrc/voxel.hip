@@ -10,15 +10,10 @@
 // linear index (ix * G + iy) * G + iz in 64 bits.  Sample j of ray n sits at p = o + d * z, z = zgrid[j] + jitter[n], every step a
 // separately rounded fp32 operation (as sample_pdf.hip forms its depths): the cell of a sample is a pure function of its inputs.
 //
-// SELECT: count per ray -> exclusive scan (select_scan_kernel of select.hip) -> ordered write.  The list is in torch.nonzero
-// (row-major) order and no atomic decides a position; the predicate is a gather vox[cell] > thresh (a NaN cell is empty).
-//
-// UPDATE, deterministic whatever the order of arrival: (1) every sample takes atomicMax of an order-preserving uint32 key of its
-// sigma into a scratch grid (0 = none; every finite float's key is > 0; non-finite sigmas are skipped); (2) every sample atomicExch'es
-// its cell's scratch word with 0 and the one thread that receives a non-zero key is the cell's single writer of
-//   V <- (1 - beta) * V + beta * m      as  __fadd_rn(__fmul_rn(1 - beta, V), __fmul_rn(beta, m)),  1 - beta formed on the host.
-// Untouched cells keep their bits, and the scratch grid is all zero again afterwards.
+// SELECT: the ordered list compaction of mcnerf_compact.h with scale 1 under the predicate vox[cell] > thresh (a NaN cell is empty).
+// UPDATE: the "max per cell, single writer" protocol of mcnerf_maxkey.h on the grid, an item being a sample and its raw sigma.
 #include "mcnerf_voxel.h"
+#include "mcnerf_compact.h"
 #include "mcnerf_maxkey.h"
 
 __device__ __forceinline__ int vox_axis(float p, float bmin, float s, int G) {
@@ -39,50 +34,23 @@ __device__ __forceinline__ size_t vox_sample_cell(const float* rays_o, const flo
 }
 
 // ------------------------------------------------------------------ select
-// one wavefront per ray, four rays per workgroup (as select_count_kernel / select_write_kernel)
+struct VoxelPred {
+    const McnVoxelSelectArgs& a;
+    __device__ __forceinline__ bool operator()(int n, int j) const {
+        return a.vox[vox_sample_cell(a.rays_o, a.rays_d, a.zgrid, a.jitter, n, j, a.bmin, a.s, a.G)] > a.thresh;
+    }
+};
 __global__ __launch_bounds__(256) void voxel_count_kernel(McnVoxelSelectArgs a) {
-    const int lane = threadIdx.x & 63;
-    const int n = blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (n >= a.N) return;
-    int cnt = 0;
-    for (int base = 0; base < a.Sc; base += 64) {
-        const int j = base + lane;
-        const bool sel = j < a.Sc && a.vox[vox_sample_cell(a.rays_o, a.rays_d, a.zgrid, a.jitter, n, j, a.bmin, a.s, a.G)] > a.thresh;
-        cnt += __popcll(__ballot(sel));
-    }
-    if (lane == 0) a.ray_counts[n] = cnt;
-    if (a.out_c) {      // defaults for never-evaluated coarse samples (model/mc_nerf.py:689-694)
-        f32x4 d; d[0] = a.sigma_default; d[1] = 1.f; d[2] = 1.f; d[3] = 1.f;
-        f32x4* o = reinterpret_cast<f32x4*>(a.out_c) + (size_t)n * a.Sc;
-        for (int j = lane; j < a.Sc; j += 64) o[j] = d;
-    }
+    mcn_compact_count<VoxelPred>(a.N, a.Sc, 1, a.sigma_default, a.ray_counts, a.out_c, a);
 }
 __global__ __launch_bounds__(256) void voxel_write_kernel(McnVoxelSelectArgs a) {
-    const int lane = threadIdx.x & 63;
-    const int n = blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (n >= a.N) return;
-    int pos = a.ray_offsets[n];
-    for (int base = 0; base < a.Sc; base += 64) {
-        const int j = base + lane;
-        const bool sel = j < a.Sc && a.vox[vox_sample_cell(a.rays_o, a.rays_d, a.zgrid, a.jitter, n, j, a.bmin, a.s, a.G)] > a.thresh;
-        const unsigned long long m = __ballot(sel);
-        if (sel) a.idx[pos + __popcll(m & ((1ull << lane) - 1ull))] = make_int2(n, j);
-        pos += __popcll(m);
-    }
+    mcn_compact_write<VoxelPred>(a.N, a.Sc, 1, a.ray_offsets, a.idx, a);
 }
 hipError_t mcn_launch_voxel_select(const McnVoxelSelectArgs& a, hipStream_t st) {
-    if (a.N <= 0) return hipSuccess;
-    const dim3 g((a.N + 3) / 4), b(256);
-    hipLaunchKernelGGL(voxel_count_kernel, g, b, 0, st, a);
-    McnSelectArgs sc = {};
-    sc.N = a.N; sc.ray_counts = a.ray_counts; sc.ray_offsets = a.ray_offsets; sc.count = a.count;
-    hipError_t e = mcn_launch_select_scan(sc, st);
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(voxel_write_kernel, g, b, 0, st, a);
-    return hipGetLastError();
+    return mcn_launch_compact<McnVoxelSelectArgs, voxel_count_kernel, voxel_write_kernel>(a, st);
 }
 
-// ------------------------------------------------------------------ update (vox_key / vox_unkey: mcnerf_maxkey.h)
+// ------------------------------------------------------------------ update
 // Item i of an update: its cell and its sigma.  false: nothing there (beyond the list, a pair outside [N) x [Sc), a non-finite sigma).
 __device__ __forceinline__ bool vox_item(const McnVoxelUpdateArgs& a, long long i, size_t& cell, float& sig) {
     if (a.pts) {
@@ -107,16 +75,10 @@ __device__ __forceinline__ bool vox_item(const McnVoxelUpdateArgs& a, long long 
     return (__float_as_uint(sig) & 0x7F800000u) != 0x7F800000u;
 }
 __global__ __launch_bounds__(256) void voxel_max_kernel(McnVoxelUpdateArgs a) {
-    size_t cell; float sig;
-    if (!vox_item(a, (long long)blockIdx.x * 256 + threadIdx.x, cell, sig)) return;
-    atomicMax(&a.scratch[cell], vox_key(sig));
+    mcn_cell_max(a.scratch, [&](long long i, size_t& cell, float& sig) { return vox_item(a, i, cell, sig); });
 }
 __global__ __launch_bounds__(256) void voxel_blend_kernel(McnVoxelUpdateArgs a) {
-    size_t cell; float sig;
-    if (!vox_item(a, (long long)blockIdx.x * 256 + threadIdx.x, cell, sig)) return;
-    const unsigned k = atomicExch(&a.scratch[cell], 0u);
-    if (k == 0u) return;                                    // another sample of this cell is its writer
-    a.vox[cell] = __fadd_rn(__fmul_rn(a.one_minus_beta, a.vox[cell]), __fmul_rn(a.beta, vox_unkey(k)));
+    mcn_cell_blend(a.vox, a.scratch, a.beta, a.one_minus_beta, [&](long long i, size_t& cell, float& sig) { return vox_item(a, i, cell, sig); });
 }
 hipError_t mcn_launch_voxel_update(const McnVoxelUpdateArgs& a, hipStream_t st) {
     const long long rows = a.pts ? a.M : (a.idx ? a.max_rows : (long long)a.N * a.Sc);

@@ -233,8 +233,7 @@ def select_and_cap(st: RenderSettings, w_sel, wmax, n_rays, cap_perm, train: boo
             else:
                 max_rows = min(max_rows, max(k, 1))
         else:
-            seed = torch.randint(0, 2 ** 31 - 1, (1,), dtype=torch.int32, device=idx.device)
-            idx, count = ops.cap_random(idx, count, max_rows, keep, seed)
+            idx, count = ops.cap_random(idx, count, max_rows, keep, ops.seed_word(idx.device))
             max_rows = keep
     return idx, count, out_f, max_rows
 

@@ -302,11 +302,17 @@ def mlp_fwd(net: Net, params: Tensor, packed: Tensor, rays_o: Tensor, rays_d: Te
               _p(save.mask, torch.int32) if save else None, _stream())
 
 
+def seed_word(device) -> Tensor:
+    """The key word of a device-side draw (sample_perm, the ray-batch forwards, cap_random): one int32 [1] from torch's device
+    generator, so torch.manual_seed reproduces it."""
+    return torch.randint(0, 2 ** 31 - 1, (1,), dtype=torch.int32, device=device)
+
+
 def sample_perm(n: int, batch: int, device, seed: Optional[Tensor] = None) -> Tensor:
     """randperm(n)[:batch] (model/mc_nerf.py:329) in one kernel: `batch` distinct uniformly random ids of [0, n) in random
     order (int64); the key is a device word drawn from torch's device generator, so torch.manual_seed reproduces it."""
     if seed is None:
-        seed = torch.randint(0, 2 ** 31 - 1, (1,), dtype=torch.int32, device=device)
+        seed = seed_word(device)
     out = torch.empty(batch, dtype=torch.int64, device=device)
     _lib.call("mcnerf_sample_perm", _p(out, torch.int64), int(n), int(batch), _p(seed, torch.int32), _stream())
     return out
@@ -360,7 +366,7 @@ def _ray_batch_fwd(symbol: str, pose: Tensor, kinv: Tensor, lens: Optional[Tenso
     dev = pose.device
     lens_args = () if lens is None else (_p(_lens_arg(lens, int(pose.shape[0]))),)
     if draw_seed:
-        seed = torch.randint(0, 2 ** 31 - 1, (1,), dtype=torch.int32, device=dev)
+        seed = seed_word(dev)
     if pix is not None and pix.numel() != n:
         raise _lib.McnerfError(f"pix must hold seg_start[-1] = {n} ids, got {pix.numel()}")
     if images is not None and (images.dim() != 3 or images.shape[0] != pose.shape[0] or images.shape[1] != H * W):
@@ -553,16 +559,22 @@ def composite_bwd(sig_rgb: Tensor, zgrid: Tensor, jitter: Optional[Tensor], eps:
     return (d, gmax) if want_gmax else d
 
 
+def _list_buffers(N: int, S: int, prefill: bool, idx: Optional[Tensor], dev):
+    """What an ordered (ray, sample) list over [N, S] needs (csrc/mcnerf_compact.h): idx [N*S,2] (or the caller's), count [1], the two
+    [N] workspaces and, with `prefill`, the [N,S,4] output the count kernel fills with the defaults."""
+    if idx is None:
+        idx = torch.empty(N * S, 2, dtype=torch.int32, device=dev)
+    count = torch.empty(1, dtype=torch.int32, device=dev)
+    rc = torch.empty(N, dtype=torch.int32, device=dev)
+    ro = torch.empty(N, dtype=torch.int32, device=dev)
+    return idx, count, rc, ro, torch.empty(N, S, 4, dtype=torch.float32, device=dev) if prefill else None
+
+
 def select_fine(w_sel: Tensor, wmax: Tensor, thresh: float, scale: int, sigma_default: float,
                 prefill: bool = True):
     """-> idx [N*Sc*scale,2] int32 (first *count rows valid), count [1] int32, out_f [N,Sf,4] | None"""
     N, Sc = w_sel.shape
-    dev = w_sel.device
-    idx = torch.empty(N * Sc * scale, 2, dtype=torch.int32, device=dev)
-    count = torch.empty(1, dtype=torch.int32, device=dev)
-    rc = torch.empty(N, dtype=torch.int32, device=dev)
-    ro = torch.empty(N, dtype=torch.int32, device=dev)
-    out_f = torch.empty(N, Sc * scale, 4, dtype=torch.float32, device=dev) if prefill else None
+    idx, count, rc, ro, out_f = _list_buffers(N, Sc * scale, prefill, None, w_sel.device)
     _lib.call("mcnerf_select_fine", _p(w_sel), _p(wmax, torch.int32), float(thresh), N, Sc, scale,
               float(sigma_default), _p(rc, torch.int32), _p(ro, torch.int32), _p(idx, torch.int32),
               _p(count, torch.int32), _p(out_f), _stream())
@@ -622,15 +634,9 @@ def voxel_select(grid: VoxelGrid, thresh: float, rays_o: Tensor, rays_d: Tensor,
     pairs whose cell holds a sigma > thresh, and the (sigma_default, 1, 1, 1) prefill of the coarse pass.  No host synchronisation.
     `idx`: the caller's own list buffer (rows beyond *count are left as they are)."""
     N, Sc = rays_d.shape[0], zgrid.numel()
-    dev = rays_d.device
-    if idx is None:
-        idx = torch.empty(N * Sc, 2, dtype=torch.int32, device=dev)
-    elif idx.numel() < N * Sc * 2:
+    if idx is not None and idx.numel() < N * Sc * 2:
         raise _lib.McnerfError(f"voxel_select: idx must hold N * Sc = {N * Sc} pairs, got {tuple(idx.shape)}")
-    count = torch.empty(1, dtype=torch.int32, device=dev)
-    rc = torch.empty(N, dtype=torch.int32, device=dev)
-    ro = torch.empty(N, dtype=torch.int32, device=dev)
-    out_c = torch.empty(N, Sc, 4, dtype=torch.float32, device=dev) if prefill else None
+    idx, count, rc, ro, out_c = _list_buffers(N, Sc, prefill, idx, rays_d.device)
     _lib.call("mcnerf_voxel_select", _p(grid.vox), *grid.geom, float(thresh), _p(rays_o), _p(rays_d), _p(zgrid), _p(jitter), N, Sc,
               float(sigma_default), _p(rc, torch.int32), _p(ro, torch.int32), _p(idx, torch.int32), _p(count, torch.int32), _p(out_c), _stream())
     return idx, count, out_c

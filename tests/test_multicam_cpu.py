@@ -209,6 +209,24 @@ def test_ray_preamble_expressions_are_written_once(what, text):
     assert len(hits) == 1 and sum(hits.values()) == 1, (what, hits)
 
 
+def test_compaction_maxblend_and_radam_element_are_written_once():
+    """The two ordered lists share one count body and one write body (mcnerf_compact.h), the voxel grid and the error map one
+    max / blend pair (mcnerf_maxkey.h), the dense and the row-lazy RAdam one element update (mcnerf_optim_rows.h)."""
+    src = _csrc()
+    for text, owner in (("atomicExch(", "mcnerf_maxkey.h"), ("sqrtf(vi)", "mcnerf_optim_rows.h")):
+        assert [f for f, s in src.items() if text in s] == [owner], text
+    for body in ("mcn_compact_count", "mcn_compact_write"):
+        assert [f for f, s in src.items() if f"void {body}(" in s] == ["mcnerf_compact.h"], body
+        assert sorted(f for f, s in src.items() if f"{body}<" in s) == ["select.hip", "voxel.hip"], body
+    for f, names in (("select.hip", ("select_count_kernel", "select_write_kernel")), ("voxel.hip", ("voxel_count_kernel", "voxel_write_kernel", "voxel_max_kernel", "voxel_blend_kernel")),
+                     ("errmap.hip", ("errmap_max_kernel", "errmap_blend_kernel"))):
+        for name in names:
+            m = re.search(r"__global__ __launch_bounds__\(256\) void " + name + r"\(([^)]*)\) \{\n(.*?)\n\}\n", src[f], flags=re.S)
+            assert m and len(m.group(2).split("\n")) == 1 and "mcn_c" in m.group(2), (f, name)
+    for f in ("optim.hip", "optim_rows.hip"):
+        assert src[f].count("mcn_radam_element(") == 1, f
+
+
 def test_ray_batch_entry_points_stay_in_their_files_as_thin_kernels():
     src = _csrc()
     for f, names in (("rays.hip", ("ray_batch_fwd_kernel", "ray_batch_bwd_kernel")), ("lens.hip", ("lens_ray_batch_fwd_kernel", "lens_ray_batch_bwd_kernel"))):

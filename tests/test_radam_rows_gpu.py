@@ -1,7 +1,7 @@
 """The row-lazy RAdam (`"lazy_rows": True` param groups; csrc/optim_rows.hip) on the GPU.
 
 Shapes, schedules and runners are tests/radam_rows_cases.py's (its docstring lists the cases).  The equalities are torch.equal: the
-kernel's element arithmetic is radam_kernel's expression for expression, a wave owns its row, and nothing is atomic.  Against the host
+kernel's element arithmetic is mcn_radam_element (csrc/mcnerf_optim_rows.h), the function radam_kernel calls, a wave owns its row, and nothing is atomic.  Against the host
 path the gate is the 1e-6 of test_a_ops_gpu.py::test_fused_radam_matches_host_arithmetic (the host forms step_size * lr in double)."""
 import pytest
 import torch
