@@ -38,6 +38,13 @@ extern "C" {
 #endif
 
 #define MCNERF_ABI_VERSION 7      /* 7: per-ray depth rows (z_stride) and mcnerf_sample_pdf; 6: dtype 3 (f16x3h) of the register-chain entry points */
+#define MCNERF_SKIP_MASK 256      /* `skip` >= this: the mask form of the conventions above */
+
+/* Marks a pointer parameter that addresses HOST memory where its type alone does not say so (the segment tables, the values of
+ * mcnerf_upload_f32); long long* and T* const* parameters are host arrays by their type.  Expands to nothing.  The Python binding is
+ * derived from this header (mc_nerf_amd/_lib.py): it checks a tensor's dtype against a device pointer's element type and refuses a
+ * tensor at a host position. */
+#define MCNERF_HOST
 
 int mcnerf_abi_version(void);
 const char* mcnerf_last_error(void);
@@ -101,7 +108,7 @@ int mcnerf_encode(const float* x, const float* barf_w, int n, int n_freqs, float
  * one-wave kernel stores them to `dst` (device).  For the per-step host scalars of the train step (the ten BARF weights of
  * model/net_block.py:26-29, evaluated in fp32 on the host exactly as the reference does): a pageable hipMemcpy would block
  * the host until every kernel queued before it has finished, i.e. serialise host and device once per step. */
-int mcnerf_upload_f32(float* dst, const float* host_vals, int n, void* stream);
+int mcnerf_upload_f32(float* dst, MCNERF_HOST const float* host_vals, int n, void* stream);
 int mcnerf_mlp_apply(int depth, int width, int skip, const float* params, const float* packed, const float* x_enc,
                      const float* dirs, int n, float* out, void* stream);
 
@@ -232,6 +239,7 @@ int mcnerf_select_fine(const float* w_sel, const uint32_t* wmax_bits, float thre
  *   search ind = #{cdf <= u} with denom = pdf[ind-1] (the bin's OWN pdf entry, not a difference of CDF entries; < 1e-5 -> 1);
  *   z_all [N, Sc+I] = sort(zc ++ zs) ascending.  w [N,Sc] are the coarse selection weights (w_sel of mcnerf_composite_fwd),
  *   u [N,I] in any order.  3 <= Sc, 1 <= I, Sc + I <= 1024.  Not differentiated (z_all is a constant of the fine pass). */
+#define MCNERF_PDF_MAX_SAMPLES 1024      /* bound on Sc + I */
 int mcnerf_sample_pdf(const float* w, const float* zgrid, const float* jitter, const float* u, int N, int Sc, int I,
                       float* z_all, void* stream);
 
@@ -250,6 +258,7 @@ int mcnerf_sample_pdf(const float* w, const float* zgrid, const float* jitter, c
  * mcnerf_voxel_select: every (ray, sample) pair with vox[cell] > thresh, in torch.nonzero (row-major) order, into idx [N*Sc] (int32
  * pairs) with the total in *count (0 is legal and leaves idx untouched); out_c [N,Sc,4] (or NULL) is pre-filled with
  * (sigma_default, 1, 1, 1).  ray_counts / ray_offsets: int32 [N] workspaces.  No atomic decides a position. */
+#define MCNERF_VOXEL_MAX_G 1024      /* bound on G */
 int mcnerf_voxel_select(const float* vox, int G, float bmin, float s, float thresh, const float* rays_o, const float* rays_d,
                         const float* zgrid, const float* jitter, int N, int Sc, float sigma_default, int32_t* ray_counts,
                         int32_t* ray_offsets, int32_t* idx, int32_t* count, float* out_c, void* stream);
@@ -308,13 +317,14 @@ int mcnerf_gather_gt(const uint8_t* image, int channels, const int64_t* pix, int
  *   ray    rays_d / rays_o [n,3] from pose[seg_cam[k]], kinv[seg_cam[k]]: the bits of mcnerf_raygen_fwd for that camera and pixel;
  *   gt     images NULL: not written (gt may be NULL);  otherwise images [C, H*W, channels] uint8 -> gt [n,3], the bits of
  *          mcnerf_gather_gt on images[seg_cam[k]]. */
-int mcnerf_ray_batch_fwd(const float* pose, const float* kinv, int C, const int32_t* seg_cam, const int32_t* seg_start, int K,
+#define MCNERF_MULTICAM_MAXSEG 64      /* bound on K, here and in every other entry point that takes a segment table */
+int mcnerf_ray_batch_fwd(const float* pose, const float* kinv, int C, MCNERF_HOST const int32_t* seg_cam, MCNERF_HOST const int32_t* seg_start, int K,
                          int n, int H, int W, const int64_t* pix_in, const uint32_t* seed, const uint8_t* images, int channels,
                          int64_t* pix_out, float* rays_d, float* rays_o, float* gt, void* stream);
 /* Backward of the above (autograd through model/mc_nerf.py:124-145, 327-345): d_rays_d, d_rays_o [n,3] and the forward's pixels
  * pix [n] -> ACCUMULATES into d_pose [C,3,4] and d_kinv [C,3,3] (caller zeroes them: rows of cameras not in the table stay zero, a
  * camera listed in two segments receives the sum).  mcnerf_raygen_bwd's per-ray terms, summed in another order (float atomics). */
-int mcnerf_ray_batch_bwd(const float* pose, const float* kinv, int C, const int32_t* seg_cam, const int32_t* seg_start, int K,
+int mcnerf_ray_batch_bwd(const float* pose, const float* kinv, int C, MCNERF_HOST const int32_t* seg_cam, MCNERF_HOST const int32_t* seg_start, int K,
                          int n, int W, const int64_t* pix, const float* d_rays_d, const float* d_rays_o,
                          float* d_pose, float* d_kinv, void* stream);
 
@@ -333,10 +343,10 @@ int mcnerf_ray_batch_bwd(const float* pose, const float* kinv, int C, const int3
  * mcnerf_lens_ray_batch_bwd: mcnerf_ray_batch_bwd plus `lens` and d_lens [C,2]; ACCUMULATES into d_pose, d_kinv, d_lens (caller zeroes
  *   them).  The root is differentiated implicitly at the final radius, not through the iterations.
  * Both refuse, before any device work, everything mcnerf_ray_batch_fwd / _bwd refuse and a null lens / d_lens. */
-int mcnerf_lens_ray_batch_fwd(const float* pose, const float* kinv, const float* lens, int C, const int32_t* seg_cam, const int32_t* seg_start,
+int mcnerf_lens_ray_batch_fwd(const float* pose, const float* kinv, const float* lens, int C, MCNERF_HOST const int32_t* seg_cam, MCNERF_HOST const int32_t* seg_start,
                               int K, int n, int H, int W, const int64_t* pix_in, const uint32_t* seed, const uint8_t* images, int channels,
                               int64_t* pix_out, float* rays_d, float* rays_o, float* gt, void* stream);
-int mcnerf_lens_ray_batch_bwd(const float* pose, const float* kinv, const float* lens, int C, const int32_t* seg_cam, const int32_t* seg_start,
+int mcnerf_lens_ray_batch_bwd(const float* pose, const float* kinv, const float* lens, int C, MCNERF_HOST const int32_t* seg_cam, MCNERF_HOST const int32_t* seg_start,
                               int K, int n, int W, const int64_t* pix, const float* d_rays_d, const float* d_rays_o,
                               float* d_pose, float* d_kinv, float* d_lens, void* stream);
 
@@ -399,7 +409,7 @@ int mcnerf_scale3(float* a, int na, float* b, int nb, float* c, int nc, const fl
 #define MCNERF_TRAIN_LOSS_CALIB_WS 896
 int mcnerf_train_loss_calib(const float* pd, const float* pt_gt, int np, int H, int W, int normalise,
                             const float* rgb_c, const float* rgb_f, const float* gt, int n,
-                            const float* color_w, int C, const int32_t* seg_cam, const int32_t* seg_start, int K, float reg_lambda,
+                            const float* color_w, int C, MCNERF_HOST const int32_t* seg_cam, MCNERF_HOST const int32_t* seg_start, int K, float reg_lambda,
                             float* out, float* d_pd, float* d_c, float* d_f, float* d_color, float* partials, void* stream);
 
 /* ---- Error-guided pixel sampling (this build's own sys_param key "pixel_sampler" = "error"; the default, "uniform", runs
@@ -432,9 +442,10 @@ int mcnerf_train_loss_calib(const float* pd, const float* pt_gt, int np, int H, 
  *
  * Refused ahead of any device work: K < 1, K > 64, a camera id outside [0, C), a decreasing seg_start, seg_start[0] != 0,
  * seg_start[K] != n, tile < 1, H W > 2^26, uniform_frac (beta, one_minus_beta) outside [0, 1] or NaN, a null pointer. */
-int mcnerf_errmap_sample(const float* err, int C, int H, int W, int tile, const int32_t* seg_cam, const int32_t* seg_start, int K,
+#define MCNERF_ERRMAP_MAX_PIXELS 67108864      /* bound on H W: 2^26 */
+int mcnerf_errmap_sample(const float* err, int C, int H, int W, int tile, MCNERF_HOST const int32_t* seg_cam, MCNERF_HOST const int32_t* seg_start, int K,
                          int n, float uniform_frac, const float* u, uint64_t* cdf, int64_t* pix, void* stream);
-int mcnerf_errmap_update(float* err, uint32_t* scratch, int C, int H, int W, int tile, const int32_t* seg_cam, const int32_t* seg_start,
+int mcnerf_errmap_update(float* err, uint32_t* scratch, int C, int H, int W, int tile, MCNERF_HOST const int32_t* seg_cam, MCNERF_HOST const int32_t* seg_start,
                          int K, int n, const int64_t* pix, const float* rgb, const float* gt, float beta, float one_minus_beta,
                          void* stream);
 

@@ -1,111 +1,109 @@
-"""ctypes binding of libmcnerf.so (the C ABI declared in include/mcnerf.h).
+"""ctypes binding of libmcnerf.so, DERIVED from include/mcnerf.h, the one statement of the C ABI.
 
-There is deliberately NO fallback: if the HIP library is missing or does not load, importing the
-symbols raises, and every op in ``mc_nerf_amd.ops`` fails loudly.
+The header is parsed once at import (`parse_header`): every prototype gives an entry point's ctypes signature (`SIGNATURES`), its
+parameter names and, per pointer, the dtype a tensor handed to it must have (`PARAMS`); every decimal `#define MCNERF_*` gives a
+constant (`DEFINES`).  A type the parser does not know is an import error that names the prototype: nothing is guessed.
+
+There is deliberately NO fallback: if the HIP library is missing or does not load, `lib()` raises and every op in ``mc_nerf_amd.ops`` fails loudly.
 """
 import ctypes
 import os
+import re
 from ctypes import c_char_p, c_float, c_int, c_longlong, c_void_p
 
 # torch ships its own HIP runtime (torch/lib/libamdhip64.so).  It MUST be in the process before
 # libmcnerf.so is loaded, so that the library's libamdhip64 dependency resolves to the same runtime
 # instance that owns torch's streams and allocations (two runtimes in one process do not share devices).
-import torch  # noqa: F401
+import torch
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # MCNERF_LIB selects another build of the same ABI, e.g. the parent commit's
 LIB_PATH = os.environ.get("MCNERF_LIB") or os.path.join(_HERE, "libmcnerf.so")
-ABI_VERSION = 7
-
-_P = c_void_p
-_I = c_int
-_L = c_longlong
-
-# name -> (restype, argtypes); mirrors include/mcnerf.h line by line
-SIGNATURES = {
-    "mcnerf_abi_version": (_I, []),
-    "mcnerf_last_error": (c_char_p, []),
-    "mcnerf_param_count": (_L, [_I, _I, _I]),
-    "mcnerf_packed_count": (_L, [_I, _I, _I]),
-    "mcnerf_tile_rows": (_I, [_I]),
-    "mcnerf_param_offsets": (_I, [_I, _I, _I, _P]),
-    "mcnerf_pack_weights": (_I, [_I, _I, _I, _P, _P, _P]),
-    "mcnerf_raygen_fwd": (_I, [_P, _P, _P, _I, _I, _P, _P, _P]),
-    "mcnerf_raygen_bwd": (_I, [_P, _P, _P, _I, _I, _P, _P, _P, _P, _P]),
-    "mcnerf_mlp_fwd": (_I, [_I, _I, _I, _P, _P, _P, _P, _P, _I, _P, _P, _P, _P, _I, _I, _I, _P, _P, _L, _P, _P, _P, _P]),
-    "mcnerf_encode": (_I, [_P, _P, _I, _I, _P, _P]),
-    "mcnerf_upload_f32": (_I, [_P, _P, _I, _P]),
-    "mcnerf_train_loss": (_I, [_P, _P, _I, _I, _I, _I, _P, _P, _P, _I, _P, _P, _P, _P, _P]),
-    "mcnerf_train_loss_calib": (_I, [_P, _P, _I, _I, _I, _I, _P, _P, _P, _I, _P, _I, _P, _P, _I, c_float, _P, _P, _P, _P, _P, _P, _P]),
-    "mcnerf_errmap_sample": (_I, [_P, _I, _I, _I, _I, _P, _P, _I, _I, c_float, _P, _P, _P, _P]),
-    "mcnerf_errmap_update": (_I, [_P, _P, _I, _I, _I, _I, _P, _P, _I, _I, _P, _P, _P, c_float, c_float, _P]),
-    "mcnerf_scale3": (_I, [_P, _I, _P, _I, _P, _I, _P, _P]),
-    "mcnerf_sample_perm": (_I, [_P, ctypes.c_longlong, _I, _P, _P]),
-    "mcnerf_mlp_apply": (_I, [_I, _I, _I, _P, _P, _P, _P, _I, _P, _P]),
-    "mcnerf_encode_bwd": (_I, [_P, _P, _I, _I, _P, _P, _P]),
-    "mcnerf_sync_finish": (_I, [_P, _L, _I, _I, _P, _P, _P]),
-    "mcnerf_mlp_apply_save": (_I, [_I, _I, _I, _P, _P, _P, _P, _I, _P, _P, _L, _P, _P, _P, _P]),
-    "mcnerf_mlp_apply_bwd": (_I, [_I, _I, _I, _P, _P, _P, _P, _I, _P, _P, _P, _L, _P, _P, _P, _P, _P, _P, _P]),
-    "mcnerf_mlp_bwd": (_I, [_I, _I, _I, _P, _P, _P, _P, _P, _I, _P, _P, _P, _P, _I, _I, _I, _P, _P, _P, _L, _P, _P,
-                            _P, _P, _P, _P, _P]),
-    "mcnerf_mlp_dw": (_I, [_I, _I, _I, _P, _I, _P, _P, _P, _P, _L, _P, _P]),
-    "mcnerf_packed_bytes_16": (_L, [_I, _I, _I, _I, _I]),
-    "mcnerf_pack_weights_16": (_I, [_I, _I, _I, _P, _P, _P, _I, _P, _P]),
-    "mcnerf_ws_bytes_16": (_L, [_I, _I, _I, _L, _I]),
-    "mcnerf_mlp_fwd_16": (_I, [_I, _I, _I, _I, _P, _P, _P, _P, _P, _I, _P, _P, _P, _P, _I, _I, _I, _P, _P, _L, _P, _P, _P, _P]),
-    "mcnerf_mlp_bwd_16": (_I, [_I, _I, _I, _I, _P, _P, _P, _P, _P, _I, _P, _P, _P, _P, _I, _I, _I, _P, _P, _P, _L, _P, _P,
-                               _P, _P, _P, _P, _P, _P]),
-    "mcnerf_mlp_dw_16": (_I, [_I, _I, _I, _I, _P, _I, _P, _P, _P, _P, _L, _P, _P, _P]),
-    "mcnerf_composite_fwd": (_I, [_P, _P, _P, _I, _P, _P, _P, _I, _I, _I, _P, _P, _P, _P, _P, _P]),
-    "mcnerf_composite_bwd": (_I, [_P, _P, _I, _P, _P, _P, _I, _I, _I, _P, _P, _P]),
-    "mcnerf_select_fine": (_I, [_P, _P, c_float, _I, _I, _I, c_float, _P, _P, _P, _P, _P, _P]),
-    "mcnerf_sample_pdf": (_I, [_P, _P, _P, _P, _I, _I, _I, _P, _P]),
-    "mcnerf_voxel_select": (_I, [_P, _I, c_float, c_float, c_float, _P, _P, _P, _P, _I, _I, c_float, _P, _P, _P, _P, _P, _P]),
-    "mcnerf_voxel_update": (_I, [_P, _P, _I, c_float, c_float, c_float, c_float, _P, _P, _P, _P, _I, _I, _P, _P, _I, _P, _P]),
-    "mcnerf_voxel_query": (_I, [_P, _I, c_float, c_float, _P, _I, _P, _P]),
-    "mcnerf_voxel_update_points": (_I, [_P, _P, _I, c_float, c_float, c_float, c_float, _P, _P, _I, _P]),
-    "mcnerf_cap_gather": (_I, [_P, _P, _I, _P, _P, _P]),
-    "mcnerf_cap_ws_words": (_L, []),
-    "mcnerf_cap_random": (_I, [_P, _P, _I, _I, _P, _P, _P, _P, _P]),
-    "mcnerf_gather_gt": (_I, [_P, _I, _P, _I, _P, _P]),
-    "mcnerf_ray_batch_fwd": (_I, [_P, _P, _I, _P, _P, _I, _I, _I, _I, _P, _P, _P, _I, _P, _P, _P, _P, _P]),
-    "mcnerf_ray_batch_bwd": (_I, [_P, _P, _I, _P, _P, _I, _I, _I, _P, _P, _P, _P, _P, _P]),
-    "mcnerf_lens_ray_batch_fwd": (_I, [_P, _P, _P, _I, _P, _P, _I, _I, _I, _I, _P, _P, _P, _I, _P, _P, _P, _P, _P]),
-    "mcnerf_lens_ray_batch_bwd": (_I, [_P, _P, _P, _I, _P, _P, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P]),
-    "mcnerf_camera_fwd": (_I, [_P, _P, _P, _P, _P, _P, _I, _I, _I, _P, _P, _P, _P, _P, _P, _I, _P, _P, _P]),
-    "mcnerf_camera_bwd": (_I, [_P, _P, _P, _P, _P, _P, _I, _I, _I, _P, _P, _P, _P, _P, _P, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
-    "mcnerf_reproj_loss_fwd": (_I, [_P, _P, _I, _I, _I, _P, _P]),
-    "mcnerf_reproj_loss_bwd": (_I, [_P, _P, _I, _I, _I, _P, _P, _P]),
-    "mcnerf_radam_step": (_I, [_I, _P, _P, _P, _P, _P, c_float, c_float, c_float, c_float, c_float, c_float, _I, _P, _I, _P]),
-    "mcnerf_radam_rows_step": (_I, [_I, _P, _P, _P, _P, _P, _P, _P, c_float, c_float, c_float, c_float, c_float, _P, _I, _P, _I, _P]),
-}
-
-_lib = None
+HOST = "host table"      # element class of a pointer into HOST memory: long long*, T* const*, and what the header marks MCNERF_HOST
+BY_VALUE = {"int": c_int, "long long": c_longlong, "float": c_float}
+# element type of a pointer -> dtype of the device tensor it takes (the unsigned words travel in signed tensors, void* is bytes)
+ELEMENT = {"float": torch.float32, "int32_t": torch.int32, "uint32_t": torch.int32, "int64_t": torch.int64, "uint64_t": torch.int64,
+           "uint8_t": torch.uint8, "void": torch.uint8, "long long": HOST}
 
 
 class McnerfError(RuntimeError):
     pass
 
 
+def _classify(ctype):
+    """C parameter type -> (ctypes type, element class: None by value, a torch dtype, or HOST); raises on any other type."""
+    host = ctype.lstrip().startswith("MCNERF_HOST ")
+    t = " ".join(re.findall(r"\w+|\S", ctype)).removeprefix("MCNERF_HOST ").removeprefix("const ")
+    if not host and t in BY_VALUE:
+        return BY_VALUE[t], None
+    base, table = re.fullmatch(r"(long long|\w+) \*( const \*)?", t).groups()
+    return c_void_p, HOST if ELEMENT[base] is HOST or host or table else ELEMENT[base]
+
+
+def parse_header(text):
+    """Header text -> ({function: (restype, ((parameter name, C type, ctypes type, element class), ...))}, {MCNERF_* define: int})."""
+    text = re.sub(r"//[^\n]*", "", re.sub(r"/\*.*?\*/", "", text, flags=re.S))
+    defines = {k: int(v) for k, v in re.findall(r"^[ \t]*#[ \t]*define[ \t]+(MCNERF_\w+)[ \t]+(\d+)[ \t]*$", text, flags=re.M)}
+    code = re.sub(r"^[ \t]*#[^\n]*", "", text, flags=re.M)
+    functions = {}
+    for ret, name, args in re.findall(r"([\w\s*]+?)\b(mcnerf_\w+)\s*\(([^()]*)\)\s*;", code):
+        try:
+            restype = {"const char *": c_char_p, **BY_VALUE}[" ".join(re.findall(r"\w+|\*", ret))]
+            params = []
+            for arg in ([] if args.strip() in ("", "void") else args.split(",")):
+                ctype, pname = re.fullmatch(r"\s*(.*[\s*])(\w+)\s*", arg, flags=re.S).groups()
+                params.append((pname, " ".join(ctype.split()), *_classify(ctype)))
+        except (KeyError, AttributeError):
+            raise McnerfError(f"include/mcnerf.h: {name}: '{ret.strip()}' or a parameter of ({' '.join(args.split())}) has a type the binding does not know") from None
+        functions[name] = (restype, tuple(params))
+    unparsed = set(re.findall(r"\b(mcnerf_\w+)\s*\(", code)) - set(functions)
+    if unparsed:
+        raise McnerfError(f"include/mcnerf.h: cannot parse the prototype of {sorted(unparsed)}")
+    return functions, defines
+
+
+with open(os.path.join(_HERE, "csrc", "..", "..", "include", "mcnerf.h")) as _f:      # (the path csrc/api.hip includes it by)
+    PARAMS, DEFINES = parse_header(_f.read())
+SIGNATURES = {name: (res, [p[2] for p in params]) for name, (res, params) in PARAMS.items()}      # name -> (restype, argtypes)
+ABI_VERSION = DEFINES["MCNERF_ABI_VERSION"]
+
+
+def _pointer(fn, pname, ctype, want):
+    """Converter of a tensor at one pointer position -> its checked device address."""
+    def conv(a):
+        if want is HOST:
+            raise McnerfError(f"{fn}: {pname} ({ctype}) is a host array: it takes a ctypes array, not a tensor")
+        if not a.is_cuda:
+            raise McnerfError(f"{fn}: {pname} must be a CUDA/HIP tensor (no CPU fallback), got one on {a.device}")
+        if a.dtype != want:
+            raise McnerfError(f"{fn}: {pname} ({ctype}) takes a {want} tensor, got {a.dtype}")
+        if not a.is_contiguous():
+            raise McnerfError(f"{fn}: {pname} must be contiguous")
+        return a.data_ptr()
+    return conv
+
+
+# per entry point one converter per position (None: by value); whatever is not a tensor goes to ctypes as it is: None (NULL), raw
+# addresses (data_ptr(), the stream), ctypes arrays and casts
+_CONVERTERS = {name: tuple(cls and _pointer(name, pname, ctype, cls) for pname, ctype, _, cls in params) for name, (_, params) in PARAMS.items()}
+_lib = None
+
+
 def lib():
-    """Returns the loaded library; raises McnerfError if it is missing (build it with
-    ``python -m mc_nerf_amd.build``)."""
+    """Returns the loaded library; raises McnerfError if it is missing (build it with ``python -m mc_nerf_amd.build``)."""
     global _lib
     if _lib is not None:
         return _lib
     if not os.path.exists(LIB_PATH):
-        raise McnerfError(f"{LIB_PATH} not found: the HIP extension is required (python -m mc_nerf_amd.build); "
-                          "there is no CPU fallback")
+        raise McnerfError(f"{LIB_PATH} not found: the HIP extension is required (python -m mc_nerf_amd.build); there is no CPU fallback")
     try:
         l = ctypes.CDLL(LIB_PATH)
     except OSError as e:  # pragma: no cover
         raise McnerfError(f"cannot load {LIB_PATH}: {e}") from e
     for name, (res, args) in SIGNATURES.items():
-        try:
-            f = getattr(l, name)
-        except AttributeError as e:
-            raise McnerfError(f"{LIB_PATH} does not export {name}") from e
-        f.restype, f.argtypes = res, args
+        if not hasattr(l, name):
+            raise McnerfError(f"{LIB_PATH} does not export {name}")
+        getattr(l, name).restype, getattr(l, name).argtypes = res, args
     if l.mcnerf_abi_version() != ABI_VERSION:
         raise McnerfError("libmcnerf.so ABI version mismatch; rebuild")
     _lib = l
@@ -113,7 +111,8 @@ def lib():
 
 
 def call(name, *args):
-    """Calls a status-returning entry point and raises with the library's message on failure."""
+    """Calls a status-returning entry point (tensor arguments are first checked against the header) and raises with the library's message on failure."""
+    args = [c(a) if c and isinstance(a, torch.Tensor) else a for c, a in zip(_CONVERTERS[name], args, strict=True)]
     l = lib()
     rc = getattr(l, name)(*args)
     if rc != 0:

@@ -13,6 +13,12 @@
 #include <stdio.h>
 #include <string.h>
 
+// the limits the public header states are the kernels' own
+static_assert(MCNERF_SKIP_MASK == MCN_SKIP_MASK, "include/mcnerf.h: MCNERF_SKIP_MASK");
+static_assert(MCNERF_MULTICAM_MAXSEG == MCN_MULTICAM_MAXSEG, "include/mcnerf.h: MCNERF_MULTICAM_MAXSEG");
+static_assert(MCNERF_PDF_MAX_SAMPLES == MCN_PDF_MAX_SAMPLES, "include/mcnerf.h: MCNERF_PDF_MAX_SAMPLES");
+static_assert(MCNERF_TRAIN_LOSS_OUT == 4 + MCN_LOSS_BLOCKS, "include/mcnerf.h: MCNERF_TRAIN_LOSS_OUT");
+
 static thread_local char g_err[512] = "";
 
 static int fail(const char* where, const char* what) {
@@ -213,7 +219,7 @@ int mcnerf_train_loss_calib(const float* pd, const float* pt_gt, int np, int H, 
     return check("mcnerf_train_loss_calib", mcn_launch_train_loss_calib(a, t, (hipStream_t)stream));
 }
 // the error map's geometry (as vox_ok for the voxel grid): a tile of at least one pixel, an image of at most 2^26 pixels
-static bool err_ok(int H, int W, int tile) { return H > 0 && W > 0 && tile >= 1 && (long long)H * W <= (1ll << 26); }
+static bool err_ok(int H, int W, int tile) { return H > 0 && W > 0 && tile >= 1 && (long long)H * W <= MCNERF_ERRMAP_MAX_PIXELS; }
 // The error-guided pixel sampler (errmap.hip): everything is checked before any HIP call, as for mcnerf_ray_batch_fwd.
 int mcnerf_errmap_sample(const float* err, int C, int H, int W, int tile, const int32_t* seg_cam, const int32_t* seg_start, int K,
                          int n, float uniform_frac, const float* u, uint64_t* cdf, int64_t* pix, void* stream) {
@@ -441,7 +447,7 @@ int mcnerf_sample_pdf(const float* w, const float* zgrid, const float* jitter, c
     return check("mcnerf_sample_pdf", mcn_launch_sample_pdf(a, (hipStream_t)stream));
 }
 // the voxel grid's geometry: 2 <= G <= 1024 cells per axis, a finite positive cells-per-unit scale
-static bool vox_ok(int G, float bmin, float s) { return G >= 2 && G <= 1024 && bmin == bmin && s > 0.f && s <= 3.0e38f; }
+static bool vox_ok(int G, float bmin, float s) { return G >= 2 && G <= MCNERF_VOXEL_MAX_G && bmin == bmin && s > 0.f && s <= 3.0e38f; }
 int mcnerf_voxel_select(const float* vox, int G, float bmin, float s, float thresh, const float* rays_o, const float* rays_d,
                         const float* zgrid, const float* jitter, int N, int Sc, float sigma_default, int32_t* ray_counts,
                         int32_t* ray_offsets, int32_t* idx, int32_t* count, float* out_c, void* stream) {

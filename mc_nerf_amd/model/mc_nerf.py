@@ -132,7 +132,7 @@ class NeRF_Model(nn.Module):
     def _voxel_settings(self, sys_param):
         """Reads and validates the keys of "voxel" mode (a ValueError names the key) -> the RenderSettings fields."""
         number = lambda key, default: _number_key(sys_param, key, default, finite=True)
-        G = _int_key(sys_param, "grid_nerf", None, 2, 1024)
+        G = _int_key(sys_param, "grid_nerf", None, 2, ops.VOXEL_MAX_G)
         bmin, bmax = number("boader_min", None), number("boader_max", None)
         if not bmin < bmax:
             raise ValueError(f"boader_min must be below boader_max, got {bmin!r} and {bmax!r}")

@@ -1,8 +1,9 @@
 """Tensor-level wrappers over the C ABI (include/mcnerf.h).
 
 PyTorch is plumbing here: it owns device memory and the current HIP stream; every function below
-checks its tensors (device, dtype, contiguity), passes raw pointers to libmcnerf.so and returns
-tensors.  All launches go to ``torch.cuda.current_stream()``.  There is no CPU path.
+hands its tensors to ``_lib.call``, which checks them against the header's parameters (device, dtype,
+contiguity) and passes raw pointers to libmcnerf.so, and returns tensors.  All launches go to
+``torch.cuda.current_stream()``.  There is no CPU path.
 """
 from __future__ import annotations
 
@@ -16,7 +17,15 @@ from . import _lib
 Tensor = torch.Tensor
 
 
-SKIP_MASK = 256          # MCN_SKIP_MASK: skip >= 256 = (bit mask of skip layers) << 8 (include/mcnerf.h)
+# the limits and buffer sizes include/mcnerf.h defines
+SKIP_MASK = _lib.DEFINES["MCNERF_SKIP_MASK"]                        # skip >= 256 = (bit mask of skip layers) << 8
+MULTICAM_MAXSEG = _lib.DEFINES["MCNERF_MULTICAM_MAXSEG"]            # segments (cameras) of one step
+PDF_MAX_SAMPLES = _lib.DEFINES["MCNERF_PDF_MAX_SAMPLES"]            # bound on Sc + n_importance of sample_pdf
+VOXEL_MAX_G = _lib.DEFINES["MCNERF_VOXEL_MAX_G"]                    # cells per axis of the voxel sigma cache
+ERRMAP_MAX_PIXELS = _lib.DEFINES["MCNERF_ERRMAP_MAX_PIXELS"]        # H * W of one image: the integer tile weights then sum to <= 2^52, exact in a double
+TRAIN_LOSS_OUT = _lib.DEFINES["MCNERF_TRAIN_LOSS_OUT"]
+TRAIN_LOSS_CALIB_OUT = _lib.DEFINES["MCNERF_TRAIN_LOSS_CALIB_OUT"]
+TRAIN_LOSS_CALIB_WS = _lib.DEFINES["MCNERF_TRAIN_LOSS_CALIB_WS"]
 
 
 def skip_code(skips, depth: int, deg: int = 2, n_freqs: int = 10) -> int:
@@ -129,20 +138,9 @@ def tile_rows(width: int) -> int:
 
 
 # --------------------------------------------------------------------------- helpers
-def _p(t: Optional[Tensor], dtype=torch.float32):
-    if t is None:
-        return None
-    if not t.is_cuda:
-        raise _lib.McnerfError("mc_nerf_amd ops need CUDA/HIP tensors (no CPU fallback)")
-    if t.dtype != dtype:
-        raise _lib.McnerfError(f"expected {dtype}, got {t.dtype}")
-    if not t.is_contiguous():
-        raise _lib.McnerfError("tensor must be contiguous")
-    return t.data_ptr()
-
-
 def _stream():
-    return torch.cuda.current_stream().cuda_stream
+    # (before the runtime is up there is no device tensor: the null stream, and `_lib.call` refuses the host tensors it is handed)
+    return torch.cuda.current_stream().cuda_stream if torch.cuda.is_initialized() else 0
 
 
 def _depths(zgrid: Optional[Tensor], z_rows: Optional[Tensor], n_rays: int):
@@ -199,12 +197,12 @@ def pack_weights(net: Net, params: Tensor, packed=None, precision: str = "f32", 
             packed = torch.empty(int(l.mcnerf_packed_bytes_16(*net.triple, dt, 0)) + int(l.mcnerf_packed_bytes_16(*net.triple, dt, 1)),
                                  dtype=torch.uint8, device=params.device)
         pf, pb = packed16_split(net, packed, precision)
-        _lib.call("mcnerf_pack_weights_16", *net.triple, _p(params), _p(pf, torch.uint8), _p(pb, torch.uint8), DTYPE16[precision],
-                  _p(range_flags, torch.int32), _stream())
+        _lib.call("mcnerf_pack_weights_16", *net.triple, params, pf, pb, DTYPE16[precision],
+                  range_flags, _stream())
         return packed
     if packed is None:
         packed = torch.empty(packed_count(net), dtype=torch.float32, device=params.device)
-    _lib.call("mcnerf_pack_weights", *net.triple, _p(params), _p(packed), _stream())
+    _lib.call("mcnerf_pack_weights", *net.triple, params, packed, _stream())
     return packed
 
 
@@ -237,15 +235,15 @@ def raygen_fwd(pose: Tensor, kinv: Tensor, pix: Tensor, W: int) -> Tuple[Tensor,
     n = pix.numel()
     d = torch.empty(n, 3, dtype=torch.float32, device=pix.device)
     o = torch.empty_like(d)
-    _lib.call("mcnerf_raygen_fwd", _p(pose), _p(kinv), _p(pix, torch.int64), n, W, _p(d), _p(o), _stream())
+    _lib.call("mcnerf_raygen_fwd", pose, kinv, pix, n, W, d, o, _stream())
     return d, o
 
 
 def raygen_bwd(pose: Tensor, kinv: Tensor, pix: Tensor, W: int, d_d: Tensor, d_o: Tensor) -> Tuple[Tensor, Tensor]:
     z = torch.zeros(24, dtype=torch.float32, device=pix.device)          # (one fill for both accumulation targets)
     d_pose, d_kinv = z[:12].view(3, 4), z[12:21].view(3, 3)
-    _lib.call("mcnerf_raygen_bwd", _p(pose), _p(kinv), _p(pix, torch.int64), pix.numel(), W,
-              _p(d_d), _p(d_o), _p(d_pose), _p(d_kinv), _stream())
+    _lib.call("mcnerf_raygen_bwd", pose, kinv, pix, pix.numel(), W,
+              d_d, d_o, d_pose, d_kinv, _stream())
     return d_pose, d_kinv
 
 
@@ -289,17 +287,17 @@ def mlp_fwd(net: Net, params: Tensor, packed: Tensor, rays_o: Tensor, rays_d: Te
     zgrid, S, zs = _depths(zgrid, z_rows, n_rays)
     assert out.numel() == n_rays * S * 4
     if is16(precision):
-        _lib.call("mcnerf_mlp_fwd_16", *net.triple, DTYPE16[precision], _p(params), _p(packed16_split(net, packed, precision)[0], torch.uint8), _p(rays_o), _p(rays_d),
-                  _p(zgrid), zs, _p(jitter), _p(barf_w), _p(idx, torch.int32), _p(count, torch.int32), int(max_rows), n_rays, S,
-                  _p(out), _p(save.act, torch.uint8) if save else None, save.capacity if save else 0,
-                  _p(save.enc, torch.uint8) if save else None, _p(save.mask, torch.int32) if save else None,
-                  _p(save.sh, torch.uint8) if save else None, _stream())
+        _lib.call("mcnerf_mlp_fwd_16", *net.triple, DTYPE16[precision], params, packed16_split(net, packed, precision)[0], rays_o, rays_d,
+                  zgrid, zs, jitter, barf_w, idx, count, int(max_rows), n_rays, S,
+                  out, save.act if save else None, save.capacity if save else 0,
+                  save.enc if save else None, save.mask if save else None,
+                  save.sh if save else None, _stream())
         return
-    _lib.call("mcnerf_mlp_fwd", *net.triple, _p(params), _p(packed), _p(rays_o), _p(rays_d), _p(zgrid), zs,
-              _p(jitter), _p(barf_w), _p(idx, torch.int32), _p(count, torch.int32), int(max_rows), n_rays, S,
-              _p(out), _p(save.act) if save else None, save.capacity if save else 0,
-              _p(save.enc) if save else None, _p(save.sh) if save else None,
-              _p(save.mask, torch.int32) if save else None, _stream())
+    _lib.call("mcnerf_mlp_fwd", *net.triple, params, packed, rays_o, rays_d, zgrid, zs,
+              jitter, barf_w, idx, count, int(max_rows), n_rays, S,
+              out, save.act if save else None, save.capacity if save else 0,
+              save.enc if save else None, save.sh if save else None,
+              save.mask if save else None, _stream())
 
 
 def seed_word(device) -> Tensor:
@@ -314,11 +312,8 @@ def sample_perm(n: int, batch: int, device, seed: Optional[Tensor] = None) -> Te
     if seed is None:
         seed = seed_word(device)
     out = torch.empty(batch, dtype=torch.int64, device=device)
-    _lib.call("mcnerf_sample_perm", _p(out, torch.int64), int(n), int(batch), _p(seed, torch.int32), _stream())
+    _lib.call("mcnerf_sample_perm", out, int(n), int(batch), seed, _stream())
     return out
-
-
-MULTICAM_MAXSEG = 64        # MCN_MULTICAM_MAXSEG
 
 
 def ray_segments(batch: int, K: int):
@@ -352,8 +347,6 @@ def _seg_arrays(seg_cam, seg_start):
 
 
 def _lens_arg(lens: Tensor, C: int) -> Tensor:
-    if not lens.is_cuda:
-        raise _lib.McnerfError("the lens ray-batch ops need CUDA/HIP tensors (no CPU fallback)")
     if lens.dim() != 2 or tuple(lens.shape) != (C, 2):
         raise _lib.McnerfError(f"lens must be [C = {C}, 2] (k1, k2), got {tuple(lens.shape)}")
     return lens
@@ -364,7 +357,7 @@ def _ray_batch_fwd(symbol: str, pose: Tensor, kinv: Tensor, lens: Optional[Tenso
     """Both forwards: `symbol` with `lens` [C,2] behind kinv, or without it (None).  draw_seed: the key word is still to be drawn."""
     cams, start, K, n = _seg_arrays(seg_cam, seg_start)
     dev = pose.device
-    lens_args = () if lens is None else (_p(_lens_arg(lens, int(pose.shape[0]))),)
+    lens_args = () if lens is None else (_lens_arg(lens, int(pose.shape[0])),)
     if draw_seed:
         seed = seed_word(dev)
     if pix is not None and pix.numel() != n:
@@ -375,9 +368,9 @@ def _ray_batch_fwd(symbol: str, pose: Tensor, kinv: Tensor, lens: Optional[Tenso
     d = torch.empty(n, 3, dtype=torch.float32, device=dev)
     o = torch.empty_like(d)
     gt = torch.empty_like(d) if images is not None else None
-    _lib.call(symbol, _p(pose), _p(kinv), *lens_args, int(pose.shape[0]), cams, start, K, n, int(H), int(W),
-              _p(pix, torch.int64), _p(seed, torch.int32), _p(images, torch.uint8), int(images.shape[-1]) if images is not None else 0,
-              _p(pix_out, torch.int64), _p(d), _p(o), _p(gt), _stream())
+    _lib.call(symbol, pose, kinv, *lens_args, int(pose.shape[0]), cams, start, K, n, int(H), int(W),
+              pix, seed, images, int(images.shape[-1]) if images is not None else 0,
+              pix_out, d, o, gt, _stream())
     return pix_out, d, o, gt
 
 
@@ -386,13 +379,13 @@ def _ray_batch_bwd(symbol: str, pose: Tensor, kinv: Tensor, lens: Optional[Tenso
     """Both backwards -> (d_pose [C,3,4], d_kinv [C,3,3]) and, with `lens`, d_lens [C,2]: views of one zero-filled buffer."""
     cams, start, K, n = _seg_arrays(seg_cam, seg_start)
     C = int(pose.shape[0])
-    lens_args = () if lens is None else (_p(_lens_arg(lens, C)),)
+    lens_args = () if lens is None else (_lens_arg(lens, C),)
     z = torch.zeros(C * (21 if lens is None else 23), dtype=torch.float32, device=pose.device)     # (one fill for every accumulation target)
     outs = (z[:C * 12].view(C, 3, 4), z[C * 12:C * 21].view(C, 3, 3)) + (() if lens is None else (z[C * 21:].view(C, 2),))
     if pix.numel() != n or d_d.numel() != 3 * n or d_o.numel() != 3 * n:
         raise _lib.McnerfError(f"pix / d_rays_d / d_rays_o must hold seg_start[-1] = {n} rays")
-    _lib.call(symbol, _p(pose), _p(kinv), *lens_args, C, cams, start, K, n, int(W), _p(pix, torch.int64),
-              _p(d_d), _p(d_o), *(_p(g) for g in outs), _stream())
+    _lib.call(symbol, pose, kinv, *lens_args, C, cams, start, K, n, int(W), pix,
+              d_d, d_o, *outs, _stream())
     return outs
 
 
@@ -435,7 +428,7 @@ def upload_f32(host_vals: Tensor, device) -> Tensor:
     hv = host_vals.detach().reshape(-1).float().contiguous()
     assert hv.device.type == "cpu" and hv.numel() <= 16
     out = torch.empty(hv.numel(), dtype=torch.float32, device=device)
-    _lib.call("mcnerf_upload_f32", _p(out), hv.data_ptr(), hv.numel(), _stream())
+    _lib.call("mcnerf_upload_f32", out, hv.data_ptr(), hv.numel(), _stream())
     return out
 
 
@@ -443,7 +436,7 @@ def encode(x: Tensor, barf_w: Tensor) -> Tensor:
     """SinCosEmbedding.forward (model/net_block.py:20-35): [n,3] -> [n, 3 + 6 F] with F = len(barf_w) frequencies (10: 63)."""
     n, F = x.shape[0], barf_w.numel()
     out = torch.empty(n, 3 + 6 * F, dtype=torch.float32, device=x.device)
-    _lib.call("mcnerf_encode", _p(x), _p(barf_w), n, F, _p(out), _stream())
+    _lib.call("mcnerf_encode", x, barf_w, n, F, out, _stream())
     return out
 
 
@@ -451,22 +444,22 @@ def mlp_apply(net: Net, params: Tensor, packed: Tensor, x_enc: Tensor, dirs: Ten
     """CorseFine_NeRF.forward (model/net_block.py:67-78) on given encodings: [n,63], [n,3] -> [n,4] (exact-fp32 kernel)."""
     n = x_enc.shape[0]
     out = torch.empty(n, 4, dtype=torch.float32, device=x_enc.device)
-    _lib.call("mcnerf_mlp_apply", *net.triple, _p(params), _p(packed), _p(x_enc), _p(dirs), n, _p(out), _stream())
+    _lib.call("mcnerf_mlp_apply", *net.triple, params, packed, x_enc, dirs, n, out, _stream())
     return out
 
 
 def sync_finish(arena: Tensor, n_grad: int, world: int, local_flags: Tensor, asym: Tensor) -> None:
     """arena[:n_grad] /= world; asym += any(arena[n_grad:] != world * local_flags) -- the finish of FlatGradSync's one all-reduce
     in one launch."""
-    _lib.call("mcnerf_sync_finish", _p(arena), int(n_grad), int(arena.numel() - n_grad), int(world), _p(local_flags),
-              _p(asym, torch.int32), _stream())
+    _lib.call("mcnerf_sync_finish", arena, int(n_grad), int(arena.numel() - n_grad), int(world), local_flags,
+              asym, _stream())
 
 
 def encode_bwd(x: Tensor, barf_w: Tensor, d_out: Tensor) -> Tensor:
     """Backward of `encode`: d_out [n, 3 + 6 F] -> d_x [n,3]."""
     n = x.shape[0]
     d_x = torch.empty(n, 3, dtype=torch.float32, device=x.device)
-    _lib.call("mcnerf_encode_bwd", _p(x), _p(barf_w), n, barf_w.numel(), _p(d_out), _p(d_x), _stream())
+    _lib.call("mcnerf_encode_bwd", x, barf_w, n, barf_w.numel(), d_out, d_x, _stream())
     return d_x
 
 
@@ -475,8 +468,8 @@ def mlp_apply_save(net: Net, params: Tensor, packed: Tensor, x_enc: Tensor, dirs
     n = x_enc.shape[0]
     out = torch.empty(n, 4, dtype=torch.float32, device=x_enc.device)
     save = alloc_save(net, n, x_enc.device, "f32")
-    _lib.call("mcnerf_mlp_apply_save", *net.triple, _p(params), _p(packed), _p(x_enc), _p(dirs), n, _p(out),
-              _p(save.act), save.capacity, _p(save.enc), _p(save.sh), _p(save.mask, torch.int32), _stream())
+    _lib.call("mcnerf_mlp_apply_save", *net.triple, params, packed, x_enc, dirs, n, out,
+              save.act, save.capacity, save.enc, save.sh, save.mask, _stream())
     return out, save
 
 
@@ -490,8 +483,8 @@ def mlp_apply_bwd(net: Net, params: Tensor, packed: Tensor, dirs: Tensor, out: T
     d_x = torch.empty(n, net.n_enc, dtype=torch.float32, device=dev)
     z = torch.zeros(n * 3 + 1, dtype=torch.float32, device=dev)          # (d_dirs accumulator + the zero sample depth, one fill)
     d_dirs = z[:n * 3].view(n, 3)
-    _lib.call("mcnerf_mlp_apply_bwd", *net.triple, _p(params), _p(packed), _p(dirs), _p(z[n * 3:]), n, _p(out), _p(d_out),
-              _p(save.mask, torch.int32), save.capacity, _p(save.enc), _p(save.sh), _p(dy), _p(dsh), _p(d_x), _p(d_dirs), _stream())
+    _lib.call("mcnerf_mlp_apply_bwd", *net.triple, params, packed, dirs, z[n * 3:], n, out, d_out,
+              save.mask, save.capacity, save.enc, save.sh, dy, dsh, d_x, d_dirs, _stream())
     if grads is not None:
         mlp_dw(net, save, dy, dsh, grads, n)
     return d_x, d_dirs
@@ -506,26 +499,26 @@ def mlp_bwd(net: Net, params: Tensor, packed: Tensor, rays_o: Tensor, rays_d: Te
     n_rays = rays_d.shape[0]
     zgrid, S, zs = _depths(zgrid, z_rows, n_rays)
     if is16(precision):
-        _lib.call("mcnerf_mlp_bwd_16", *net.triple, DTYPE16[precision], _p(params), _p(packed16_split(net, packed, precision)[1], torch.uint8), _p(rays_o), _p(rays_d),
-                  _p(zgrid), zs, _p(jitter), _p(barf_w), _p(idx, torch.int32), _p(count, torch.int32), int(max_rows), n_rays, S,
-                  _p(out), _p(d_out), _p(save.mask, torch.int32), save.capacity, _p(save.enc, torch.uint8), _p(save.sh, torch.uint8),
-                  _p(dy, torch.uint8), _p(dsh, torch.uint8), _p(d_rays_o), _p(d_rays_d), _p(gmax, torch.int32), _stream())
+        _lib.call("mcnerf_mlp_bwd_16", *net.triple, DTYPE16[precision], params, packed16_split(net, packed, precision)[1], rays_o, rays_d,
+                  zgrid, zs, jitter, barf_w, idx, count, int(max_rows), n_rays, S,
+                  out, d_out, save.mask, save.capacity, save.enc, save.sh,
+                  dy, dsh, d_rays_o, d_rays_d, gmax, _stream())
         return
-    args = [*net.triple, _p(params), _p(packed), _p(rays_o), _p(rays_d), _p(zgrid), zs,
-            _p(jitter), _p(barf_w), _p(idx, torch.int32), _p(count, torch.int32), int(max_rows), n_rays, S,
-            _p(out), _p(d_out), _p(save.mask, torch.int32), save.capacity, _p(save.enc), _p(save.sh),
-            _p(dy), _p(dsh), _p(d_rays_o), _p(d_rays_d)]
+    args = [*net.triple, params, packed, rays_o, rays_d, zgrid, zs,
+            jitter, barf_w, idx, count, int(max_rows), n_rays, S,
+            out, d_out, save.mask, save.capacity, save.enc, save.sh,
+            dy, dsh, d_rays_o, d_rays_d]
     _lib.call("mcnerf_mlp_bwd", *args, _stream())
 
 
 def mlp_dw(net: Net, save: MlpSave, dy: Tensor, dsh: Tensor, grads: Tensor, rows: int,
            count: Optional[Tensor] = None, precision: str = "f32", gmax: Optional[Tensor] = None) -> None:
     if is16(precision):
-        _lib.call("mcnerf_mlp_dw_16", *net.triple, DTYPE16[precision], _p(count, torch.int32), int(rows), _p(save.act, torch.uint8),
-                  _p(save.enc, torch.uint8), _p(dy, torch.uint8), _p(dsh, torch.uint8), save.capacity, _p(grads),
-                  _p(gmax, torch.int32), _stream())
+        _lib.call("mcnerf_mlp_dw_16", *net.triple, DTYPE16[precision], count, int(rows), save.act,
+                  save.enc, dy, dsh, save.capacity, grads,
+                  gmax, _stream())
         return
-    args = [*net.triple, _p(count, torch.int32), int(rows), _p(save.act), _p(save.enc), _p(dy), _p(dsh), save.capacity, _p(grads)]
+    args = [*net.triple, count, int(rows), save.act, save.enc, dy, dsh, save.capacity, grads]
     _lib.call("mcnerf_mlp_dw", *args, _stream())
 
 
@@ -542,8 +535,8 @@ def composite_fwd(sig_rgb: Tensor, rays_d: Tensor, zgrid: Tensor, jitter: Option
     opac = torch.empty(N, 1, dtype=torch.float32, device=dev) if want_depth else None
     w_sel = torch.empty(N, S, dtype=torch.float32, device=dev) if eps_sel is not None else None
     wmax = torch.zeros(1, dtype=torch.int32, device=dev) if eps_sel is not None else None
-    _lib.call("mcnerf_composite_fwd", _p(sig_rgb), _p(rays_d), _p(zgrid), zs, _p(jitter), _p(eps), _p(eps_sel), N, S,
-              int(bool(white_back)), _p(rgb), _p(depth), _p(opac), _p(w_sel), _p(wmax, torch.int32), _stream())
+    _lib.call("mcnerf_composite_fwd", sig_rgb, rays_d, zgrid, zs, jitter, eps, eps_sel, N, S,
+              int(bool(white_back)), rgb, depth, opac, w_sel, wmax, _stream())
     return rgb, depth, opac, w_sel, wmax
 
 
@@ -554,8 +547,8 @@ def composite_bwd(sig_rgb: Tensor, zgrid: Tensor, jitter: Optional[Tensor], eps:
     zgrid, S, zs = _depths(zgrid, z_rows, N)
     d = torch.empty(N, S, 4, dtype=torch.float32, device=d_rgb.device)
     gmax = torch.zeros(1, dtype=torch.int32, device=d_rgb.device) if want_gmax else None
-    _lib.call("mcnerf_composite_bwd", _p(sig_rgb), _p(zgrid), zs, _p(jitter), _p(eps), _p(d_rgb), N, S,
-              int(bool(white_back)), _p(d), _p(gmax, torch.int32), _stream())
+    _lib.call("mcnerf_composite_bwd", sig_rgb, zgrid, zs, jitter, eps, d_rgb, N, S,
+              int(bool(white_back)), d, gmax, _stream())
     return (d, gmax) if want_gmax else d
 
 
@@ -575,13 +568,10 @@ def select_fine(w_sel: Tensor, wmax: Tensor, thresh: float, scale: int, sigma_de
     """-> idx [N*Sc*scale,2] int32 (first *count rows valid), count [1] int32, out_f [N,Sf,4] | None"""
     N, Sc = w_sel.shape
     idx, count, rc, ro, out_f = _list_buffers(N, Sc * scale, prefill, None, w_sel.device)
-    _lib.call("mcnerf_select_fine", _p(w_sel), _p(wmax, torch.int32), float(thresh), N, Sc, scale,
-              float(sigma_default), _p(rc, torch.int32), _p(ro, torch.int32), _p(idx, torch.int32),
-              _p(count, torch.int32), _p(out_f), _stream())
+    _lib.call("mcnerf_select_fine", w_sel, wmax, float(thresh), N, Sc, scale,
+              float(sigma_default), rc, ro, idx,
+              count, out_f, _stream())
     return idx, count, out_f
-
-
-PDF_MAX_SAMPLES = 1024      # MCN_PDF_MAX_SAMPLES: bound on Sc + n_importance of sample_pdf
 
 
 def sample_pdf(w_sel: Tensor, zgrid: Tensor, jitter: Optional[Tensor], u: Tensor) -> Tensor:
@@ -593,7 +583,7 @@ def sample_pdf(w_sel: Tensor, zgrid: Tensor, jitter: Optional[Tensor], u: Tensor
         raise _lib.McnerfError(f"sample_pdf: w_sel [N,Sc] {tuple(w_sel.shape)}, zgrid [Sc] {tuple(zgrid.shape)}, u [N,I] {tuple(u.shape)}")
     I = u.shape[1]
     z_all = torch.empty(N, Sc + I, dtype=torch.float32, device=w_sel.device)
-    _lib.call("mcnerf_sample_pdf", _p(w_sel), _p(zgrid), _p(jitter), _p(u), N, Sc, I, _p(z_all), _stream())
+    _lib.call("mcnerf_sample_pdf", w_sel, zgrid, jitter, u, N, Sc, I, z_all, _stream())
     return z_all
 
 
@@ -637,8 +627,8 @@ def voxel_select(grid: VoxelGrid, thresh: float, rays_o: Tensor, rays_d: Tensor,
     if idx is not None and idx.numel() < N * Sc * 2:
         raise _lib.McnerfError(f"voxel_select: idx must hold N * Sc = {N * Sc} pairs, got {tuple(idx.shape)}")
     idx, count, rc, ro, out_c = _list_buffers(N, Sc, prefill, idx, rays_d.device)
-    _lib.call("mcnerf_voxel_select", _p(grid.vox), *grid.geom, float(thresh), _p(rays_o), _p(rays_d), _p(zgrid), _p(jitter), N, Sc,
-              float(sigma_default), _p(rc, torch.int32), _p(ro, torch.int32), _p(idx, torch.int32), _p(count, torch.int32), _p(out_c), _stream())
+    _lib.call("mcnerf_voxel_select", grid.vox, *grid.geom, float(thresh), rays_o, rays_d, zgrid, jitter, N, Sc,
+              float(sigma_default), rc, ro, idx, count, out_c, _stream())
     return idx, count, out_c
 
 
@@ -649,15 +639,15 @@ def voxel_update(grid: VoxelGrid, beta: float, rays_o: Tensor, rays_d: Tensor, z
     N, Sc = rays_d.shape[0], zgrid.numel()
     if sig_rgb.numel() != N * Sc * 4 or (jitter is not None and jitter.numel() != N):
         raise _lib.McnerfError(f"voxel_update: sig_rgb must be [N = {N}, Sc = {Sc}, 4], got {tuple(sig_rgb.shape)}")
-    _lib.call("mcnerf_voxel_update", _p(grid.vox), _p(grid.scratch, torch.int32), *grid.geom, *voxel_blend(beta), _p(rays_o), _p(rays_d),
-              _p(zgrid), _p(jitter), N, Sc, _p(idx, torch.int32), _p(count, torch.int32), int(max_rows), _p(sig_rgb), _stream())
+    _lib.call("mcnerf_voxel_update", grid.vox, grid.scratch, *grid.geom, *voxel_blend(beta), rays_o, rays_d,
+              zgrid, jitter, N, Sc, idx, count, int(max_rows), sig_rgb, _stream())
 
 
 def voxel_query(grid: VoxelGrid, xyz: Tensor) -> Tensor:
     """query_sigma (model/mc_nerf.py:859-862): xyz [M,3] -> the cells' sigma [M]."""
     M = xyz.shape[0]
     out = torch.empty(M, dtype=torch.float32, device=xyz.device)
-    _lib.call("mcnerf_voxel_query", _p(grid.vox), *grid.geom, _p(xyz), M, _p(out), _stream())
+    _lib.call("mcnerf_voxel_query", grid.vox, *grid.geom, xyz, M, out, _stream())
     return out
 
 
@@ -666,14 +656,11 @@ def voxel_update_points(grid: VoxelGrid, xyz: Tensor, sigma: Tensor, beta: float
     M = xyz.shape[0]
     if sigma.numel() != M:
         raise _lib.McnerfError(f"voxel_update_points: xyz [M,3] {tuple(xyz.shape)}, sigma [M] {tuple(sigma.shape)}")
-    _lib.call("mcnerf_voxel_update_points", _p(grid.vox), _p(grid.scratch, torch.int32), *grid.geom, *voxel_blend(beta), _p(xyz), _p(sigma),
+    _lib.call("mcnerf_voxel_update_points", grid.vox, grid.scratch, *grid.geom, *voxel_blend(beta), xyz, sigma,
               M, _stream())
 
 
 # --------------------------------------------------------------------------- error-guided pixel sampling (include/mcnerf.h: mcnerf_errmap_*)
-ERRMAP_MAX_PIXELS = 1 << 26     # H * W of one image at most: the integer tile weights then sum to <= 2^52, exact in a double
-
-
 class ErrorMap:
     """The three device buffers of `pixel_sampler = "error"` and the map's geometry: err [C,Th,Tw] fp32 (running squared colour error
     per tile of tile x tile pixels, Th = ceil(H / tile), Tw = ceil(W / tile), edge tiles smaller; filled with 1.0 -- optimistic: a tile
@@ -707,8 +694,8 @@ def errmap_sample(emap: ErrorMap, seg_cam, seg_start, uniform_frac: float, u: Op
     if u is not None and u.numel() != 2 * n:
         raise _lib.McnerfError(f"errmap_sample: u must be [seg_start[-1] = {n}, 2], got {tuple(u.shape)}")
     pix = torch.empty(n, dtype=torch.int64, device=dev)
-    _lib.call("mcnerf_errmap_sample", _p(emap.err), *emap.geom, cams, start, K, n, float(uniform_frac), _p(u), _p(emap.cdf, torch.int64),
-              _p(pix, torch.int64), _stream())
+    _lib.call("mcnerf_errmap_sample", emap.err, *emap.geom, cams, start, K, n, float(uniform_frac), u, emap.cdf,
+              pix, _stream())
     return pix
 
 
@@ -719,15 +706,15 @@ def errmap_update(emap: ErrorMap, seg_cam, seg_start, pix: Tensor, rgb: Tensor, 
     cams, start, K, n = _seg_arrays(seg_cam, seg_start)
     if pix.numel() != n or rgb.numel() != 3 * n or gt.numel() != 3 * n:
         raise _lib.McnerfError(f"errmap_update: pix / rgb / gt must hold seg_start[-1] = {n} rays, got {tuple(pix.shape)}, {tuple(rgb.shape)}, {tuple(gt.shape)}")
-    _lib.call("mcnerf_errmap_update", _p(emap.err), _p(emap.scratch, torch.int32), *emap.geom, cams, start, K, n, _p(pix, torch.int64),
-              _p(rgb), _p(gt), *voxel_blend(beta), _stream())
+    _lib.call("mcnerf_errmap_update", emap.err, emap.scratch, *emap.geom, cams, start, K, n, pix,
+              rgb, gt, *voxel_blend(beta), _stream())
 
 
 def cap_gather(idx: Tensor, perm: Tensor, keep: int):
     idx2 = torch.empty(keep, 2, dtype=torch.int32, device=idx.device)
     count = torch.empty(1, dtype=torch.int32, device=idx.device)
-    _lib.call("mcnerf_cap_gather", _p(idx, torch.int32), _p(perm, torch.int64), int(keep), _p(idx2, torch.int32),
-              _p(count, torch.int32), _stream())
+    _lib.call("mcnerf_cap_gather", idx, perm, int(keep), idx2,
+              count, _stream())
     return idx2, count
 
 
@@ -737,8 +724,8 @@ def cap_random(idx: Tensor, count: Tensor, max_rows: int, keep: int, seed: Tenso
     idx2 = torch.empty(keep, 2, dtype=torch.int32, device=dev)
     count2 = torch.empty(1, dtype=torch.int32, device=dev)
     ws = torch.empty(int(_lib.lib().mcnerf_cap_ws_words()), dtype=torch.int32, device=dev)
-    _lib.call("mcnerf_cap_random", _p(idx, torch.int32), _p(count, torch.int32), int(max_rows), int(keep), _p(seed, torch.int32),
-              _p(ws, torch.int32), _p(idx2, torch.int32), _p(count2, torch.int32), _stream())
+    _lib.call("mcnerf_cap_random", idx, count, int(max_rows), int(keep), seed,
+              ws, idx2, count2, _stream())
     return idx2, count2
 
 
@@ -757,8 +744,8 @@ def camera_fwd(wpose: Tensor, wpose_intr: Tensor, wfx: Tensor, wfy: Tensor, wux:
             P = w.shape[1]
     pi = torch.empty(C, P, 2, dtype=torch.float32, device=dev) if wpts_intr is not None else None
     pe = torch.empty(C, P, 2, dtype=torch.float32, device=dev) if wpts_extr is not None else None
-    _lib.call("mcnerf_camera_fwd", _p(wpose), _p(wpose_intr), _p(wfx), _p(wfy), _p(wux), _p(wuy), C, int(H), int(W),
-              _p(K), _p(Kinv), _p(pose), _p(calib), _p(wpts_intr), _p(wpts_extr), int(P), _p(pi), _p(pe), _stream())
+    _lib.call("mcnerf_camera_fwd", wpose, wpose_intr, wfx, wfy, wux, wuy, C, int(H), int(W),
+              K, Kinv, pose, calib, wpts_intr, wpts_extr, int(P), pi, pe, _stream())
     return K, Kinv, pose, calib, pi, pe
 
 
@@ -772,21 +759,21 @@ def camera_bwd(wpose, wpose_intr, wfx, wfy, wux, wuy, H: int, W: int, dK, dKinv,
     for w in (wpts_intr, wpts_extr):
         if w is not None:
             P = w.shape[1]
-    _lib.call("mcnerf_camera_bwd", _p(wpose), _p(wpose_intr), _p(wfx), _p(wfy), _p(wux), _p(wuy), C, int(H), int(W),
-              _p(dK), _p(dKinv), _p(dpose), _p(dcalib), _p(wpts_intr), _p(wpts_extr), int(P), _p(dpix_intr), _p(dpix_extr),
-              *[_p(o) for o in outs], _stream())
+    _lib.call("mcnerf_camera_bwd", wpose, wpose_intr, wfx, wfy, wux, wuy, C, int(H), int(W),
+              dK, dKinv, dpose, dcalib, wpts_intr, wpts_extr, int(P), dpix_intr, dpix_extr,
+              *outs, _stream())
     return outs
 
 
 def reproj_loss_fwd(pd: Tensor, gt: Tensor, H: int, W: int) -> Tensor:
     loss = torch.empty((), dtype=torch.float32, device=pd.device)
-    _lib.call("mcnerf_reproj_loss_fwd", _p(pd), _p(gt), pd.numel() // 2, int(H), int(W), _p(loss), _stream())
+    _lib.call("mcnerf_reproj_loss_fwd", pd, gt, pd.numel() // 2, int(H), int(W), loss, _stream())
     return loss
 
 
 def reproj_loss_bwd(pd: Tensor, gt: Tensor, H: int, W: int, dloss: Tensor) -> Tensor:
     d = torch.empty_like(pd)
-    _lib.call("mcnerf_reproj_loss_bwd", _p(pd), _p(gt), pd.numel() // 2, int(H), int(W), _p(dloss), _p(d), _stream())
+    _lib.call("mcnerf_reproj_loss_bwd", pd, gt, pd.numel() // 2, int(H), int(W), dloss, d, _stream())
     return d
 
 
@@ -798,16 +785,9 @@ def train_loss(pd: Optional[Tensor], pt_gt: Optional[Tensor], H: int, W: int, no
     d_pd = torch.empty_like(pd) if pd is not None else None
     d_c = torch.empty_like(rgb_c)
     d_f = torch.empty_like(rgb_f) if rgb_f is not None else None
-    _lib.call("mcnerf_train_loss", _p(pd), _p(pt_gt), np_, int(H), int(W), int(bool(normalise)), _p(rgb_c), _p(rgb_f), _p(gt), rgb_c.numel(),
-              _p(out), _p(d_pd), _p(d_c), _p(d_f), _stream())
+    _lib.call("mcnerf_train_loss", pd, pt_gt, np_, int(H), int(W), int(bool(normalise)), rgb_c, rgb_f, gt, rgb_c.numel(),
+              out, d_pd, d_c, d_f, _stream())
     return out[:3], d_pd, d_c, d_f
-
-
-TRAIN_LOSS_OUT = 132        # MCNERF_TRAIN_LOSS_OUT
-
-
-TRAIN_LOSS_CALIB_OUT = 8     # MCNERF_TRAIN_LOSS_CALIB_OUT
-TRAIN_LOSS_CALIB_WS = 896    # MCNERF_TRAIN_LOSS_CALIB_WS
 
 
 def train_loss_calib(pd: Optional[Tensor], pt_gt: Optional[Tensor], H: int, W: int, normalise: bool, rgb_c: Tensor, rgb_f: Optional[Tensor],
@@ -818,11 +798,6 @@ def train_loss_calib(pd: Optional[Tensor], pt_gt: Optional[Tensor], H: int, W: i
     TRAIN_LOSS_CALIB_OUT + TRAIN_LOSS_CALIB_WS floats to re-use (its word [4], the kernel's arrival counter, zero on entry: it is
     zero again on exit); allocated and zeroed when not given."""
     cams, start, K, n = _seg_arrays(seg_cam, seg_start)
-    if not rgb_c.is_cuda:
-        raise _lib.McnerfError("train_loss_calib needs CUDA/HIP tensors (no CPU fallback; MC_NeRF_Loss keeps the eager formulation for host tensors)")
-    for name, t in (("pd", pd), ("pt_gt", pt_gt), ("rgb_f", rgb_f), ("gt", gt), ("color_w", color_w), ("out", out)):
-        if t is not None and (t.device != rgb_c.device or t.dtype != torch.float32):       # (before anything is allocated or launched)
-            raise _lib.McnerfError(f"train_loss_calib: {name} must be a float32 tensor on {rgb_c.device}, got {t.dtype} on {t.device}")
     if rgb_c.numel() != 3 * n or gt.numel() != 3 * n or (rgb_f is not None and rgb_f.numel() != 3 * n):
         raise _lib.McnerfError(f"rgb_c / rgb_f / gt must hold seg_start[-1] = {n} rays of 3 channels")
     if color_w.dim() != 2 or color_w.shape[1] != 6:
@@ -837,22 +812,22 @@ def train_loss_calib(pd: Optional[Tensor], pt_gt: Optional[Tensor], H: int, W: i
     d_c = torch.empty_like(rgb_c)
     d_f = torch.empty_like(rgb_f) if rgb_f is not None else None
     d_color = torch.empty_like(color_w)
-    _lib.call("mcnerf_train_loss_calib", _p(pd), _p(pt_gt), np_, int(H), int(W), int(bool(normalise)), _p(rgb_c), _p(rgb_f), _p(gt), n,
-              _p(color_w), int(color_w.shape[0]), cams, start, K, float(reg_lambda), _p(out), _p(d_pd), _p(d_c), _p(d_f), _p(d_color),
-              _p(out[TRAIN_LOSS_CALIB_OUT:]), _stream())
+    _lib.call("mcnerf_train_loss_calib", pd, pt_gt, np_, int(H), int(W), int(bool(normalise)), rgb_c, rgb_f, gt, n,
+              color_w, int(color_w.shape[0]), cams, start, K, float(reg_lambda), out, d_pd, d_c, d_f, d_color,
+              out[TRAIN_LOSS_CALIB_OUT:], _stream())
     return out[:4], d_pd, d_c, d_f, d_color
 
 
 def scale3_(a: Optional[Tensor], b: Tensor, c: Optional[Tensor], g: Tensor):
     """a, b, c *= g (device scalar) in place, one launch."""
-    _lib.call("mcnerf_scale3", _p(a), a.numel() if a is not None else 0, _p(b), b.numel(), _p(c), c.numel() if c is not None else 0, _p(g), _stream())
+    _lib.call("mcnerf_scale3", a, a.numel() if a is not None else 0, b, b.numel(), c, c.numel() if c is not None else 0, g, _stream())
 
 
 def gather_gt(image_u8: Tensor, pix: Tensor) -> Tensor:
     """image_u8 [H*W, 3|4] uint8 on the device, pix [n] int64 -> [n,3] fp32 (RGBA blended on white)."""
     n = pix.numel()
     out = torch.empty(n, 3, dtype=torch.float32, device=pix.device)
-    _lib.call("mcnerf_gather_gt", _p(image_u8, torch.uint8), int(image_u8.shape[-1]), _p(pix, torch.int64), n, _p(out), _stream())
+    _lib.call("mcnerf_gather_gt", image_u8, int(image_u8.shape[-1]), pix, n, out, _stream())
     return out
 
 

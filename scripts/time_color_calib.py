@@ -48,18 +48,18 @@ def main():
     d_pd, d_c, d_f, d_w = torch.empty_like(pd), torch.empty_like(rgb_c), torch.empty_like(rgb_f), torch.empty_like(cw)
     out0 = torch.zeros(ops.TRAIN_LOSS_OUT, device=dev)
     out1 = torch.zeros(ops.TRAIN_LOSS_CALIB_OUT + ops.TRAIN_LOSS_CALIB_WS, device=dev)
-    p, st = ops._p, ops._stream()
+    st = ops._stream()
     np_ = pd.numel() // 2
 
     def plain(i):
-        _lib.call("mcnerf_train_loss", p(pd), p(ptg), np_, H, W, 1, p(rgb_c), p(rgb_f), p(gt), rgb_c.numel(), p(out0), p(d_pd), p(d_c), p(d_f), st)
+        _lib.call("mcnerf_train_loss", pd, ptg, np_, H, W, 1, rgb_c, rgb_f, gt, rgb_c.numel(), out0, d_pd, d_c, d_f, st)
 
     def calib_of(K):
         cams, start, _, n = ops._seg_arrays([(7 * k) % C for k in range(K)], ops.ray_segments(rays, K))
 
         def f(i):
-            _lib.call("mcnerf_train_loss_calib", p(pd), p(ptg), np_, H, W, 1, p(rgb_c), p(rgb_f), p(gt), n, p(cw), C, cams, start, K, 1e-3,
-                      p(out1), p(d_pd), p(d_c), p(d_f), p(d_w), p(out1[ops.TRAIN_LOSS_CALIB_OUT:]), st)
+            _lib.call("mcnerf_train_loss_calib", pd, ptg, np_, H, W, 1, rgb_c, rgb_f, gt, n, cw, C, cams, start, K, 1e-3,
+                      out1, d_pd, d_c, d_f, d_w, out1[ops.TRAIN_LOSS_CALIB_OUT:], st)
         return f
 
     fns = {"train_loss": plain, **{f"train_loss_calib K = {K:2d}": calib_of(K) for K in (1, 8, 64)}}

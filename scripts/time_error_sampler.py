@@ -53,20 +53,20 @@ def main():
     pix = torch.empty(rays, dtype=torch.int64, device=dev)
     perm_out = torch.empty(rays, dtype=torch.int64, device=dev)
     seed = torch.randint(0, 2 ** 31 - 1, (1,), dtype=torch.int32, device=dev)
-    p, st = ops._p, ops._stream()
+    st = ops._stream()
     beta, omb = ops.voxel_blend(0.5)
 
     def perm(i):
-        _lib.call("mcnerf_sample_perm", p(perm_out, torch.int64), H * W, rays, p(seed, torch.int32), st)
+        _lib.call("mcnerf_sample_perm", perm_out, H * W, rays, seed, st)
 
     def pair_of(K):
         cams, start, _, n = ops._seg_arrays([(7 * k) % C for k in range(K)], ops.ray_segments(rays, K))
 
         def sample(i):
-            _lib.call("mcnerf_errmap_sample", p(em.err), C, H, W, tile, cams, start, K, n, 0.5, p(u), p(em.cdf, torch.int64), p(pix, torch.int64), st)
+            _lib.call("mcnerf_errmap_sample", em.err, C, H, W, tile, cams, start, K, n, 0.5, u, em.cdf, pix, st)
 
         def update(i):
-            _lib.call("mcnerf_errmap_update", p(em.err), p(em.scratch, torch.int32), C, H, W, tile, cams, start, K, n, p(pix, torch.int64), p(rgb), p(gt),
+            _lib.call("mcnerf_errmap_update", em.err, em.scratch, C, H, W, tile, cams, start, K, n, pix, rgb, gt,
                       beta, omb, st)
         return sample, update
 

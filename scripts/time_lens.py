@@ -56,26 +56,26 @@ def main():
     d, o, gt = (torch.empty(rays, 3, device=dev) for _ in range(3))
     grads = torch.zeros(C * 23, device=dev)
     d_pose, d_kinv, d_lens = grads[:C * 12], grads[C * 12:C * 21], grads[C * 21:]
-    p, st = ops._p, ops._stream()
+    st = ops._stream()
     u8 = images.images
 
     def quad_of(K):
         cams, start, _, n = ops._seg_arrays([(7 * k) % C for k in range(K)], ops.ray_segments(rays, K))
 
         def fwd(i):
-            _lib.call("mcnerf_ray_batch_fwd", p(pose), p(kinv), C, cams, start, K, n, H, W, p(pix, torch.int64), None, p(u8, torch.uint8),
-                      int(u8.shape[-1]), p(pix_out, torch.int64), p(d), p(o), p(gt), st)
+            _lib.call("mcnerf_ray_batch_fwd", pose, kinv, C, cams, start, K, n, H, W, pix, None, u8,
+                      int(u8.shape[-1]), pix_out, d, o, gt, st)
 
         def bwd(i):
-            _lib.call("mcnerf_ray_batch_bwd", p(pose), p(kinv), C, cams, start, K, n, W, p(pix, torch.int64), p(g_d), p(g_o), p(d_pose), p(d_kinv), st)
+            _lib.call("mcnerf_ray_batch_bwd", pose, kinv, C, cams, start, K, n, W, pix, g_d, g_o, d_pose, d_kinv, st)
 
         def lfwd(i):
-            _lib.call("mcnerf_lens_ray_batch_fwd", p(pose), p(kinv), p(lens), C, cams, start, K, n, H, W, p(pix, torch.int64), None,
-                      p(u8, torch.uint8), int(u8.shape[-1]), p(pix_out, torch.int64), p(d), p(o), p(gt), st)
+            _lib.call("mcnerf_lens_ray_batch_fwd", pose, kinv, lens, C, cams, start, K, n, H, W, pix, None,
+                      u8, int(u8.shape[-1]), pix_out, d, o, gt, st)
 
         def lbwd(i):
-            _lib.call("mcnerf_lens_ray_batch_bwd", p(pose), p(kinv), p(lens), C, cams, start, K, n, W, p(pix, torch.int64), p(g_d), p(g_o),
-                      p(d_pose), p(d_kinv), p(d_lens), st)
+            _lib.call("mcnerf_lens_ray_batch_bwd", pose, kinv, lens, C, cams, start, K, n, W, pix, g_d, g_o,
+                      d_pose, d_kinv, d_lens, st)
         return fwd, lfwd, bwd, lbwd
 
     fns = {}

@@ -139,3 +139,130 @@ def test_hi_plane_mode_workspace_layout(built_lib):
             assert ws(0, "f16x3h") == (depth + 2) * tiles * (width // 16) * 1024
             assert ws(2, "f16x3h") == (depth + 2) * tiles * 64 * 4 * max(1, width // 64)
             assert ws(3, "f16x3h") == tiles * 2 * 1024 and ws(4, "f16x3h") == tiles * 4096
+
+
+# ------------------------------------------------------------------------------------------------------------------ the derived binding
+def header_prototypes():
+    """{function: number of parameters}, by this file's own regex: the commas between a prototype's parentheses."""
+    src = re.sub(r"//[^\n]*", "", re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "mcnerf.h")).read(), flags=re.S))
+    return {name: 0 if args.strip() in ("", "void") else args.count(",") + 1 for name, args in re.findall(r"\b(mcnerf_[a-z_0-9]+)\s*\(([^)]*)\)\s*;", src)}
+
+
+def header_define(name):
+    return int(re.search(rf"^#define {name} (\d+)\b", open(os.path.join(ROOT, "include", "mcnerf.h")).read(), flags=re.M).group(1))
+
+
+MINI_HEADER = """
+/* a comment with a prototype in it: int mcnerf_ghost(float* x, int n); and (parentheses) */
+#define MCNERF_ABI_VERSION 7   /* trailing comment (with parentheses) */
+#define MCNERF_LIMIT 64
+#define MCNERF_MARKER
+#define OTHER_THING 3
+int mcnerf_abi_version(void);
+const char* mcnerf_last_error(void);
+long long mcnerf_count(int depth, long long capacity, float thresh);   // int mcnerf_ghost2(int n);
+int mcnerf_all(const float* a, float* b, const int32_t* c, int32_t* d, const uint32_t* e, uint32_t* f,
+               const int64_t* g, uint64_t* h,
+               const uint8_t* i, const void* j, void* stream);
+int mcnerf_tables(int n, float* const* params, const float* const* grads, int32_t* const* row_step, const long long* sizes, long long* offsets,
+                  MCNERF_HOST const int32_t* seg_cam, MCNERF_HOST const float* host_vals);
+"""
+
+
+def test_parser_covers_every_type_class_on_a_literal_header():
+    import torch
+    from ctypes import c_char_p, c_float, c_int, c_longlong, c_void_p
+    from mc_nerf_amd import _lib
+    fns, defines = _lib.parse_header(MINI_HEADER)
+    assert defines == {"MCNERF_ABI_VERSION": 7, "MCNERF_LIMIT": 64}
+    assert sorted(fns) == ["mcnerf_abi_version", "mcnerf_all", "mcnerf_count", "mcnerf_last_error", "mcnerf_tables"]       # (no ghost)
+    assert fns["mcnerf_abi_version"] == (c_int, ()) and fns["mcnerf_last_error"] == (c_char_p, ())
+    res, params = fns["mcnerf_count"]
+    assert res is c_longlong and [(p[0], p[2], p[3]) for p in params] == [("depth", c_int, None), ("capacity", c_longlong, None), ("thresh", c_float, None)]
+    res, params = fns["mcnerf_all"]                                                                   # (a prototype split over three lines)
+    assert res is c_int and [p[0] for p in params] == list("abcdefghij") + ["stream"] and all(p[2] is c_void_p for p in params)
+    assert [p[3] for p in params] == [torch.float32] * 2 + [torch.int32] * 4 + [torch.int64] * 2 + [torch.uint8] * 3
+    assert params[0][1] == "const float*" and params[7][1] == "uint64_t*"
+    res, params = fns["mcnerf_tables"]
+    assert [p[2] for p in params] == [c_int] + [c_void_p] * 7 and [p[3] for p in params] == [None] + [_lib.HOST] * 7
+    assert [p[0] for p in params][-2:] == ["seg_cam", "host_vals"]
+
+
+@pytest.mark.parametrize("proto, names", [("int mcnerf_bad(const float* x, double y);", ["mcnerf_bad"]),
+                                          ("int mcnerf_bad(unsigned n);", ["mcnerf_bad"]),
+                                          ("int mcnerf_bad(const char* name);", ["mcnerf_bad"]),
+                                          ("int mcnerf_bad(float** table);", ["mcnerf_bad"]),
+                                          ("int mcnerf_bad(int);", ["mcnerf_bad"]),
+                                          ("double mcnerf_bad(int n);", ["mcnerf_bad"]),
+                                          ("int mcnerf_ok(int n);\nint mcnerf_bad(int (*callback)(int), int n);", ["mcnerf_bad"])])
+def test_parser_refuses_a_type_it_does_not_know_and_names_the_function(proto, names):
+    from mc_nerf_amd import _lib
+    with pytest.raises(_lib.McnerfError) as e:
+        _lib.parse_header(proto)
+    assert all(n in str(e.value) for n in names) and "mcnerf_ok" not in str(e.value)
+
+
+@pytest.mark.parametrize("name", sorted(header_prototypes()))
+def test_every_signature_has_the_headers_argument_count(name):
+    from mc_nerf_amd import _lib
+    res, argtypes = _lib.SIGNATURES[name]
+    assert len(argtypes) == header_prototypes()[name] == len(_lib.PARAMS[name][1])
+    assert res is (ctypes.c_char_p if name == "mcnerf_last_error" else ctypes.c_longlong if name in
+                   ("mcnerf_param_count", "mcnerf_packed_count", "mcnerf_packed_bytes_16", "mcnerf_ws_bytes_16", "mcnerf_cap_ws_words") else ctypes.c_int)
+
+
+def test_the_header_declares_53_entry_points_and_version_7(built_lib):
+    from mc_nerf_amd import _lib
+    assert len(header_prototypes()) == len(_lib.SIGNATURES) == 53 and sorted(header_prototypes()) == header_functions()
+    assert _lib.ABI_VERSION == header_define("MCNERF_ABI_VERSION") == 7 == _lib.lib().mcnerf_abi_version()
+
+
+def test_float_arguments_by_value_are_c_float():
+    from ctypes import c_float
+    from mc_nerf_amd import _lib
+    at = lambda name: {p[0]: p[2] for p in _lib.PARAMS[name][1]}
+    floats = lambda name: [i for i, t in enumerate(_lib.SIGNATURES[name][1]) if t is c_float]
+    assert floats("mcnerf_voxel_update") == [3, 4, 5, 6] and [k for k, t in at("mcnerf_voxel_update").items() if t is c_float] == ["bmin", "s", "beta", "one_minus_beta"]
+    assert floats("mcnerf_select_fine") == [2, 6] and [k for k, t in at("mcnerf_select_fine").items() if t is c_float] == ["thresh", "sigma_default"]
+    assert floats("mcnerf_radam_step") == [6, 7, 8, 9, 10, 11]
+    assert [k for k, t in at("mcnerf_radam_step").items() if t is c_float] == ["lr", "beta1", "beta2", "eps", "weight_decay", "step_size"]
+
+
+def test_ops_constants_are_the_headers_defines():
+    from mc_nerf_amd import ops
+    for py, c, value in (("SKIP_MASK", "MCNERF_SKIP_MASK", 256), ("MULTICAM_MAXSEG", "MCNERF_MULTICAM_MAXSEG", 64),
+                         ("PDF_MAX_SAMPLES", "MCNERF_PDF_MAX_SAMPLES", 1024), ("ERRMAP_MAX_PIXELS", "MCNERF_ERRMAP_MAX_PIXELS", 1 << 26),
+                         ("VOXEL_MAX_G", "MCNERF_VOXEL_MAX_G", 1024), ("TRAIN_LOSS_OUT", "MCNERF_TRAIN_LOSS_OUT", 132),
+                         ("TRAIN_LOSS_CALIB_OUT", "MCNERF_TRAIN_LOSS_CALIB_OUT", 8), ("TRAIN_LOSS_CALIB_WS", "MCNERF_TRAIN_LOSS_CALIB_WS", 896)):
+        assert getattr(ops, py) == header_define(c) == value, py
+    api = open(os.path.join(ROOT, "mc_nerf_amd", "csrc", "api.hip")).read()
+    for c, internal in (("MCNERF_SKIP_MASK", "MCN_SKIP_MASK"), ("MCNERF_MULTICAM_MAXSEG", "MCN_MULTICAM_MAXSEG"),
+                        ("MCNERF_PDF_MAX_SAMPLES", "MCN_PDF_MAX_SAMPLES"), ("MCNERF_TRAIN_LOSS_OUT", "4 + MCN_LOSS_BLOCKS")):
+        assert f"static_assert({c} == {internal}," in api
+    assert "<= MCNERF_ERRMAP_MAX_PIXELS" in api and "<= MCNERF_VOXEL_MAX_G" in api and "1ll << 26" not in api
+
+
+def test_call_refuses_host_tensors_by_entry_point_and_parameter(built_lib):
+    """A CPU tensor at a float*, an int32_t* and a void* parameter: refused with the names of both before anything reaches C (the
+    buffers the calls would have written keep their values; nothing launches, no GPU is needed)."""
+    import torch
+    from mc_nerf_amd import _lib
+    x, w, out = torch.rand(5, 3), torch.ones(4), torch.full((5, 27), -7.0)
+    with pytest.raises(_lib.McnerfError, match=r"mcnerf_encode: x .*no CPU fallback"):
+        _lib.call("mcnerf_encode", x, w, 5, 4, out, 0)
+    with pytest.raises(_lib.McnerfError, match=r"mcnerf_encode: out .*no CPU fallback"):                 # (an address is not checked: x passes)
+        _lib.call("mcnerf_encode", 4096, None, 5, 4, out, 0)
+    idx, perm, idx2, count = torch.zeros(4, 2, dtype=torch.int32), torch.arange(4), torch.full((4, 2), -7, dtype=torch.int32), torch.full((1,), -7, dtype=torch.int32)
+    with pytest.raises(_lib.McnerfError, match=r"mcnerf_cap_gather: idx_in .*no CPU fallback"):
+        _lib.call("mcnerf_cap_gather", idx, perm, 4, idx2, count, 0)
+    params, packed = torch.zeros(64), torch.full((64,), 7, dtype=torch.uint8)
+    with pytest.raises(_lib.McnerfError, match=r"mcnerf_pack_weights_16: packed_fwd .*no CPU fallback"):
+        _lib.call("mcnerf_pack_weights_16", 4, 32, 2, None, packed, packed, 0, None, 0)
+    with pytest.raises(_lib.McnerfError, match=r"mcnerf_pack_weights_16: params .*no CPU fallback"):
+        _lib.call("mcnerf_pack_weights_16", 4, 32, 2, params, packed, packed, 0, None, 0)
+    with pytest.raises(_lib.McnerfError, match=r"mcnerf_errmap_sample: seg_cam .*host array"):           # a tensor at a host-table position
+        _lib.call("mcnerf_errmap_sample", None, 1, 4, 4, 2, torch.zeros(1, dtype=torch.int32), None, 1, 4, 0.5, None, None, None, 0)
+    for args in ((None, None, 0, 4, None), (None, None, 0, 4, None, 0, 0)):                             # (one argument short, one too many)
+        with pytest.raises(ValueError):
+            _lib.call("mcnerf_encode", *args)
+    assert bool((out == -7.0).all()) and bool((idx2 == -7).all()) and int(count) == -7 and bool((packed == 7).all())

@@ -136,7 +136,7 @@ def test_update_equals_the_reference_and_does_not_depend_on_the_order(gpu_device
 # ------------------------------------------------------------------------------------------------------------------ 3. refusals
 def test_refusals_leave_the_output_buffers_untouched(gpu_device):
     from mc_nerf_amd import _lib, ops
-    from mc_nerf_amd.ops import _p, _seg_arrays, _stream
+    from mc_nerf_amd.ops import _seg_arrays, _stream
     H, W, tile, n = 37, 53, 8, 6
     em = _emap(gpu_device, H, W, tile, _maps(H, W, tile, 5)["random"])
     em.cdf.fill_(-7)
@@ -147,14 +147,14 @@ def test_refusals_leave_the_output_buffers_untouched(gpu_device):
 
     def sample(cams=(0, 1), start=(0, 3, 6), n_=n, geom=(C, H, W, tile), frac=0.5, err=True, u_=True, cdf=True, out=True):
         cs, st, K, _ = _seg_arrays(cams, start)
-        q = lambda t, on, dt=torch.float32: _p(t, dt) if on else None
-        _lib.call("mcnerf_errmap_sample", q(em.err, err), *geom, cs, st, K, n_, frac, q(u, u_), q(em.cdf, cdf, torch.int64),
-                  q(pix, out, torch.int64), _stream())
+        q = lambda t, on: t if on else None
+        _lib.call("mcnerf_errmap_sample", q(em.err, err), *geom, cs, st, K, n_, frac, q(u, u_), q(em.cdf, cdf),
+                  q(pix, out), _stream())
 
     def update(cams=(0, 1), start=(0, 3, 6), n_=n, geom=(C, H, W, tile), beta=0.5, omb=0.5, err=True, scratch=True, p=True, c=True, g=True):
         cs, st, K, _ = _seg_arrays(cams, start)
-        q = lambda t, on, dt=torch.float32: _p(t, dt) if on else None
-        _lib.call("mcnerf_errmap_update", q(em.err, err), q(em.scratch, scratch, torch.int32), *geom, cs, st, K, n_, q(pix, p, torch.int64),
+        q = lambda t, on: t if on else None
+        _lib.call("mcnerf_errmap_update", q(em.err, err), q(em.scratch, scratch), *geom, cs, st, K, n_, q(pix, p),
                   q(rgb, c), q(gt, g), beta, omb, _stream())
 
     tables = [dict(cams=(), start=(0,), n_=0), dict(cams=(0,) * 65, start=tuple(range(66)), n_=65), dict(cams=(0, C)), dict(cams=(-1, 1)),

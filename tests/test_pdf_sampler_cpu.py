@@ -126,7 +126,6 @@ def test_sampler_kernel_uses_no_scratch(tmp_path):
 
 def test_abi_declares_the_sampler():
     from mc_nerf_amd import _lib
-    assert _lib.ABI_VERSION == 7 and "mcnerf_sample_pdf" in _lib.SIGNATURES
     hdr = open(os.path.join(ROOT, "include", "mcnerf.h")).read()
-    assert "int mcnerf_sample_pdf(" in hdr and "#define MCNERF_ABI_VERSION 7" in hdr
-    assert _lib.lib().mcnerf_abi_version() == 7
+    assert "int mcnerf_sample_pdf(" in hdr and hasattr(_lib.lib(), "mcnerf_sample_pdf")
+    assert _lib.ABI_VERSION == 7                             # (new symbols only; tests/test_abi_cpu.py checks header, table and library)
