@@ -1,4 +1,4 @@
-"""Builds mc_nerf_amd/libmcnerf.so (hipcc, gfx950 only) in-tree.
+"""Builds mc_nerf_amd/libmcnerf.so and, beside it, the extension library mc_nerf_amd/libmcnext.so (hipcc, gfx950 only) in-tree.
 
     python -m mc_nerf_amd.build [--force]
 
@@ -14,6 +14,12 @@ CSRC = os.path.join(HERE, "csrc")
 OUT = os.path.join(HERE, "libmcnerf.so")
 SOURCES = ["api.hip", "pack.hip", "mlp_fwd.hip", "mlp_bwd.hip", "mlp_dw.hip", "pack16.hip", "mlp16_fwd.hip", "mlp16_bwd.hip", "mlp16_dw.hip", "mlp_x3_fwd.hip", "mlp_x3_bwd.hip", "mlp_x3_dw.hip", "composite.hip", "sample_pdf.hip", "select.hip", "rays.hip", "voxel.hip", "optim.hip", "optim_rows.hip", "camera.hip", "color_calib.hip", "errmap.hip", "lens.hip"]
 HEADERS = ["mcnerf_common.h", "mcnerf_kernels.h", "mcnerf_wave.h", "mcnerf_16.h", "mcnerf_x3.h", "mcnerf_launch.h", "mcnerf_voxel.h", "mcnerf_multicam.h", "mcnerf_colorcal.h", "mcnerf_errmap.h", "mcnerf_maxkey.h", "mcnerf_compact.h", "mcnerf_hash.h", "mcnerf_rays.h", "mcnerf_lens.h", "mcnerf_optim_rows.h", os.path.join("..", "..", "include", "mcnerf.h")]
+# The extension library (include/mcnerf_ext.h): opt-in features whose entry points are not part of the core ABI.  Its
+# objects share the object directory; nothing of it is linked into libmcnerf.so and it links none of the core's objects.
+EXT_OUT = os.path.join(HERE, "libmcnext.so")
+EXT_SOURCES = ["ext_api.hip", "mask.hip"]
+EXT_HEADERS = ["mcnerf_common.h", "mcnerf_wave.h", "mcnerf_multicam.h", "mcnerf_mask.h", os.path.join("..", "..", "include", "mcnerf.h"),
+               os.path.join("..", "..", "include", "mcnerf_ext.h")]
 # the f16x3 chains: a layer body is ~400 MFMAs with its epilogue slices, fully unrolled (beyond hipcc's default pragma-unroll budget);
 # their 256-wide instantiations run one wave per SIMD with 512 registers, where hipcc would otherwise put the MFMA
 # accumulators in AGPRs (every epilogue read then costs a v_accvgpr_read behind a full MFMA drain)
@@ -29,12 +35,18 @@ def _newer(a, b):
 
 
 def build(force=False, verbose=True):
+    """Both libraries; returns the core library's path."""
+    _build_library(EXT_SOURCES, EXT_HEADERS, EXT_OUT, force, verbose)
+    return _build_library(SOURCES, HEADERS, OUT, force, verbose)
+
+
+def _build_library(sources, headers, out, force, verbose):
     hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
     objdir = os.path.join(HERE, "build")
     os.makedirs(objdir, exist_ok=True)
-    hdrs = [os.path.normpath(os.path.join(CSRC, h)) for h in HEADERS]
+    hdrs = [os.path.normpath(os.path.join(CSRC, h)) for h in headers]
     jobs = []
-    for s in SOURCES:
+    for s in sources:
         src, obj = os.path.join(CSRC, s), os.path.join(objdir, s.replace(".hip", ".o"))
         if force or _newer(src, obj) or any(_newer(h, obj) for h in hdrs):
             jobs.append((src, obj))
@@ -53,15 +65,15 @@ def build(force=False, verbose=True):
                 raise RuntimeError(f"hipcc failed on {src}\n{log}")
             if verbose:
                 print(f"[mc_nerf_amd.build] compiled {os.path.basename(src)}")
-    objs = [os.path.join(objdir, s.replace(".hip", ".o")) for s in SOURCES]
-    if jobs or not os.path.exists(OUT):
-        cmd = [hipcc, "--offload-arch=gfx950", "-shared", "-fPIC", "-o", OUT] + objs
+    objs = [os.path.join(objdir, s.replace(".hip", ".o")) for s in sources]
+    if jobs or not os.path.exists(out):
+        cmd = [hipcc, "--offload-arch=gfx950", "-shared", "-fPIC", "-o", out] + objs
         r = subprocess.run(cmd, capture_output=True, text=True)
         if r.returncode != 0:
             raise RuntimeError("link failed\n" + r.stdout + r.stderr)
         if verbose:
-            print(f"[mc_nerf_amd.build] linked {OUT}")
-    return OUT
+            print(f"[mc_nerf_amd.build] linked {out}")
+    return out
 
 
 if __name__ == "__main__":

@@ -21,6 +21,15 @@ def color_calib_settings(sys_param):
     return mode, float(reg)
 
 
+def mask_weight_setting(sys_param):
+    """This build's own sys_param key "mask_weight" (DESIGN.md 4h): the weight lambda >= 0 of the alpha-mask term, a finite float (an
+    int counts, a bool does not); 0.0, the default, is today's path.  A ValueError names the key.  NOT tuned: there is no recommended value."""
+    w = sys_param.get("mask_weight", 0.0)
+    if isinstance(w, bool) or not isinstance(w, (int, float)) or not 0.0 <= w < float("inf"):
+        raise ValueError(f"mask_weight must be a finite float >= 0, got {w!r}")
+    return float(w)
+
+
 class MC_NeRF_Loss(nn.Module):
     def __init__(self, sys_param, tblogger=None):
         super().__init__()
@@ -30,9 +39,17 @@ class MC_NeRF_Loss(nn.Module):
         self.img_h = sys_param["data_img_h"]
         self.img_w = sys_param["data_img_w"]
         self.color_reg = color_calib_settings(sys_param)[1]
+        self.mask_weight = mask_weight_setting(sys_param)
 
     def forward(self, loss_dict, epoch_type):
         self.global_step += 1
+        if "mask" in loss_dict:
+            # mask mode: the other keys exactly as without it, plus the alpha-mask term of the two front weights
+            rest = {k: v for k, v in loss_dict.items() if k != "mask"}
+            return self._terms(rest, epoch_type) + self.get_mask_loss(loss_dict["mask"])
+        return self._terms(loss_dict, epoch_type)
+
+    def _terms(self, loss_dict, epoch_type):
         if set(loss_dict) == {"intr", "rgb"} and loss_dict["rgb"][0].is_cuda:
             # the NeRF stages: reprojection term (rescaled to value 1 outside the camera-only stage, :20-23) + both rgb terms,
             # value and gradients in one launch (csrc/camera.hip: train_loss_kernel)
@@ -70,6 +87,18 @@ class MC_NeRF_Loss(nn.Module):
         if rgb_f is not None:
             loss = loss + F.mse_loss(rgb_f, gt)
         return loss
+
+    def get_mask_loss(self, mask_list, weight=None):
+        """weight * (mean (fg_c - alpha)^2 + mean (fg_f - alpha)^2) of [fg_c, fg_f | None, alpha]: the front weights [N] a mask-mode
+        NeRF_Model keeps in `last_front_weight`, and the drawn pixels' alpha in [0, 1] (a float tensor [N]; MC_Model gathers it from the
+        RGBA image set, a loop that drives NeRF_Model directly supplies it).  `weight` None: the model's "mask_weight".  One launch
+        (render.MaskLossFn); device tensors only.  MSE, not BCE: fg can exceed 1 by roundoff, where BCE's logs are singular."""
+        fg_c, fg_f, alpha = mask_list
+        weight = self.mask_weight if weight is None else float(weight)
+        if not 0.0 <= weight < float("inf"):
+            raise ValueError(f"mask_weight must be a finite float >= 0, got {weight!r}")
+        from .render import MaskLossFn
+        return MaskLossFn.apply(fg_c, fg_f, alpha, weight)
 
     def get_rgb_loss_calibrated(self, rgbs_list, weights_color, cams, seg_start, reg=None):
         """get_rgb_loss with the per-camera colour calibration weights_color [C,6], for loops that drive NeRF_Model

@@ -23,7 +23,7 @@ import torch.distributed as dist
 from .. import ops
 from ..data import DeviceImageSet
 from ..lens import distort_pixels, lens_model_setting
-from .loss import color_calib_settings
+from .loss import color_calib_settings, mask_weight_setting
 from .net_block import CorseFine_NeRF, SinCosEmbedding
 from .render import CameraFn, RayBatchFn, RaygenFn, Rays, RenderCall, RenderSettings, RenderTrainFn, SamplePass, _pool, render_test, run_pass
 
@@ -112,6 +112,11 @@ class NeRF_Model(nn.Module):
                                        float(self.sigma_default), bool(self.white_back), precision=self.precision,
                                        fine_sampler=self.fine_sampler, n_importance=int(self.n_importance),
                                        coarse_sampler=self.coarse_sampler, **voxel_kw)
+        # "mask_weight" is this build's own key as well: lambda > 0 makes each pass's front weight -- the rgb composite's
+        # weights in front of the far-plane sample -- one more differentiable output of the train render, kept for the loss in
+        # `last_front_weight`; 0.0 (the default) is today's path: the extension library is not even loaded
+        self.mask_weight = mask_weight_setting(sys_param)
+        self.last_front_weight = None     # mask mode: (fg_c, fg_f | None) [N] of the last train render, attached to its graph
         self.last_coarse_selection = None  # (idx_c, count_c) of the last pruned coarse pass; None in "dense" mode and in the warm-up
         self.last_selection = None        # (idx, count) of the last fine pass in "threshold" mode; None in "pdf" mode
         self.last_z_all = None            # the fine pass's depth rows [N, samples + n_importance] in "pdf" mode
@@ -235,16 +240,21 @@ class NeRF_Model(nn.Module):
         drawn from torch's device generator in the reference's order.  `fine_sampler = "pdf"`: `u` [N, n_importance] are the
         sampler's U(0,1) draws (drawn after eps_sel), eps_f is [N, samples + n_importance] and cap_perm is not used."""
         N, dev = rays_d.shape[0], rays_d.device
+        want_fg = self.mask_weight > 0.0
+        if want_fg and not rays_d.is_cuda:
+            raise ops._lib.McnerfError(f"mask_weight = {self.mask_weight}: the front weight is a HIP kernel, got rays on {dev} (no CPU fallback)")
         if N == 0:                                  # empty batch: empty results (the reference's tensor ops do the same)
             e3, e1 = rays_d.new_zeros(0, 3), rays_d.new_zeros(0, 1)
+            self.last_front_weight = (rays_d.new_zeros(0), None if only_coarse else rays_d.new_zeros(0)) if want_fg else None
             return (e3, None, e1) if only_coarse else (e3, e3.clone())
         draws = self._draws(N, dev, True, only_coarse, jitter, eps_c, eps_sel, u, eps_f)
         params = self.nerf_coarse.ordered_parameters() + self.nerf_fine.ordered_parameters()
         self.nerf_coarse.flat_params()
         self.nerf_fine.flat_params()
         call = RenderCall(self, self.nerf_coarse, self.nerf_fine, step_r, only_coarse, *draws, cap_perm,
-                          prune=self.settings.voxel and cur_epoch >= self.settings.voxel_warmup_epoch)
-        rgb_c, rgb_f, depth_c = RenderTrainFn.apply(rays_d, rays_o, call, *params)
+                          prune=self.settings.voxel and cur_epoch >= self.settings.voxel_warmup_epoch, want_fg=want_fg)
+        rgb_c, rgb_f, depth_c, fg_c, fg_f = RenderTrainFn.apply(rays_d, rays_o, call, *params)
+        self.last_front_weight = (fg_c, fg_f) if want_fg else None
         return (rgb_c, None, depth_c) if only_coarse else (rgb_c, rgb_f)
 
     @torch.no_grad()
@@ -509,6 +519,9 @@ class MC_Model(nn.Module):
         # one more parameter weights_lens [C,2] = (k1, k2) per training camera, OpenCV's two-coefficient radial model, undistorted inside
         # the NeRF stages' ray kernel (RayBatchFn with its lens input) and applied in closed form to the calibration-tag reprojection
         self.lens_model = lens_model_setting(sys_param)
+        # "mask_weight" is this build's own key too: lambda > 0 adds the alpha-mask term of the renderer's front weights
+        # to the NeRF stages' loss, the alpha of the drawn pixels gathered from the device-resident RGBA images; no parameter
+        self.mask_weight = mask_weight_setting(sys_param)
         self._error_map = None            # ops.ErrorMap, allocated on first use ("error" mode only): not a parameter, not a buffer
         if self.pixel_sampler == "error":
             self.error_tile, self.error_beta, self.error_uniform_frac = self._error_settings(sys_param)
@@ -701,6 +714,12 @@ class MC_Model(nn.Module):
         self.intr_adj, self.pose_adj, self.calib_pose_adj = self.add_weights2param(True, joint, True, intr_wpts, None)
         loss_dict["intr"] = [self._reproject(intr_wpts, self.intr_adj, self.calib_pose_adj, 0), intr_pts]
         error, radial = self.pixel_sampler == "error", self.lens_model == "radial"
+        if self.mask_weight > 0.0:
+            if not self.weights_pose.is_cuda:
+                raise ops._lib.McnerfError(f"mask_weight = {self.mask_weight}: mask supervision runs on the GPU only, the model is on {self.weights_pose.device}")
+            if images is None or images.images.shape[2] != 4:
+                raise ValueError(f"mask_weight = {self.mask_weight} needs a device-resident RGBA image set (DeviceImageSet, 4 channels), got "
+                                 + ("a host float image stack" if images is None else f"{images.images.shape[2]}-channel images"))
         seg_start = ops.ray_segments(self.batch, K)
         if K == 1:      # pixel subset first (same device randperm as :329), rays only for those pixels
             pix = self._draw_error_pixels(cams, seg_start) if error else self.sample_pixels(npix)
@@ -729,6 +748,8 @@ class MC_Model(nn.Module):
         loss_dict["rgb"] = [rgbs_c, rgbs_f, gt]
         if self.color_calib == "affine":
             loss_dict["color"] = [self.weights_color, cams, seg_start]
+        if self.mask_weight > 0.0:
+            loss_dict["mask"] = [*self.nerf.last_front_weight, ops.gather_alpha(images.images, cams, seg_start, pix.contiguous())]
         self.opt_idx = 1 if joint else 2
         if K > 1 or error:
             self.last_step_segments, self.last_step_pix = (cams, seg_start), pix

@@ -202,12 +202,23 @@ def run_pass(p: SamplePass, st: RenderSettings, rays: Rays, lease: Optional[Work
     return ops.composite_fwd(p.out, rays.d, p.zgrid, p.jitter, p.eps, eps_sel, st.white_back, want_depth=want_depth, z_rows=p.z_rows)
 
 
-def pass_backward(p: SamplePass, st: RenderSettings, rays: Rays, d_rgb, grads, d_o, d_d, lease: WorkspaceLease):
+def front_weight(p: SamplePass):
+    """fg [N] of a pass that `run_pass` has composited (ops.front_weight: the rgb composite's weights in front of the far-plane sample)."""
+    return ops.front_weight(p.out, p.zgrid, p.jitter, p.eps, z_rows=p.z_rows)
+
+
+def pass_backward(p: SamplePass, st: RenderSettings, rays: Rays, d_rgb, grads, d_o, d_d, lease: WorkspaceLease, d_fg=None):
     """The pass's composite backward, dX chain (into d_o / d_d [N,3] when given) and weight gradients (into `grads`); nothing when
-    `d_rgb` is None.  Either way the pass's saved-operand set goes back to the pool."""
+    `d_rgb` and `d_fg` are None.  Either way the pass's saved-operand set goes back to the pool.  `d_fg` [N] (mask mode): the gradient
+    on the pass's front weight; the composite backward is then the extension library's, which takes both (d_rgb None: zeros)."""
     net = p.model.net
-    if d_rgb is not None:
-        d_out, gmax = ops.composite_bwd(p.out, p.zgrid, p.jitter, p.eps, d_rgb.contiguous(), st.white_back, want_gmax=True, z_rows=p.z_rows)
+    if d_rgb is not None or d_fg is not None:
+        if d_fg is not None:
+            d_rgb = torch.zeros(p.out.shape[0], 3, dtype=torch.float32, device=p.out.device) if d_rgb is None else d_rgb.contiguous()
+            d_out, gmax = ops.composite_bwd_front(p.out, p.zgrid, p.jitter, p.eps, d_rgb, d_fg.contiguous(), st.white_back,
+                                                  want_gmax=True, z_rows=p.z_rows)
+        else:
+            d_out, gmax = ops.composite_bwd(p.out, p.zgrid, p.jitter, p.eps, d_rgb.contiguous(), st.white_back, want_gmax=True, z_rows=p.z_rows)
         dy, dsh = ws = lease.take_grad(net, p.save)
         ops.mlp_bwd(net, p.flat, p.packed, rays.o, rays.d, p.zgrid, p.jitter, rays.barf_w, p.out, d_out, p.save, dy, dsh,
                     d_o, d_d, idx=p.idx, count=p.count, max_rows=p.max_rows, precision=st.precision, gmax=gmax, z_rows=p.z_rows)
@@ -274,11 +285,13 @@ def _packed(model, flat, st: RenderSettings, dev):
 
 # Everything non-differentiable of one RenderTrainFn call.  `prune` (read in "voxel" mode only): True = the coarse net runs on the
 # grid's (ray, sample) list, False = the warm-up's dense pass; either way the grid is then updated from the evaluated samples.
-RenderCall = namedtuple("RenderCall", "owner model_c model_f step_r only_coarse jitter eps_c eps_sel u eps_f cap_perm prune")
+# `want_fg` (mask mode): each pass's front weight is one more differentiable output.
+RenderCall = namedtuple("RenderCall", "owner model_c model_f step_r only_coarse jitter eps_c eps_sel u eps_f cap_perm prune want_fg", defaults=(False,))
 
 
 class RenderTrainFn(torch.autograd.Function):
-    """rgb_c, rgb_f, depth_c = f(rays_d, rays_o, call, *coarse_params, *fine_params); `call` (RenderCall) holds the explicit draws."""
+    """rgb_c, rgb_f, depth_c, fg_c, fg_f = f(rays_d, rays_o, call, *coarse_params, *fine_params); `call` (RenderCall) holds the explicit
+    draws.  fg_c / fg_f [N]: the passes' front weights with `call.want_fg`, else None (and nothing of the extension library runs)."""
 
     @staticmethod
     def forward(ctx, rays_d, rays_o, call: RenderCall, *params):
@@ -292,15 +305,17 @@ class RenderTrainFn(torch.autograd.Function):
             coarse = coarse_pass(owner, call.model_c, flat_c, _packed(call.model_c, flat_c, st, dev), rays, jit, call.eps_c, call.prune)
             rgb_c, depth_c, _, w_sel, wmax = run_pass(coarse, st, rays, saving, None if call.only_coarse else call.eps_sel,
                                                       want_depth=call.only_coarse)
+            fg_c = front_weight(coarse) if call.want_fg else None
             if st.voxel:
                 ops.voxel_update(owner.voxel_grid(), st.voxel_beta, rays.o, rays.d, coarse.zgrid, jit, coarse.out,
                                  coarse.idx, coarse.count, coarse.max_rows)
-            passes, rgb_f = [coarse], None
+            passes, rgb_f, fg_f = [coarse], None, None
             if not call.only_coarse:
                 flat_f = call.model_f.flat_params()
                 fine = fine_pass(owner, call.model_f, flat_f, _packed(call.model_f, flat_f, st, dev), rays, jit, w_sel, wmax,
                                  call.eps_f, call.u, call.cap_perm, train=True)
                 rgb_f = run_pass(fine, st, rays, saving)[0]
+                fg_f = front_weight(fine) if call.want_fg else None
                 passes.append(fine)
         if need_grad:                                       # the lease, with the sets it holds, waits in ctx for the backward
             ctx.owner, ctx.model_f, ctx.lease = owner, call.model_f, lease          # (not `call`: it would keep every draw alive)
@@ -308,10 +323,10 @@ class RenderTrainFn(torch.autograd.Function):
             ctx.save_for_backward(*rays, *(t for p in passes for t in p.tensors()))
         if depth_c is not None:                             # (only_coarse; rgb_f is None then)
             ctx.mark_non_differentiable(depth_c)
-        return rgb_c, rgb_f, depth_c
+        return rgb_c, rgb_f, depth_c, fg_c, fg_f
 
     @staticmethod
-    def backward(ctx, d_rgb_c, d_rgb_f, _d_depth):
+    def backward(ctx, d_rgb_c, d_rgb_f, _d_depth, d_fg_c=None, d_fg_f=None):
         if getattr(ctx, "workspaces_given_back", False):
             # retain_graph=True + a second backward: the saved-operand set went back to the pool after the first one and the next
             # forward may already have overwritten it -- refuse instead of returning gradients of clobbered operands
@@ -339,8 +354,8 @@ class RenderTrainFn(torch.autograd.Function):
         with lease:
             for p in fine:                                  # (none after an only_coarse call)
                 g_f = arena[n_c:n_c + n_f] if arena is not None else torch.zeros_like(p.flat)
-                pass_backward(p, st, rays, d_rgb_f, g_f, d_o, d_d, lease)
-            pass_backward(coarse, st, rays, d_rgb_c, g_c, d_o, d_d, lease)
+                pass_backward(p, st, rays, d_rgb_f, g_f, d_o, d_d, lease, d_fg_f)
+            pass_backward(coarse, st, rays, d_rgb_c, g_c, d_o, d_d, lease, d_fg_c)
         grads_c = coarse.model.grad_views(g_c)
         grads_f = model_f.grad_views(g_f) if g_f is not None else [None] * len(model_f.ordered_parameters())
         owner.last_flat_grads = (g_c, g_f)
@@ -483,6 +498,34 @@ class TrainLossCalibFn(torch.autograd.Function):
         ops.scale3_(None, d_color, None, g)
         ctx.grads = None
         return d_pd, None, d_c, d_f, None, d_color, None, None, None, None, None, None
+
+
+class MaskLossFn(torch.autograd.Function):
+    """weight * (mean (fg_c - alpha)^2 + mean (fg_f - alpha)^2) (csrc/mask.hip), value and both gradients in ONE launch of
+    the extension library; backward scales the saved gradients by the upstream scalar on the device.  `fg_f` may be None (only_coarse);
+    `alpha` [n] is a constant.  An empty batch is a zero that carries no gradient."""
+
+    @staticmethod
+    def forward(ctx, fg_c, fg_f, alpha, weight):
+        cf = lambda t: None if t is None else t.contiguous().float().reshape(-1)
+        ctx.shapes = (fg_c.shape, None if fg_f is None else fg_f.shape)
+        fg_c, fg_f, alpha = cf(fg_c), cf(fg_f), cf(alpha)
+        ctx.grads = None
+        if fg_c.numel() == 0:
+            return fg_c.new_zeros(())
+        out, d_c, d_f = ops.mask_loss(fg_c, fg_f, alpha, weight)
+        ctx.grads = (d_c, d_f)
+        ctx.parts = out
+        return out[0]
+
+    @staticmethod
+    def backward(ctx, g):
+        if ctx.grads is None:
+            return None, None, None, None
+        d_c, d_f = ctx.grads
+        ops.scale3_(None, d_c, d_f, g.contiguous().float().reshape(1))
+        ctx.grads = None
+        return d_c.reshape(ctx.shapes[0]), None if d_f is None else d_f.reshape(ctx.shapes[1]), None, None
 
 
 class ReprojLossFn(torch.autograd.Function):

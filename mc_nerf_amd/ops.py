@@ -12,7 +12,7 @@ from typing import Optional, Tuple
 
 import torch
 
-from . import _lib
+from . import _ext, _lib
 
 Tensor = torch.Tensor
 
@@ -26,6 +26,8 @@ ERRMAP_MAX_PIXELS = _lib.DEFINES["MCNERF_ERRMAP_MAX_PIXELS"]        # H * W of o
 TRAIN_LOSS_OUT = _lib.DEFINES["MCNERF_TRAIN_LOSS_OUT"]
 TRAIN_LOSS_CALIB_OUT = _lib.DEFINES["MCNERF_TRAIN_LOSS_CALIB_OUT"]
 TRAIN_LOSS_CALIB_WS = _lib.DEFINES["MCNERF_TRAIN_LOSS_CALIB_WS"]
+# ... and include/mcnerf_ext.h, the extension library's header (`_ext`: loaded on the first call of one of its entry points)
+MASK_LOSS_OUT = _ext.DEFINES["MCNERF_EXT_MASK_LOSS_OUT"]
 
 
 def skip_code(skips, depth: int, deg: int = 2, n_freqs: int = 10) -> int:
@@ -550,6 +552,54 @@ def composite_bwd(sig_rgb: Tensor, zgrid: Tensor, jitter: Optional[Tensor], eps:
     _lib.call("mcnerf_composite_bwd", sig_rgb, zgrid, zs, jitter, eps, d_rgb, N, S,
               int(bool(white_back)), d, gmax, _stream())
     return (d, gmax) if want_gmax else d
+
+
+# --------------------------------------------------------------------------- alpha-mask supervision (the extension library)
+def front_weight(sig_rgb: Tensor, zgrid: Tensor, jitter: Optional[Tensor], eps: Tensor, *, z_rows: Optional[Tensor] = None) -> Tensor:
+    """-> fg [N] = sum_{j < S-1} w_j of the rgb composite's weights of `composite_fwd` on the same inputs: every weight but the
+    far-plane sample's (delta = 1e10), which takes whatever transmittance is left."""
+    N = sig_rgb.shape[0]
+    zgrid, S, zs = _depths(zgrid, z_rows, N)
+    fg = torch.empty(N, dtype=torch.float32, device=sig_rgb.device)
+    _ext.call("mcnerf_ext_front_weight", sig_rgb, zgrid, zs, jitter, eps, N, S, fg, _stream())
+    return fg
+
+
+def composite_bwd_front(sig_rgb: Tensor, zgrid: Tensor, jitter: Optional[Tensor], eps: Tensor, d_rgb: Tensor, d_fg: Optional[Tensor],
+                        white_back: bool = True, want_gmax: bool = False, *, z_rows: Optional[Tensor] = None):
+    """`composite_bwd` of  sum rgb * d_rgb + sum fg * d_fg  (d_fg [N]); with d_fg None the bits of `composite_bwd`."""
+    N = d_rgb.shape[0]
+    zgrid, S, zs = _depths(zgrid, z_rows, N)
+    d = torch.empty(N, S, 4, dtype=torch.float32, device=d_rgb.device)
+    gmax = torch.zeros(1, dtype=torch.int32, device=d_rgb.device) if want_gmax else None
+    _ext.call("mcnerf_ext_composite_bwd_front", sig_rgb, zgrid, zs, jitter, eps, d_rgb, d_fg, N, S,
+              int(bool(white_back)), d, gmax, _stream())
+    return (d, gmax) if want_gmax else d
+
+
+def gather_alpha(images_u8: Tensor, seg_cam, seg_start, pix: Tensor) -> Tensor:
+    """images_u8 [C, H*W, 3|4] uint8 on the device, pix [n] int64 (segment k = rays [seg_start[k], seg_start[k+1]) of camera
+    seg_cam[k]; host lists) -> alpha [n] fp32 = a / 255 of the drawn pixels, ones for 3-channel images."""
+    cams, start, K, n = _seg_arrays(seg_cam, seg_start)
+    if images_u8.dim() != 3 or pix.numel() != n:
+        raise _lib.McnerfError(f"images must be [C, H*W, channels] and pix must hold seg_start[-1] = {n} ids, got {tuple(images_u8.shape)}, {pix.numel()}")
+    alpha = torch.empty(n, dtype=torch.float32, device=pix.device)
+    _ext.call("mcnerf_ext_gather_alpha", images_u8, int(images_u8.shape[0]), int(images_u8.shape[1]), int(images_u8.shape[2]),
+              cams, start, K, pix, n, alpha, _stream())
+    return alpha
+
+
+def mask_loss(fg_c: Tensor, fg_f: Optional[Tensor], alpha: Tensor, weight: float):
+    """-> out [2] = (weight * m, m), m = mean (fg_c - alpha)^2 + mean (fg_f - alpha)^2, and d_fg_c, d_fg_f | None =
+    (2 weight / n) (fg - alpha); one launch, deterministic."""
+    n = fg_c.numel()
+    if alpha.numel() != n or (fg_f is not None and fg_f.numel() != n):
+        raise _lib.McnerfError(f"fg_c, fg_f and alpha must hold the same {n} rays")
+    out = torch.zeros(MASK_LOSS_OUT, dtype=torch.float32, device=fg_c.device)      # [3] = the kernel's arrival counter: zero on entry
+    d_c = torch.empty_like(fg_c)
+    d_f = torch.empty_like(fg_f) if fg_f is not None else None
+    _ext.call("mcnerf_ext_mask_loss", fg_c, fg_f, alpha, n, float(weight), out, d_c, d_f, _stream())
+    return out[:2], d_c, d_f
 
 
 def _list_buffers(N: int, S: int, prefill: bool, idx: Optional[Tensor], dev):

@@ -260,10 +260,8 @@ BLOB_COLORS = ((0.9, 0.15, 0.1), (0.1, 0.7, 0.2), (0.15, 0.25, 0.9))
 BLOB_DENSITY = 18.0
 
 
-@torch.no_grad()
-def blob_scene_render(rays_d, rays_o, near=1.0, far=8.0, n_quad=384):
-    """Ground-truth colour [M,3] of the blob scene along rays (white background), the reference's compositing rule
-    (model/mc_nerf.py:729-736 without noise) on a dense uniform quadrature."""
+def _blob_quadrature(rays_d, rays_o, near, far, n_quad):
+    """(weights [M,n_quad], colours [M,n_quad,3]) of the blob scene's dense uniform quadrature along rays."""
     dev = rays_d.device
     cen, sg, col = (torch.tensor(v, device=dev) for v in (BLOB_CENTERS, BLOB_SIGMAS, BLOB_COLORS))
     z = torch.linspace(near, far, n_quad, device=dev)
@@ -272,8 +270,22 @@ def blob_scene_render(rays_d, rays_o, near=1.0, far=8.0, n_quad=384):
     sig, c = BLOB_DENSITY * w.sum(-1), (w.unsqueeze(-1) * col).sum(-2) / (w.sum(-1, keepdim=True) + 1e-8)
     alpha = 1 - torch.exp(-sig * (far - near) / (n_quad - 1))
     T = torch.cumprod(torch.cat([torch.ones_like(alpha[:, :1]), 1 - alpha + 1e-10], 1), 1)[:, :-1]
-    wt = alpha * T
+    return alpha * T, c
+
+
+@torch.no_grad()
+def blob_scene_render(rays_d, rays_o, near=1.0, far=8.0, n_quad=384):
+    """Ground-truth colour [M,3] of the blob scene along rays (white background), the reference's compositing rule
+    (model/mc_nerf.py:729-736 without noise) on a dense uniform quadrature."""
+    wt, c = _blob_quadrature(rays_d, rays_o, near, far, n_quad)
     return (wt.unsqueeze(-1) * c).sum(1) + (1 - wt.sum(1, keepdim=True))
+
+
+@torch.no_grad()
+def blob_scene_alpha(rays_d, rays_o, near=1.0, far=8.0, n_quad=384):
+    """Ground-truth alpha [M] of the blob scene along rays: the sum of `blob_scene_render`'s quadrature weights (what its white
+    background is blended with 1 - of), the mask an RGBA image of the scene carries."""
+    return _blob_quadrature(rays_d, rays_o, near, far, n_quad)[0].sum(1)
 
 
 @torch.no_grad()
@@ -314,6 +326,29 @@ def blob_scene_images(pose, K, H, W, chunk=8192, lens=None):
             d, o = ops.raygen_fwd(pose[i].contiguous(), Kinv[i].contiguous(), allpix, W)
         out.append(torch.cat([blob_scene_render(d[j:j + chunk], o[j:j + chunk]) for j in range(0, H * W, chunk)]))
     return torch.stack(out)
+
+
+@torch.no_grad()
+def blob_scene_alpha_images(pose, K, H, W, chunk=8192):
+    """[C, H*W] ground-truth alpha of the blob scene for the pinhole cameras of `blob_scene_images` (same rays): with its colours,
+    `blob_scene_rgba` packs the RGBA uint8 stack a DeviceImageSet takes."""
+    from . import ops
+    Kinv = torch.linalg.inv(K)
+    allpix = torch.arange(H * W, device=pose.device)
+    out = []
+    for i in range(pose.shape[0]):
+        d, o = ops.raygen_fwd(pose[i].contiguous(), Kinv[i].contiguous(), allpix, W)
+        out.append(torch.cat([blob_scene_alpha(d[j:j + chunk], o[j:j + chunk]) for j in range(0, H * W, chunk)]))
+    return torch.stack(out)
+
+
+def blob_scene_rgba(images: torch.Tensor, alpha: torch.Tensor) -> torch.Tensor:
+    """uint8 [C, H*W, 4] from the white-blended colours `images` [C, H*W, 3] and `alpha` [C, H*W]: the straight (un-premultiplied)
+    colour (rgb - (1 - a)) / a and round(255 a), so that blending the stored pixel on white (csrc/mcnerf_rays.h) gives `images` back
+    to the 8-bit rounding; colour 1 where a rounds to 0."""
+    a = alpha.clamp(0.0, 1.0).unsqueeze(-1)
+    straight = torch.where(a > 0.5 / 255.0, (images - (1.0 - a)) / a.clamp_min(1e-6), torch.ones_like(images)).clamp(0.0, 1.0)
+    return torch.cat([straight, a], -1).mul(255.0).round().to(torch.uint8)
 
 
 def camera_color_response(C: int, seed: int = 0, gain_spread: float = 0.15, bias_spread: float = 0.03):
