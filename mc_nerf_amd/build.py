@@ -1,4 +1,5 @@
-"""Builds mc_nerf_amd/libmcnerf.so and, beside it, the extension library mc_nerf_amd/libmcnext.so (hipcc, gfx950 only) in-tree.
+"""Builds mc_nerf_amd/libmcnerf.so and, beside it, the extension library mc_nerf_amd/libmcnext.so and the regulariser library
+mc_nerf_amd/libmcnreg.so (hipcc, gfx950 only) in-tree.
 
     python -m mc_nerf_amd.build [--force]
 
@@ -20,6 +21,11 @@ EXT_OUT = os.path.join(HERE, "libmcnext.so")
 EXT_SOURCES = ["ext_api.hip", "mask.hip"]
 EXT_HEADERS = ["mcnerf_common.h", "mcnerf_wave.h", "mcnerf_multicam.h", "mcnerf_mask.h", os.path.join("..", "..", "include", "mcnerf.h"),
                os.path.join("..", "..", "include", "mcnerf_ext.h")]
+# The regulariser library (include/mcnerf_reg.h): the extension library's ABI is pinned too, so the distortion loss has
+# a third library, built the same way.  None of its objects is linked into the other two and it links none of theirs.
+REG_OUT = os.path.join(HERE, "libmcnreg.so")
+REG_SOURCES = ["reg_api.hip", "distortion.hip"]
+REG_HEADERS = ["mcnerf_common.h", "mcnerf_wave.h", "mcnerf_distortion.h", os.path.join("..", "..", "include", "mcnerf_reg.h")]
 # the f16x3 chains: a layer body is ~400 MFMAs with its epilogue slices, fully unrolled (beyond hipcc's default pragma-unroll budget);
 # their 256-wide instantiations run one wave per SIMD with 512 registers, where hipcc would otherwise put the MFMA
 # accumulators in AGPRs (every epilogue read then costs a v_accvgpr_read behind a full MFMA drain)
@@ -35,8 +41,9 @@ def _newer(a, b):
 
 
 def build(force=False, verbose=True):
-    """Both libraries; returns the core library's path."""
+    """All three libraries; returns the core library's path."""
     _build_library(EXT_SOURCES, EXT_HEADERS, EXT_OUT, force, verbose)
+    _build_library(REG_SOURCES, REG_HEADERS, REG_OUT, force, verbose)
     return _build_library(SOURCES, HEADERS, OUT, force, verbose)
 
 

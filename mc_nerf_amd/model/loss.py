@@ -30,6 +30,15 @@ def mask_weight_setting(sys_param):
     return float(w)
 
 
+def dist_weight_setting(sys_param):
+    """This build's own sys_param key "dist_weight" (DESIGN.md 4i): the weight lambda >= 0 of the distortion term, a finite float (an
+    int counts, a bool does not); 0.0, the default, is today's path.  A ValueError names the key.  NOT tuned: there is no recommended value."""
+    w = sys_param.get("dist_weight", 0.0)
+    if isinstance(w, bool) or not isinstance(w, (int, float)) or not 0.0 <= w < float("inf"):
+        raise ValueError(f"dist_weight must be a finite float >= 0, got {w!r}")
+    return float(w)
+
+
 class MC_NeRF_Loss(nn.Module):
     def __init__(self, sys_param, tblogger=None):
         super().__init__()
@@ -40,9 +49,17 @@ class MC_NeRF_Loss(nn.Module):
         self.img_w = sys_param["data_img_w"]
         self.color_reg = color_calib_settings(sys_param)[1]
         self.mask_weight = mask_weight_setting(sys_param)
+        self.dist_weight = dist_weight_setting(sys_param)
 
     def forward(self, loss_dict, epoch_type):
         self.global_step += 1
+        if "dist" in loss_dict:
+            # distortion mode: the other keys exactly as without it (the mask term included), plus the distortion term
+            rest = {k: v for k, v in loss_dict.items() if k not in ("dist", "mask")}
+            loss = self._terms(rest, epoch_type)
+            if "mask" in loss_dict:
+                loss = loss + self.get_mask_loss(loss_dict["mask"])
+            return loss + self.get_distortion_loss(loss_dict["dist"])
         if "mask" in loss_dict:
             # mask mode: the other keys exactly as without it, plus the alpha-mask term of the two front weights
             rest = {k: v for k, v in loss_dict.items() if k != "mask"}
@@ -99,6 +116,21 @@ class MC_NeRF_Loss(nn.Module):
             raise ValueError(f"mask_weight must be a finite float >= 0, got {weight!r}")
         from .render import MaskLossFn
         return MaskLossFn.apply(fg_c, fg_f, alpha, weight)
+
+    def get_distortion_loss(self, dist_list, weight=None):
+        """weight * (dist_c.mean() + dist_f.mean()) of [dist_c, dist_f | None]: the per-ray distortion terms [N] a distortion-mode
+        NeRF_Model keeps in `last_distortion`.  `weight` None: the model's "dist_weight".  Plain torch on the tensors' device; an empty
+        ray set gives a zero that carries no gradient."""
+        dist_c, dist_f = dist_list
+        weight = self.dist_weight if weight is None else float(weight)
+        if not 0.0 <= weight < float("inf"):
+            raise ValueError(f"dist_weight must be a finite float >= 0, got {weight!r}")
+        if dist_c.numel() == 0:
+            return dist_c.new_zeros(())
+        total = dist_c.mean()
+        if dist_f is not None:
+            total = total + dist_f.mean()
+        return weight * total
 
     def get_rgb_loss_calibrated(self, rgbs_list, weights_color, cams, seg_start, reg=None):
         """get_rgb_loss with the per-camera colour calibration weights_color [C,6], for loops that drive NeRF_Model

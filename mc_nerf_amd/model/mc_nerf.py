@@ -23,7 +23,7 @@ import torch.distributed as dist
 from .. import ops
 from ..data import DeviceImageSet
 from ..lens import distort_pixels, lens_model_setting
-from .loss import color_calib_settings, mask_weight_setting
+from .loss import color_calib_settings, dist_weight_setting, mask_weight_setting
 from .net_block import CorseFine_NeRF, SinCosEmbedding
 from .render import CameraFn, RayBatchFn, RaygenFn, Rays, RenderCall, RenderSettings, RenderTrainFn, SamplePass, _pool, render_test, run_pass
 
@@ -117,6 +117,11 @@ class NeRF_Model(nn.Module):
         # `last_front_weight`; 0.0 (the default) is today's path: the extension library is not even loaded
         self.mask_weight = mask_weight_setting(sys_param)
         self.last_front_weight = None     # mask mode: (fg_c, fg_f | None) [N] of the last train render, attached to its graph
+        # "dist_weight" is this build's own key too: lambda > 0 makes each pass's distortion term -- mip-NeRF 360's, on the
+        # rgb composite's weights over the normalised depths -- one more differentiable output of the train render, kept for the loss in
+        # `last_distortion`; 0.0 (the default) is today's path: the regulariser library is not even loaded
+        self.dist_weight = dist_weight_setting(sys_param)
+        self.last_distortion = None       # distortion mode: (dist_c, dist_f | None) [N] of the last train render, attached to its graph
         self.last_coarse_selection = None  # (idx_c, count_c) of the last pruned coarse pass; None in "dense" mode and in the warm-up
         self.last_selection = None        # (idx, count) of the last fine pass in "threshold" mode; None in "pdf" mode
         self.last_z_all = None            # the fine pass's depth rows [N, samples + n_importance] in "pdf" mode
@@ -243,18 +248,24 @@ class NeRF_Model(nn.Module):
         want_fg = self.mask_weight > 0.0
         if want_fg and not rays_d.is_cuda:
             raise ops._lib.McnerfError(f"mask_weight = {self.mask_weight}: the front weight is a HIP kernel, got rays on {dev} (no CPU fallback)")
+        want_dist = self.dist_weight > 0.0
+        if want_dist and not rays_d.is_cuda:
+            raise ops._lib.McnerfError(f"dist_weight = {self.dist_weight}: the distortion term is a HIP kernel, got rays on {dev} (no CPU fallback)")
         if N == 0:                                  # empty batch: empty results (the reference's tensor ops do the same)
             e3, e1 = rays_d.new_zeros(0, 3), rays_d.new_zeros(0, 1)
             self.last_front_weight = (rays_d.new_zeros(0), None if only_coarse else rays_d.new_zeros(0)) if want_fg else None
+            self.last_distortion = (rays_d.new_zeros(0), None if only_coarse else rays_d.new_zeros(0)) if want_dist else None
             return (e3, None, e1) if only_coarse else (e3, e3.clone())
         draws = self._draws(N, dev, True, only_coarse, jitter, eps_c, eps_sel, u, eps_f)
         params = self.nerf_coarse.ordered_parameters() + self.nerf_fine.ordered_parameters()
         self.nerf_coarse.flat_params()
         self.nerf_fine.flat_params()
         call = RenderCall(self, self.nerf_coarse, self.nerf_fine, step_r, only_coarse, *draws, cap_perm,
-                          prune=self.settings.voxel and cur_epoch >= self.settings.voxel_warmup_epoch, want_fg=want_fg)
-        rgb_c, rgb_f, depth_c, fg_c, fg_f = RenderTrainFn.apply(rays_d, rays_o, call, *params)
+                          prune=self.settings.voxel and cur_epoch >= self.settings.voxel_warmup_epoch, want_dist=want_dist,
+                          want_fg=want_fg)
+        rgb_c, rgb_f, depth_c, fg_c, fg_f, dist_c, dist_f = RenderTrainFn.apply(rays_d, rays_o, call, *params)
         self.last_front_weight = (fg_c, fg_f) if want_fg else None
+        self.last_distortion = (dist_c, dist_f) if want_dist else None
         return (rgb_c, None, depth_c) if only_coarse else (rgb_c, rgb_f)
 
     @torch.no_grad()
@@ -522,6 +533,9 @@ class MC_Model(nn.Module):
         # "mask_weight" is this build's own key too: lambda > 0 adds the alpha-mask term of the renderer's front weights
         # to the NeRF stages' loss, the alpha of the drawn pixels gathered from the device-resident RGBA images; no parameter
         self.mask_weight = mask_weight_setting(sys_param)
+        # "dist_weight" likewise: lambda > 0 adds the distortion term of the renderer's two passes to the NeRF stages'
+        # loss; no parameter, no extra data
+        self.dist_weight = dist_weight_setting(sys_param)
         self._error_map = None            # ops.ErrorMap, allocated on first use ("error" mode only): not a parameter, not a buffer
         if self.pixel_sampler == "error":
             self.error_tile, self.error_beta, self.error_uniform_frac = self._error_settings(sys_param)
@@ -720,6 +734,8 @@ class MC_Model(nn.Module):
             if images is None or images.images.shape[2] != 4:
                 raise ValueError(f"mask_weight = {self.mask_weight} needs a device-resident RGBA image set (DeviceImageSet, 4 channels), got "
                                  + ("a host float image stack" if images is None else f"{images.images.shape[2]}-channel images"))
+        if self.dist_weight > 0.0 and not self.weights_pose.is_cuda:
+            raise ops._lib.McnerfError(f"dist_weight = {self.dist_weight}: the distortion term runs on the GPU only, the model is on {self.weights_pose.device}")
         seg_start = ops.ray_segments(self.batch, K)
         if K == 1:      # pixel subset first (same device randperm as :329), rays only for those pixels
             pix = self._draw_error_pixels(cams, seg_start) if error else self.sample_pixels(npix)
@@ -750,6 +766,8 @@ class MC_Model(nn.Module):
             loss_dict["color"] = [self.weights_color, cams, seg_start]
         if self.mask_weight > 0.0:
             loss_dict["mask"] = [*self.nerf.last_front_weight, ops.gather_alpha(images.images, cams, seg_start, pix.contiguous())]
+        if self.dist_weight > 0.0:
+            loss_dict["dist"] = [*self.nerf.last_distortion]
         self.opt_idx = 1 if joint else 2
         if K > 1 or error:
             self.last_step_segments, self.last_step_pix = (cams, seg_start), pix

@@ -174,8 +174,9 @@ class SamplePass:
     count: Optional[torch.Tensor] = None
     max_rows: int = 0
     save: Optional[ops.MlpSave] = None
+    moments: Optional[torch.Tensor] = None      # distortion mode: ops.distortion_fwd's per-ray sums, for the backward
 
-    TENSORS = ("flat", "packed", "zgrid", "jitter", "z_rows", "eps", "out", "idx", "count")
+    TENSORS = ("flat", "packed", "zgrid", "jitter", "z_rows", "eps", "out", "idx", "count", "moments")
 
     @property
     def rows(self) -> int:
@@ -207,13 +208,27 @@ def front_weight(p: SamplePass):
     return ops.front_weight(p.out, p.zgrid, p.jitter, p.eps, z_rows=p.z_rows)
 
 
-def pass_backward(p: SamplePass, st: RenderSettings, rays: Rays, d_rgb, grads, d_o, d_d, lease: WorkspaceLease, d_fg=None):
+def distortion(p: SamplePass, span):
+    """dist [N] of a pass that `run_pass` has composited (ops.distortion_fwd on the depth range `span` = (near, far)); the per-ray sums
+    its backward needs stay with the pass."""
+    dist, p.moments = ops.distortion_fwd(p.out, p.zgrid, p.jitter, p.eps, *span, z_rows=p.z_rows)
+    return dist
+
+
+def pass_backward(p: SamplePass, st: RenderSettings, rays: Rays, d_rgb, grads, d_o, d_d, lease: WorkspaceLease, d_fg=None, d_dist=None,
+                  span=None):
     """The pass's composite backward, dX chain (into d_o / d_d [N,3] when given) and weight gradients (into `grads`); nothing when
-    `d_rgb` and `d_fg` are None.  Either way the pass's saved-operand set goes back to the pool.  `d_fg` [N] (mask mode): the gradient
-    on the pass's front weight; the composite backward is then the extension library's, which takes both (d_rgb None: zeros)."""
+    `d_rgb`, `d_fg` and `d_dist` are None.  Either way the pass's saved-operand set goes back to the pool.  `d_fg` [N] (mask mode): the
+    gradient on the pass's front weight; the composite backward is then the extension library's, which takes both (d_rgb None: zeros).
+    `d_dist` [N] (distortion mode, with `span` = (near, far)): the gradient on the pass's distortion term; the composite backward is
+    then the regulariser library's, which takes all three."""
     net = p.model.net
-    if d_rgb is not None or d_fg is not None:
-        if d_fg is not None:
+    if d_rgb is not None or d_fg is not None or d_dist is not None:
+        if d_dist is not None:
+            d_rgb = torch.zeros(p.out.shape[0], 3, dtype=torch.float32, device=p.out.device) if d_rgb is None else d_rgb.contiguous()
+            d_out, gmax = ops.composite_bwd_w(p.out, p.zgrid, p.jitter, p.eps, d_rgb, None if d_fg is None else d_fg.contiguous(),
+                                              d_dist.contiguous(), p.moments, *span, st.white_back, want_gmax=True, z_rows=p.z_rows)
+        elif d_fg is not None:
             d_rgb = torch.zeros(p.out.shape[0], 3, dtype=torch.float32, device=p.out.device) if d_rgb is None else d_rgb.contiguous()
             d_out, gmax = ops.composite_bwd_front(p.out, p.zgrid, p.jitter, p.eps, d_rgb, d_fg.contiguous(), st.white_back,
                                                   want_gmax=True, z_rows=p.z_rows)
@@ -285,13 +300,17 @@ def _packed(model, flat, st: RenderSettings, dev):
 
 # Everything non-differentiable of one RenderTrainFn call.  `prune` (read in "voxel" mode only): True = the coarse net runs on the
 # grid's (ray, sample) list, False = the warm-up's dense pass; either way the grid is then updated from the evaluated samples.
-# `want_fg` (mask mode): each pass's front weight is one more differentiable output.
-RenderCall = namedtuple("RenderCall", "owner model_c model_f step_r only_coarse jitter eps_c eps_sel u eps_f cap_perm prune want_fg", defaults=(False,))
+# `want_fg` (mask mode): each pass's front weight is one more differentiable output.  `want_dist` (distortion mode,
+# DESIGN.md 4i): so is each pass's distortion term.
+RenderCall = namedtuple("RenderCall", "owner model_c model_f step_r only_coarse jitter eps_c eps_sel u eps_f cap_perm prune want_dist want_fg",
+                        defaults=(False, False))
 
 
 class RenderTrainFn(torch.autograd.Function):
-    """rgb_c, rgb_f, depth_c, fg_c, fg_f = f(rays_d, rays_o, call, *coarse_params, *fine_params); `call` (RenderCall) holds the explicit
-    draws.  fg_c / fg_f [N]: the passes' front weights with `call.want_fg`, else None (and nothing of the extension library runs)."""
+    """rgb_c, rgb_f, depth_c, fg_c, fg_f, dist_c, dist_f = f(rays_d, rays_o, call, *coarse_params, *fine_params); `call` (RenderCall)
+    holds the explicit draws.  fg_c / fg_f [N]: the passes' front weights with `call.want_fg`, else None (and nothing of the extension
+    library runs).  dist_c / dist_f [N]: the passes' distortion terms with `call.want_dist`, else None (and nothing of the
+    regulariser library runs)."""
 
     @staticmethod
     def forward(ctx, rays_d, rays_o, call: RenderCall, *params):
@@ -306,16 +325,19 @@ class RenderTrainFn(torch.autograd.Function):
             rgb_c, depth_c, _, w_sel, wmax = run_pass(coarse, st, rays, saving, None if call.only_coarse else call.eps_sel,
                                                       want_depth=call.only_coarse)
             fg_c = front_weight(coarse) if call.want_fg else None
+            span = (float(owner.near), float(owner.far))
+            dist_c = distortion(coarse, span) if call.want_dist else None
             if st.voxel:
                 ops.voxel_update(owner.voxel_grid(), st.voxel_beta, rays.o, rays.d, coarse.zgrid, jit, coarse.out,
                                  coarse.idx, coarse.count, coarse.max_rows)
-            passes, rgb_f, fg_f = [coarse], None, None
+            passes, rgb_f, fg_f, dist_f = [coarse], None, None, None
             if not call.only_coarse:
                 flat_f = call.model_f.flat_params()
                 fine = fine_pass(owner, call.model_f, flat_f, _packed(call.model_f, flat_f, st, dev), rays, jit, w_sel, wmax,
                                  call.eps_f, call.u, call.cap_perm, train=True)
                 rgb_f = run_pass(fine, st, rays, saving)[0]
                 fg_f = front_weight(fine) if call.want_fg else None
+                dist_f = distortion(fine, span) if call.want_dist else None
                 passes.append(fine)
         if need_grad:                                       # the lease, with the sets it holds, waits in ctx for the backward
             ctx.owner, ctx.model_f, ctx.lease = owner, call.model_f, lease          # (not `call`: it would keep every draw alive)
@@ -323,10 +345,10 @@ class RenderTrainFn(torch.autograd.Function):
             ctx.save_for_backward(*rays, *(t for p in passes for t in p.tensors()))
         if depth_c is not None:                             # (only_coarse; rgb_f is None then)
             ctx.mark_non_differentiable(depth_c)
-        return rgb_c, rgb_f, depth_c, fg_c, fg_f
+        return rgb_c, rgb_f, depth_c, fg_c, fg_f, dist_c, dist_f
 
     @staticmethod
-    def backward(ctx, d_rgb_c, d_rgb_f, _d_depth, d_fg_c=None, d_fg_f=None):
+    def backward(ctx, d_rgb_c, d_rgb_f, _d_depth, d_fg_c=None, d_fg_f=None, d_dist_c=None, d_dist_f=None):
         if getattr(ctx, "workspaces_given_back", False):
             # retain_graph=True + a second backward: the saved-operand set went back to the pool after the first one and the next
             # forward may already have overwritten it -- refuse instead of returning gradients of clobbered operands
@@ -337,6 +359,7 @@ class RenderTrainFn(torch.autograd.Function):
         rays = Rays(next(saved), next(saved), next(saved))
         coarse, *fine = [SamplePass.restored(model, saved, max_rows, save) for model, max_rows, save in ctx.stubs]
         N, dev = rays.d.shape[0], rays.d.device
+        span = (float(owner.near), float(owner.far))
         want_rays = ctx.needs_input_grad[0] or ctx.needs_input_grad[1]
         d_od = torch.zeros(2, N, 3, dtype=torch.float32, device=dev) if want_rays else None      # (one fill for both)
         d_o, d_d = (d_od[0], d_od[1]) if want_rays else (None, None)
@@ -354,8 +377,8 @@ class RenderTrainFn(torch.autograd.Function):
         with lease:
             for p in fine:                                  # (none after an only_coarse call)
                 g_f = arena[n_c:n_c + n_f] if arena is not None else torch.zeros_like(p.flat)
-                pass_backward(p, st, rays, d_rgb_f, g_f, d_o, d_d, lease, d_fg_f)
-            pass_backward(coarse, st, rays, d_rgb_c, g_c, d_o, d_d, lease, d_fg_c)
+                pass_backward(p, st, rays, d_rgb_f, g_f, d_o, d_d, lease, d_fg_f, d_dist_f, span)
+            pass_backward(coarse, st, rays, d_rgb_c, g_c, d_o, d_d, lease, d_fg_c, d_dist_c, span)
         grads_c = coarse.model.grad_views(g_c)
         grads_f = model_f.grad_views(g_f) if g_f is not None else [None] * len(model_f.ordered_parameters())
         owner.last_flat_grads = (g_c, g_f)

@@ -12,7 +12,7 @@ from typing import Optional, Tuple
 
 import torch
 
-from . import _ext, _lib
+from . import _ext, _lib, _reg
 
 Tensor = torch.Tensor
 
@@ -28,6 +28,8 @@ TRAIN_LOSS_CALIB_OUT = _lib.DEFINES["MCNERF_TRAIN_LOSS_CALIB_OUT"]
 TRAIN_LOSS_CALIB_WS = _lib.DEFINES["MCNERF_TRAIN_LOSS_CALIB_WS"]
 # ... and include/mcnerf_ext.h, the extension library's header (`_ext`: loaded on the first call of one of its entry points)
 MASK_LOSS_OUT = _ext.DEFINES["MCNERF_EXT_MASK_LOSS_OUT"]
+# ... and include/mcnerf_reg.h, the regulariser library's (`_reg`: loaded on the first call of one of its entry points as well)
+DIST_MOMENT_BYTES = _reg.DEFINES["MCNERF_REG_MOMENT_BYTES"]
 
 
 def skip_code(skips, depth: int, deg: int = 2, n_freqs: int = 10) -> int:
@@ -600,6 +602,45 @@ def mask_loss(fg_c: Tensor, fg_f: Optional[Tensor], alpha: Tensor, weight: float
     d_f = torch.empty_like(fg_f) if fg_f is not None else None
     _ext.call("mcnerf_ext_mask_loss", fg_c, fg_f, alpha, n, float(weight), out, d_c, d_f, _stream())
     return out[:2], d_c, d_f
+
+
+# --------------------------------------------------------------------------- distortion loss (the regulariser library)
+def _z_span(near: float, far: float):
+    """(z_near, z_scale = 1 / (far - near)) of s = (z - near) z_scale; an empty range gives the infinity the library refuses."""
+    near, far = float(near), float(far)
+    return near, (1.0 / (far - near) if far != near else float("inf"))
+
+
+def distortion_fwd(sig_rgb: Tensor, zgrid: Tensor, jitter: Optional[Tensor], eps: Tensor, near: float, far: float, *,
+                   z_rows: Optional[Tensor] = None):
+    """-> (dist [N], moments [N, 16] uint8) of the rgb composite's weights w of `composite_fwd` on the same inputs:
+    dist = sum_ij w_i w_j |s_i - s_j| + (1/3) sum_{j<S-1} w_j^2 (s_{j+1} - s_j), s = (z - near) / (far - near); the far-plane sample
+    takes part in the pair term and has no interval term.  The depth rows must be non-decreasing.  `moments` is opaque: the ray's
+    (sum w, sum w s) in fp64, for `composite_bwd_w`."""
+    N = sig_rgb.shape[0]
+    zgrid, S, zs = _depths(zgrid, z_rows, N)
+    dist = torch.empty(N, dtype=torch.float32, device=sig_rgb.device)
+    moments = torch.empty(N, DIST_MOMENT_BYTES, dtype=torch.uint8, device=sig_rgb.device)
+    _reg.call("mcnerf_reg_distortion_fwd", sig_rgb, zgrid, zs, jitter, eps, N, S, *_z_span(near, far), dist, moments, _stream())
+    return dist, moments
+
+
+def composite_bwd_w(sig_rgb: Tensor, zgrid: Tensor, jitter: Optional[Tensor], eps: Tensor, d_rgb: Tensor, d_fg: Optional[Tensor],
+                    d_dist: Optional[Tensor], moments: Optional[Tensor], near: float, far: float, white_back: bool = True,
+                    want_gmax: bool = False, *, z_rows: Optional[Tensor] = None):
+    """`composite_bwd` of  sum rgb * d_rgb + sum fg * d_fg + sum dist * d_dist  (d_fg, d_dist [N] or None; d_dist with the `moments`
+    of `distortion_fwd` on the same inputs, near and far).  With d_dist None the bits of `composite_bwd_front`, with both None those
+    of `composite_bwd`."""
+    N = d_rgb.shape[0]
+    zgrid, S, zs = _depths(zgrid, z_rows, N)
+    if d_dist is not None and (moments is None or tuple(moments.shape) != (N, DIST_MOMENT_BYTES)):
+        raise _lib.McnerfError(f"d_dist needs the moments [{N}, {DIST_MOMENT_BYTES}] of distortion_fwd, got "
+                               + ("None" if moments is None else str(tuple(moments.shape))))
+    d = torch.empty(N, S, 4, dtype=torch.float32, device=d_rgb.device)
+    gmax = torch.zeros(1, dtype=torch.int32, device=d_rgb.device) if want_gmax else None
+    _reg.call("mcnerf_reg_composite_bwd_w", sig_rgb, zgrid, zs, jitter, eps, d_rgb, d_fg, d_dist, moments if d_dist is not None else None,
+              *_z_span(near, far), N, S, int(bool(white_back)), d, gmax, _stream())
+    return (d, gmax) if want_gmax else d
 
 
 def _list_buffers(N: int, S: int, prefill: bool, idx: Optional[Tensor], dev):
