@@ -101,7 +101,8 @@ int mcnerf_mlp_fwd(int depth, int width, int skip, const float* params, const fl
 /* The two modules of model/net_block.py as stand-alone forward calls (exact fp32 MFMA; the render path never materialises
  * these tensors):
  *   mcnerf_encode   = SinCosEmbedding.forward (:20-35): x [n,3], barf_w [n_freqs] -> out [n, 3 + 6 n_freqs] (`emb_freqs_xyz`; 10 -> 63);
- *   mcnerf_mlp_apply = CorseFine_NeRF.forward (:67-78): x_enc [n,63], dirs [n,3] -> out [n,4] = (sigma_raw, r, g, b). */
+ *   mcnerf_mlp_apply = CorseFine_NeRF.forward (:67-78): x_enc [n,63], dirs [n,3] -> out [n,4] = (sigma_raw, r, g, b).
+ * mcnerf_encode / mcnerf_encode_bwd accept n = 0 (nothing launched) and n_freqs = 0 (out = x; barf_w may then be NULL). */
 int mcnerf_encode(const float* x, const float* barf_w, int n, int n_freqs, float* out, void* stream);
 
 /* Stream-ordered upload of up to 16 host floats WITHOUT a host-device copy: the values travel as kernel arguments and a
@@ -357,7 +358,7 @@ int mcnerf_lens_ray_batch_bwd(const float* pose, const float* kinv, const float*
  *   K [C,3,3] = [[|W wfx|,0,|W/2 wux|],[0,|W wfy|,|H/2 wuy|],[0,0,1]], Kinv its analytic inverse,
  *   pose / calib [C,3,4] = se3_to_SE3(wpose / wpose_intr) with the reference's 11-term Taylor series,
  *   pix_intr [C,P,2] = pixels of wpts_intr [C,P,3] through (K, calib), pix_extr = wpts_extr through (K, pose)
- *   (each pair may be NULL: branch not evaluated). */
+ *   (each pair may be NULL: branch not evaluated).  C = 0 is accepted by both calls and launches nothing. */
 int mcnerf_camera_fwd(const float* wpose, const float* wpose_intr, const float* wfx, const float* wfy, const float* wux,
                       const float* wuy, int C, int H, int W, float* K, float* Kinv, float* pose, float* calib,
                       const float* wpts_intr, const float* wpts_extr, int P, float* pix_intr, float* pix_extr, void* stream);
@@ -485,7 +486,8 @@ int mcnerf_radam_rows_step(int n_tensors, float* const* params, const float* con
 /* Finish of the data-parallel step's ONE gradient all-reduce (mc_nerf_amd/distributed.py; replaces the bucketed reducer of
  * DistributedDataParallel, /root/reference main.py:60-62): `arena` = [n_grad summed gradient floats | n_flags summed flags]
  * after the SUM all-reduce.  One launch divides the gradients by `world` (DDP's average) and adds 1 to *asym when some rank's
- * "produced a gradient" flags differ from this rank's `local_flags` (sum != world * local). */
+ * "produced a gradient" flags differ from this rank's `local_flags` (sum != world * local): once per call, however many flags
+ * differ.  n_grad = 0 and n_flags = 0 are accepted (local_flags may then be NULL; with both, nothing is launched). */
 int mcnerf_sync_finish(float* arena, long long n_grad, int n_flags, int world, const float* local_flags, int32_t* asym, void* stream);
 
 #ifdef __cplusplus

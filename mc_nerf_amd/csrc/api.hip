@@ -253,7 +253,9 @@ int mcnerf_upload_f32(float* dst, const float* host_vals, int n, void* stream) {
 }
 
 int mcnerf_encode(const float* x, const float* barf_w, int n, int n_freqs, float* out, void* stream) {
-    REQ(x && barf_w && out && n >= 0 && n_freqs >= 0 && n_freqs <= 16, "mcnerf_encode");
+    REQ(n >= 0 && n_freqs >= 0 && n_freqs <= 16, "mcnerf_encode");
+    if (n == 0) return 0;                 // no points: nothing is read or written (the empty arrays of a caller may be null pointers)
+    REQ(x && (barf_w || n_freqs == 0) && out, "mcnerf_encode");
     return check("mcnerf_encode", mcn_launch_encode(x, barf_w, n, n_freqs, out, (hipStream_t)stream));
 }
 int mcnerf_mlp_apply(int depth, int width, int skip, const float* params, const float* packed, const float* x_enc,
@@ -266,7 +268,9 @@ int mcnerf_mlp_apply(int depth, int width, int skip, const float* params, const 
 }
 
 int mcnerf_encode_bwd(const float* x, const float* barf_w, int n, int n_freqs, const float* d_out, float* d_x, void* stream) {
-    REQ(x && barf_w && d_out && d_x && n >= 0 && n_freqs >= 0 && n_freqs <= 16, "mcnerf_encode_bwd");
+    REQ(n >= 0 && n_freqs >= 0 && n_freqs <= 16, "mcnerf_encode_bwd");
+    if (n == 0) return 0;                 // (as mcnerf_encode)
+    REQ(x && (barf_w || n_freqs == 0) && d_out && d_x, "mcnerf_encode_bwd");
     return check("mcnerf_encode_bwd", mcn_launch_encode_bwd(x, barf_w, n, n_freqs, d_out, d_x, (hipStream_t)stream));
 }
 // CorseFine_NeRF.forward with the operands of its backward saved (exact-fp32 workspaces, as mcnerf_mlp_fwd's), and that backward
@@ -496,8 +500,10 @@ int mcnerf_gather_gt(const uint8_t* image, int channels, const int64_t* pix, int
 int mcnerf_camera_fwd(const float* wpose, const float* wpose_intr, const float* wfx, const float* wfy, const float* wux,
                       const float* wuy, int C, int H, int W, float* K, float* Kinv, float* pose, float* calib,
                       const float* wpts_intr, const float* wpts_extr, int P, float* pix_intr, float* pix_extr, void* stream) {
-    REQ(wpose && wpose_intr && wfx && wfy && wux && wuy && K && Kinv && pose && calib && C >= 0 && H > 0 && W > 0, "mcnerf_camera_fwd");
-    REQ((wpts_intr == nullptr) == (pix_intr == nullptr) && (wpts_extr == nullptr) == (pix_extr == nullptr) && P >= 0, "mcnerf_camera_fwd");
+    REQ(C >= 0 && H > 0 && W > 0 && P >= 0, "mcnerf_camera_fwd");
+    if (C == 0) return 0;                 // no cameras: nothing is read or written (the empty arrays of a caller may be null pointers)
+    REQ(wpose && wpose_intr && wfx && wfy && wux && wuy && K && Kinv && pose && calib, "mcnerf_camera_fwd");
+    REQ((wpts_intr == nullptr) == (pix_intr == nullptr) && (wpts_extr == nullptr) == (pix_extr == nullptr), "mcnerf_camera_fwd");
     McnCameraArgs a = {wpose, wpose_intr, wfx, wfy, wux, wuy, C, H, W, K, Kinv, pose, calib, wpts_intr, wpts_extr, P, pix_intr, pix_extr};
     return check("mcnerf_camera_fwd", mcn_launch_camera_fwd(a, (hipStream_t)stream));
 }
@@ -506,7 +512,9 @@ int mcnerf_camera_bwd(const float* wpose, const float* wpose_intr, const float* 
                       const float* dcalib, const float* wpts_intr, const float* wpts_extr, int P, const float* dpix_intr,
                       const float* dpix_extr, float* d_wpose, float* d_wpose_intr, float* d_wfx, float* d_wfy, float* d_wux,
                       float* d_wuy, void* stream) {
-    REQ(wpose && wpose_intr && wfx && wfy && wux && wuy && C >= 0 && H > 0 && W > 0 && P >= 0, "mcnerf_camera_bwd");
+    REQ(C >= 0 && H > 0 && W > 0 && P >= 0, "mcnerf_camera_bwd");
+    if (C == 0) return 0;                 // (as mcnerf_camera_fwd)
+    REQ(wpose && wpose_intr && wfx && wfy && wux && wuy, "mcnerf_camera_bwd");
     REQ(d_wpose && d_wpose_intr && d_wfx && d_wfy && d_wux && d_wuy, "mcnerf_camera_bwd");
     REQ((!dpix_intr || wpts_intr) && (!dpix_extr || wpts_extr), "mcnerf_camera_bwd");
     McnCameraArgs a = {wpose, wpose_intr, wfx, wfy, wux, wuy, C, H, W, nullptr, nullptr, nullptr, nullptr, wpts_intr, wpts_extr, P, nullptr, nullptr};
@@ -594,7 +602,9 @@ int mcnerf_radam_rows_step(int n_tensors, float* const* params, const float* con
 }
 
 int mcnerf_sync_finish(float* arena, long long n_grad, int n_flags, int world, const float* local_flags, int32_t* asym, void* stream) {
-    REQ(arena && local_flags && asym && n_grad >= 0 && n_flags >= 0 && world >= 1, "mcnerf_sync_finish");
+    REQ(asym && n_grad >= 0 && n_flags >= 0 && world >= 1, "mcnerf_sync_finish");
+    if (n_grad == 0 && n_flags == 0) return 0;      // an empty arena: nothing to divide, nothing to compare (its pointers may be null)
+    REQ(arena && (local_flags || n_flags == 0), "mcnerf_sync_finish");
     return check("mcnerf_sync_finish", mcn_launch_sync_finish(arena, n_grad, n_flags, (float)world, local_flags, (int*)asym, (hipStream_t)stream));
 }
 
