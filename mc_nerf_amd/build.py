@@ -14,18 +14,18 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 OUT = os.path.join(HERE, "libmcnerf.so")
 SOURCES = ["api.hip", "pack.hip", "mlp_fwd.hip", "mlp_bwd.hip", "mlp_dw.hip", "pack16.hip", "mlp16_fwd.hip", "mlp16_bwd.hip", "mlp16_dw.hip", "mlp_x3_fwd.hip", "mlp_x3_bwd.hip", "mlp_x3_dw.hip", "composite.hip", "sample_pdf.hip", "select.hip", "rays.hip", "voxel.hip", "optim.hip", "optim_rows.hip", "camera.hip", "color_calib.hip", "errmap.hip", "lens.hip"]
-HEADERS = ["mcnerf_common.h", "mcnerf_kernels.h", "mcnerf_wave.h", "mcnerf_16.h", "mcnerf_x3.h", "mcnerf_launch.h", "mcnerf_voxel.h", "mcnerf_multicam.h", "mcnerf_colorcal.h", "mcnerf_errmap.h", "mcnerf_maxkey.h", "mcnerf_compact.h", "mcnerf_hash.h", "mcnerf_rays.h", "mcnerf_lens.h", "mcnerf_optim_rows.h", os.path.join("..", "..", "include", "mcnerf.h")]
+HEADERS = ["mcnerf_common.h", "mcnerf_kernels.h", "mcnerf_wave.h", "mcnerf_composite.h", "mcnerf_16.h", "mcnerf_x3.h", "mcnerf_launch.h", "mcnerf_voxel.h", "mcnerf_multicam.h", "mcnerf_colorcal.h", "mcnerf_errmap.h", "mcnerf_maxkey.h", "mcnerf_compact.h", "mcnerf_hash.h", "mcnerf_rays.h", "mcnerf_lens.h", "mcnerf_optim_rows.h", os.path.join("..", "..", "include", "mcnerf.h")]
 # The extension library (include/mcnerf_ext.h): opt-in features whose entry points are not part of the core ABI.  Its
 # objects share the object directory; nothing of it is linked into libmcnerf.so and it links none of the core's objects.
 EXT_OUT = os.path.join(HERE, "libmcnext.so")
 EXT_SOURCES = ["ext_api.hip", "mask.hip"]
-EXT_HEADERS = ["mcnerf_common.h", "mcnerf_wave.h", "mcnerf_multicam.h", "mcnerf_mask.h", os.path.join("..", "..", "include", "mcnerf.h"),
+EXT_HEADERS = ["mcnerf_common.h", "mcnerf_wave.h", "mcnerf_composite.h", "mcnerf_multicam.h", "mcnerf_mask.h", os.path.join("..", "..", "include", "mcnerf.h"),
                os.path.join("..", "..", "include", "mcnerf_ext.h")]
 # The regulariser library (include/mcnerf_reg.h): the extension library's ABI is pinned too, so the distortion loss has
 # a third library, built the same way.  None of its objects is linked into the other two and it links none of theirs.
 REG_OUT = os.path.join(HERE, "libmcnreg.so")
 REG_SOURCES = ["reg_api.hip", "distortion.hip"]
-REG_HEADERS = ["mcnerf_common.h", "mcnerf_wave.h", "mcnerf_distortion.h", os.path.join("..", "..", "include", "mcnerf_reg.h")]
+REG_HEADERS = ["mcnerf_common.h", "mcnerf_wave.h", "mcnerf_composite.h", "mcnerf_distortion.h", os.path.join("..", "..", "include", "mcnerf_reg.h")]
 # the f16x3 chains: a layer body is ~400 MFMAs with its epilogue slices, fully unrolled (beyond hipcc's default pragma-unroll budget);
 # their 256-wide instantiations run one wave per SIMD with 512 registers, where hipcc would otherwise put the MFMA
 # accumulators in AGPRs (every epilogue read then costs a v_accvgpr_read behind a full MFMA drain)

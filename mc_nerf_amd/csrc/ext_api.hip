@@ -3,13 +3,13 @@
 // comes ahead of any device work.
 #include "../../include/mcnerf_ext.h"
 #include "mcnerf_mask.h"
+#include "mcnerf_composite.h"
 #include <stdio.h>
 
 // the limits the public headers state are the kernels' own
 static_assert(MCNERF_MULTICAM_MAXSEG == MCN_MULTICAM_MAXSEG, "include/mcnerf.h: MCNERF_MULTICAM_MAXSEG");
 static_assert(MCNERF_EXT_MASK_LOSS_OUT == 4 + MCN_MASK_LOSS_BLOCKS, "include/mcnerf_ext.h: MCNERF_EXT_MASK_LOSS_OUT");
-static_assert(MCNERF_EXT_BWD_MAX_SAMPLES == MCN_FRONT_MAX_SAMPLES, "include/mcnerf_ext.h: MCNERF_EXT_BWD_MAX_SAMPLES");
-static_assert((size_t)4 * 5 * MCN_FRONT_MAX_SAMPLES * sizeof(float) <= 160 * 1024, "the backward's LDS at the bound");
+static_assert(MCNERF_EXT_BWD_MAX_SAMPLES == MCN_COMPOSITE_BWD_MAX_SAMPLES, "include/mcnerf_ext.h: MCNERF_EXT_BWD_MAX_SAMPLES");
 
 static thread_local char g_err[512] = "";
 
@@ -61,7 +61,7 @@ int mcnerf_ext_composite_bwd_front(const float* sig_rgb, const float* zgrid, int
                                    const float* d_rgb, const float* d_fg, int N, int S, int white_back,
                                    float* d_sig_rgb, uint32_t* gmax_bits, void* stream) {
     REQ(N >= 0 && S > 0, "mcnerf_ext_composite_bwd_front");
-    REQ(S <= MCN_FRONT_MAX_SAMPLES, "mcnerf_ext_composite_bwd_front");
+    REQ(S <= MCN_COMPOSITE_BWD_MAX_SAMPLES, "mcnerf_ext_composite_bwd_front");
     REQ((long long)N * S < (1ll << 31), "mcnerf_ext_composite_bwd_front");
     if (N == 0) return 0;
     REQ(sig_rgb && zgrid && eps && d_rgb && d_sig_rgb, "mcnerf_ext_composite_bwd_front");

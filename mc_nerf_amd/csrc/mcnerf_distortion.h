@@ -3,7 +3,6 @@
 #pragma once
 #include "mcnerf_common.h"
 
-#define MCN_DIST_MAX_SAMPLES 2048     // the backward's LDS: 4 waves x 5 floats per sample = 160 KiB at this S
 #define MCN_DIST_MOMENT_BYTES 16      // (W, M) of a ray: two doubles
 
 struct McnDistortionFwdArgs {

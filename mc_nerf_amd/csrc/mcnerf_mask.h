@@ -5,7 +5,6 @@
 #include "mcnerf_multicam.h"
 
 #define MCN_MASK_LOSS_BLOCKS 128      // (include/mcnerf_ext.h: MCNERF_EXT_MASK_LOSS_OUT = 4 + MCN_MASK_LOSS_BLOCKS floats of `out`)
-#define MCN_FRONT_MAX_SAMPLES 2048    // the backward's LDS: 4 waves x 5 floats per sample = 160 KiB at this S
 
 struct McnFrontWeightArgs {
     const float* sig_rgb;   // [N,S,4]

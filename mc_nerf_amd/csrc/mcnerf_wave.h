@@ -1,5 +1,5 @@
 // Wavefront (64-lane) scan / reduction helpers on the DPP path, shared by the one-wave-per-ray kernels (composite.hip,
-// sample_pdf.hip).  Every lane of the wave must be active where they are called.
+// mcnerf_composite.h, sample_pdf.hip).  Every lane of the wave must be active where they are called.
 #pragma once
 #include "mcnerf_common.h"
 
@@ -31,19 +31,26 @@ __device__ __forceinline__ float wave_max(float v) {
 }
 
 // The same inclusive scan in fp64 (sample_pdf.hip: a CDF whose entries do not depend on the order of the sum): both 32-bit halves
-// of a double take the same DPP moves, identity 0.0.
+// of a double take the same DPP moves; out-of-range lanes keep `ident` (0.0 for the sum, 1.0 for the product of the composite
+// backward's fp64 transmittance, mcnerf_composite.h).
 template <int CTRL, int ROW_MASK>
-__device__ __forceinline__ double dpp_d(double v) {
-    const long long b = __double_as_longlong(v);
-    const int lo = __builtin_amdgcn_update_dpp(0, (int)b, CTRL, ROW_MASK, 0xf, false);
-    const int hi = __builtin_amdgcn_update_dpp(0, (int)(b >> 32), CTRL, ROW_MASK, 0xf, false);
+__device__ __forceinline__ double dpp_d(double ident, double v) {
+    const long long b = __double_as_longlong(v), o = __double_as_longlong(ident);
+    const int lo = __builtin_amdgcn_update_dpp((int)o, (int)b, CTRL, ROW_MASK, 0xf, false);
+    const int hi = __builtin_amdgcn_update_dpp((int)(o >> 32), (int)(b >> 32), CTRL, ROW_MASK, 0xf, false);
     return __longlong_as_double(((long long)hi << 32) | (unsigned)lo);
 }
 __device__ __forceinline__ double wave_incl_sum_f64(double v) {
-    v += dpp_d<0x111, 0xf>(v); v += dpp_d<0x112, 0xf>(v); v += dpp_d<0x114, 0xf>(v); v += dpp_d<0x118, 0xf>(v);
-    v += dpp_d<0x142, 0xa>(v); v += dpp_d<0x143, 0xc>(v);
+    v += dpp_d<0x111, 0xf>(0.0, v); v += dpp_d<0x112, 0xf>(0.0, v); v += dpp_d<0x114, 0xf>(0.0, v); v += dpp_d<0x118, 0xf>(0.0, v);
+    v += dpp_d<0x142, 0xa>(0.0, v); v += dpp_d<0x143, 0xc>(0.0, v);
     return v;
 }
+__device__ __forceinline__ double wave_incl_prod_f64(double v) {
+    v *= dpp_d<0x111, 0xf>(1.0, v); v *= dpp_d<0x112, 0xf>(1.0, v); v *= dpp_d<0x114, 0xf>(1.0, v); v *= dpp_d<0x118, 0xf>(1.0, v);
+    v *= dpp_d<0x142, 0xa>(1.0, v); v *= dpp_d<0x143, 0xc>(1.0, v);
+    return v;
+}
+__device__ __forceinline__ double wave_shr1_f64(double v, double ident) { return dpp_d<0x138, 0xf>(ident, v); }
 __device__ __forceinline__ double wave_last_f64(double v) {
     const long long b = __double_as_longlong(v);
     const int lo = __builtin_amdgcn_readlane((int)b, 63), hi = __builtin_amdgcn_readlane((int)(b >> 32), 63);

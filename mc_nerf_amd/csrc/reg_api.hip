@@ -3,12 +3,12 @@
 // allocates, and every refusal comes ahead of any device work.
 #include "../../include/mcnerf_reg.h"
 #include "mcnerf_distortion.h"
+#include "mcnerf_composite.h"
 #include <stdio.h>
 
 // the limits the public header states are the kernels' own
-static_assert(MCNERF_REG_BWD_MAX_SAMPLES == MCN_DIST_MAX_SAMPLES, "include/mcnerf_reg.h: MCNERF_REG_BWD_MAX_SAMPLES");
+static_assert(MCNERF_REG_BWD_MAX_SAMPLES == MCN_COMPOSITE_BWD_MAX_SAMPLES, "include/mcnerf_reg.h: MCNERF_REG_BWD_MAX_SAMPLES");
 static_assert(MCNERF_REG_MOMENT_BYTES == MCN_DIST_MOMENT_BYTES && MCN_DIST_MOMENT_BYTES == 2 * sizeof(double), "include/mcnerf_reg.h: MCNERF_REG_MOMENT_BYTES");
-static_assert((size_t)4 * 5 * MCN_DIST_MAX_SAMPLES * sizeof(float) <= 160 * 1024, "the backward's LDS at the bound");
 
 static thread_local char g_err[512] = "";
 
@@ -47,7 +47,7 @@ int mcnerf_reg_composite_bwd_w(const float* sig_rgb, const float* zgrid, int z_s
                                float z_near, float z_scale, int N, int S, int white_back,
                                float* d_sig_rgb, uint32_t* gmax_bits, void* stream) {
     REQ(N >= 0 && S > 0, "mcnerf_reg_composite_bwd_w");
-    REQ(S <= MCN_DIST_MAX_SAMPLES, "mcnerf_reg_composite_bwd_w");
+    REQ(S <= MCN_COMPOSITE_BWD_MAX_SAMPLES, "mcnerf_reg_composite_bwd_w");
     REQ((long long)N * S < (1ll << 31), "mcnerf_reg_composite_bwd_w");
     REQ(finite_f(z_near) && finite_f(z_scale), "mcnerf_reg_composite_bwd_w");
     REQ((d_dist == nullptr) == (moments == nullptr), "mcnerf_reg_composite_bwd_w");

@@ -7,7 +7,7 @@ From every *.o of a build directory the gfx950 code object is extracted (llvm-ob
 symbol, whichever object holds them.  Per symbol are compared: the sequence of (encoding, instruction text) -- addresses, the
 order of kernels inside an object and the padding behind a kernel's last instruction are not compared, they depend on its neighbours; the kernel's metadata
 note (register counts, LDS, scratch, kernarg size and argument offsets).  One line per kernel, naming its object in A (and in B where
-it moved); a kernel that differs also gets its instruction count and VGPR / SGPR / LDS / scratch figures of both builds.  Exit
+it moved); a kernel that differs, or that only one build has, also gets its instruction count and VGPR / SGPR / LDS / scratch figures of both builds.  Exit
 status 1 unless every line says identical.
 """
 import glob
@@ -77,7 +77,7 @@ def main():
     for name in sorted(set(ka) | set(kb), key=lambda k: ((ka.get(k) or kb[k])[0], k)):
         obj, code, meta = ka.get(name) or kb[name]
         if name not in ka or name not in kb:
-            verdict = "ONLY IN " + ("A" if name in ka else "B")
+            verdict = "ONLY IN " + ("A" if name in ka else "B") + f"  [{figures(code, meta)}]"
         else:
             ob, cb, mb = kb[name]
             obj += "" if ob == obj else " -> " + ob

@@ -175,3 +175,27 @@ def test_library_exports_only_the_declared_abi():
     pkg = os.path.join(ROOT, "mc_nerf_amd")
     tracked = subprocess.run(["git", "ls-files", pkg], capture_output=True, text=True, cwd=ROOT).stdout
     assert "libmcnerf_" not in tracked and "build_" not in tracked
+
+
+ONCE = ("softplus_t", "running_max_bits", "mcn_sample64", "mcn_delta64", "wave_incl_prod_f64", "mcn_composite_bwd_rays")
+
+
+def test_the_composite_backward_and_its_helpers_are_defined_once():
+    """The composite backward's body and the helpers of the fp64 weight sweep are compiled into all three libraries from ONE
+    definition (csrc/mcnerf_composite.h, csrc/mcnerf_wave.h): a definition is a line at column 0 that names the function before
+    a `(` and is no declaration.  A change of that header rebuilds every library, and it is no part of the MLP source digest."""
+    import bench
+    from mc_nerf_amd import build
+    defined = {name: [] for name in ONCE}
+    for fn in sorted(f for f in os.listdir(build.CSRC) if f.endswith((".hip", ".h"))):
+        for line in open(os.path.join(build.CSRC, fn)).read().split("\n"):
+            code = re.sub(r"//.*", "", line).rstrip()
+            for name in ONCE:
+                if re.match(rf"[A-Za-z_][^=;]*\b{name}\s*\(", code) and not code.endswith(";"):
+                    defined[name].append(fn)
+    for name, files in defined.items():
+        assert len(files) == 1, f"{name} is defined in {files}"
+    assert defined["mcn_composite_bwd_rays"] == ["mcnerf_composite.h"] and defined["wave_incl_prod_f64"] == ["mcnerf_wave.h"]
+    for headers in (build.HEADERS, build.EXT_HEADERS, build.REG_HEADERS):
+        assert "mcnerf_composite.h" in headers and "mcnerf_wave.h" in headers
+    assert "mcnerf_composite.h" not in bench.MLP_KERNEL_SOURCES

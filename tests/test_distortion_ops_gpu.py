@@ -13,8 +13,8 @@
                 5e-11 .. 1.6e-9 (bars 1.1e-9 .. 2.0e-8), with the suffix sum of the d_dist path in fp64;
   gmax          the gmax word equals max|d_sig_rgb|;
   bit identity  on every case of composite_ref.CASES, composite_bwd_w(d_fg = None, d_dist = None) is ops.composite_bwd and, with the
-                case's d_fg only, ops.composite_bwd_front -- d_sig_rgb and the gmax word: the three statements of the backward's body
-                are one computation;
+                case's d_fg only, ops.composite_bwd_front -- d_sig_rgb and the gmax word: the three libraries' instantiations of the
+                backward's body (csrc/mcnerf_composite.h) are one computation;
   refusals      S = 2049 is refused with the output untouched, the forward accepts it; N = 0 gives empty results;
   determinism   two runs are torch.equal.
 """

@@ -12,7 +12,7 @@
                 the mask path those 8 variants were at 5e-6 / 1e-5: the device's expf near 1 is biased by -0.10 * 2^-24, which adds
                 linearly over a thousand samples of the transmittance product; the mask path is fp64 per sample for that reason.);
   bit identity  composite_bwd_front(d_fg = None) is ops.composite_bwd word for word, d_sig_rgb and the gmax word, on every case of
-                composite_ref.CASES: the two statements of the backward's body are one computation;
+                composite_ref.CASES: the two libraries' instantiations of the backward's body (csrc/mcnerf_composite.h) are one computation;
   refusals      S = 2049 is refused with the output untouched; bad segment tables are refused;
   gather_alpha  against indexing the uint8 tensor, K = 1 and K = 3 with cameras [2, 0, 2]; ones for 3-channel images;
   mask_loss     n = 1, 255, 256, 257, 32768 + 261, with and without fg_f: value <= 2e-6 max(1, |ref|), gradients <= 2e-6 max|ref|
