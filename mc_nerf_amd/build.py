@@ -1,5 +1,5 @@
-"""Builds mc_nerf_amd/libmcnerf.so and, beside it, the extension library mc_nerf_amd/libmcnext.so and the regulariser library
-mc_nerf_amd/libmcnreg.so (hipcc, gfx950 only) in-tree.
+"""Builds mc_nerf_amd/libmcnerf.so and, beside it, the extension library mc_nerf_amd/libmcnext.so, the regulariser library
+mc_nerf_amd/libmcnreg.so and the geometry library mc_nerf_amd/libmcngeo.so (hipcc, gfx950 only) in-tree.
 
     python -m mc_nerf_amd.build [--force]
 
@@ -26,6 +26,12 @@ EXT_HEADERS = ["mcnerf_common.h", "mcnerf_wave.h", "mcnerf_composite.h", "mcnerf
 REG_OUT = os.path.join(HERE, "libmcnreg.so")
 REG_SOURCES = ["reg_api.hip", "distortion.hip"]
 REG_HEADERS = ["mcnerf_common.h", "mcnerf_wave.h", "mcnerf_composite.h", "mcnerf_distortion.h", os.path.join("..", "..", "include", "mcnerf_reg.h")]
+# The geometry library (include/mcnerf_geo.h): the regulariser library's ABI is pinned as well, so depth supervision has
+# a fourth library, built the same way.  None of its objects is linked into the other three and it links none of theirs.
+GEO_OUT = os.path.join(HERE, "libmcngeo.so")
+GEO_SOURCES = ["geo_api.hip", "depth.hip"]
+GEO_HEADERS = ["mcnerf_common.h", "mcnerf_wave.h", "mcnerf_composite.h", "mcnerf_multicam.h", "mcnerf_depth.h", os.path.join("..", "..", "include", "mcnerf.h"),
+               os.path.join("..", "..", "include", "mcnerf_geo.h")]
 # the f16x3 chains: a layer body is ~400 MFMAs with its epilogue slices, fully unrolled (beyond hipcc's default pragma-unroll budget);
 # their 256-wide instantiations run one wave per SIMD with 512 registers, where hipcc would otherwise put the MFMA
 # accumulators in AGPRs (every epilogue read then costs a v_accvgpr_read behind a full MFMA drain)
@@ -41,7 +47,8 @@ def _newer(a, b):
 
 
 def build(force=False, verbose=True):
-    """All three libraries; returns the core library's path."""
+    """All four libraries; returns the core library's path."""
+    _build_library(GEO_SOURCES, GEO_HEADERS, GEO_OUT, force, verbose)
     _build_library(EXT_SOURCES, EXT_HEADERS, EXT_OUT, force, verbose)
     _build_library(REG_SOURCES, REG_HEADERS, REG_OUT, force, verbose)
     return _build_library(SOURCES, HEADERS, OUT, force, verbose)

@@ -1,9 +1,9 @@
-// The alpha-compositing backward and the fp64 weight sweep of the one-wave-per-ray kernels, each defined once for the three
-// libraries that run them: composite.hip (the core: fp32), mask.hip (the extension library: a gradient on the front weight) and
-// distortion.hip (the regulariser library: a gradient on the distortion loss).  Device code and the launch helper only; every
-// library compiles its own instantiations.
+// The alpha-compositing backward and the fp64 weight sweep of the one-wave-per-ray kernels, each defined once for the four
+// libraries that run them: composite.hip (the core: fp32), mask.hip (the extension library: a gradient on the front weight),
+// distortion.hip (the regulariser library: a gradient on the distortion loss) and depth.hip (the geometry library: a gradient on the
+// expected depth).  Device code and the launch helper only; every library compiles its own instantiations.
 //
-// The mask and distortion paths (mcn_weight_sweep64, and the backward with FRONT or DIST) form the per-sample quantities and the
+// The mask, distortion and depth paths (mcn_weight_sweep64, and the backward with FRONT, DIST or ZEXP) form the per-sample quantities and the
 // transmittance product in FP64 (mcn_sample64, wave_incl_prod_f64).  The fp32 form does not hold the feature's parity bar on
 // semi-transparent rays of a thousand samples: u = 0.997 there, the device's expf near 1 is biased by -0.10 * 2^-24 (measured; the host's by +0.005), and the
 // bias adds LINEARLY over the product -- 5e-6 in fg and 1e-5 in d_sig_rgb at S = 1024, five times the bar -- where rounding errors add
@@ -87,6 +87,7 @@ struct McnCompositeBwdView {
     float* d_sig_rgb;       // [N,S,4]
     unsigned* gmax_bits;    // or null
     int z_stride;
+    const float* d_zexp;    // [N]; read with ZEXP only (the last member: a view built without it leaves it null)
 };
 
 // Backward of the rgb composite wrt (sigma_raw, rgb) of every sample:
@@ -100,7 +101,9 @@ struct McnCompositeBwdView {
 // d_dist[n] d dist / d w_j to dw_j BEFORE sDW / sDWW are stored (dw and dw w are formed in fp64 and rounded once); the suffix sum of
 // dw w then runs in fp64 over those words.  The d_fg term, when both are given, is the closed form unchanged.
 //   d dist / d w_j = 2 [ s_j (2 A_j + w_j - W) + M - 2 B_j - w_j s_j ]  +  (2/3) w_j (s_{j+1} - s_j) [j < S-1]      (distortion.hip)
-template <bool FRONT, bool DIST>
+// With ZEXP (the expected depth zexp = sum_j w_j z_j, depth.hip) the prefix pass is the fp64 one too and d_zexp[n] z_j is added to dw_j
+// in fp64 before sDW / sDWW are stored; the suffix sum runs in fp64 as with DIST.
+template <bool FRONT, bool DIST, bool ZEXP = false>
 __device__ __forceinline__ void mcn_composite_bwd_rays(const McnCompositeBwdView& a, float* sm) {
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
     const int S = a.S;
@@ -120,6 +123,8 @@ __device__ __forceinline__ void mcn_composite_bwd_rays(const McnCompositeBwdView
     double carryT64 = 1.0;
     double gd = 0.0, Wt = 0.0, Mt = 0.0, carryA = 0.0, carryB = 0.0;
     if constexpr (DIST) { gd = (double)a.d_dist[n]; Wt = a.moments[(size_t)n * 2]; Mt = a.moments[(size_t)n * 2 + 1]; }
+    double gz = 0.0;
+    if constexpr (ZEXP) gz = (double)a.d_zexp[n];
     // what sample j stages for the suffix pass, and its colour gradients
     auto stage = [&](int j, float T, float u, float e, float w, float dw, float dww) {
         sT[j] = T; sU[j] = u; sE[j] = e; sDW[j] = dw; sDWW[j] = dww;
@@ -134,7 +139,7 @@ __device__ __forceinline__ void mcn_composite_bwd_rays(const McnCompositeBwdView
         const int j = base + lane;
         const bool ok = j < S;
         f32x4 v = {0.f, 0.f, 0.f, 0.f};
-        if constexpr (FRONT || DIST) {     // the sample and the transmittance in fp64, see the top
+        if constexpr (FRONT || DIST || ZEXP) {     // the sample and the transmittance in fp64, see the top
             float e1 = 0.f;
             if (ok) { v = sr[j]; e1 = a.eps[(size_t)n * S + j]; }
             const McnWeight64 q = mcn_weight_sweep64(v[0], e1, zrow, jit, j, S, carryT64);
@@ -150,9 +155,13 @@ __device__ __forceinline__ void mcn_composite_bwd_rays(const McnCompositeBwdView
             if (ok) {
                 const float w = (float)q.w;
                 const float dwc = g0 * (v[1] - wb) + g1 * (v[2] - wb) + g2 * (v[3] - wb);
-                if constexpr (DIST) {
-                    const double ddw = 2.0 * (sj * (2.0 * p.A + q.w - Wt) + Mt - 2.0 * p.B - q.w * sj) + (2.0 / 3.0) * q.w * ds;
-                    const double dw = (double)dwc + gd * ddw;
+                if constexpr (DIST || ZEXP) {
+                    double dw = (double)dwc;
+                    if constexpr (DIST) {
+                        const double ddw = 2.0 * (sj * (2.0 * p.A + q.w - Wt) + Mt - 2.0 * p.B - q.w * sj) + (2.0 / 3.0) * q.w * ds;
+                        dw = (double)dwc + gd * ddw;
+                    }
+                    if constexpr (ZEXP) dw += gz * (double)__fadd_rn(zrow[j], jit);      // the depths are constants of the backward
                     stage(j, (float)q.T, (float)q.u, (float)q.e, w, (float)dw, (float)(dw * q.w));
                 } else {
                     stage(j, (float)q.T, (float)q.u, (float)q.e, w, dwc, dwc * w);
@@ -203,7 +212,7 @@ __device__ __forceinline__ void mcn_composite_bwd_rays(const McnCompositeBwdView
         const int j = c * 64 + (63 - lane);
         const bool ok = j < S;
         float R;                                                      // strictly later samples (of the chunk + of the chunks behind it)
-        if constexpr (DIST) {              // the suffix sum in fp64 (its terms change sign along the ray)
+        if constexpr (DIST || ZEXP) {      // the suffix sum in fp64 (with DIST its terms change sign along the ray)
             const double inc = wave_incl_sum_f64(ok ? (double)sDWW[j] : 0.0);
             R = (float)(carryR64 + wave_shr1_f64(inc, 0.0));
             carryR64 += wave_last_f64(inc);

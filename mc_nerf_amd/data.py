@@ -23,13 +23,20 @@ from . import ops
 
 
 class DeviceImageSet:
-    """uint8 images [C, H*W, channels] on the device; `gather(cam, pix)` -> fp32 [n,3]."""
+    """uint8 images [C, H*W, channels] on the device; `gather(cam, pix)` -> fp32 [n,3].  `depth` (optional; "depth_weight", DESIGN.md
+    4j): fp32 [C, H*W] on the same device, RAY DISTANCE in world units (`z_depth_to_ray_distance` converts sensor z-depth); a value
+    that is not finite and > 0 is "no measurement"."""
 
-    def __init__(self, images_u8: torch.Tensor, H: int, W: int):
+    def __init__(self, images_u8: torch.Tensor, H: int, W: int, depth: Optional[torch.Tensor] = None):
         assert images_u8.dtype == torch.uint8 and images_u8.dim() == 3 and images_u8.shape[1] == H * W
         assert images_u8.shape[2] in (3, 4)
         self.images = images_u8.contiguous()
         self.H, self.W = H, W
+        if depth is not None:
+            assert depth.dtype == torch.float32 and tuple(depth.shape) == (images_u8.shape[0], H * W), "depth must be fp32 [C, H*W]"
+            assert depth.device == images_u8.device, "depth must be on the images' device"
+            depth = depth.contiguous()
+        self.depth = depth
 
     def __len__(self):
         return self.images.shape[0]
@@ -52,6 +59,18 @@ class DeviceImageSet:
         base = torch.randint(0, 256, (distinct, H * W, channels), dtype=torch.uint8, generator=g)
         idx = torch.arange(C) % distinct
         return DeviceImageSet(base[idx].to(device), H, W)
+
+
+def z_depth_to_ray_distance(depth_z: torch.Tensor, K: torch.Tensor, H: int, W: int) -> torch.Tensor:
+    """Sensor z-depth ([..., H*W] or [..., H, W]) -> distance from the camera centre along the pixel's unit ray, the convention of
+    `DeviceImageSet.depth`: times |K^-1 (u + 1/2, v + 1/2, 1)| with the NOMINAL intrinsics K ([3,3], or [C,3,3] for depth_z [C, ...]).
+    Host-side torch, same shape and dtype out; values that are no measurement (0, negative, NaN, inf) pass through as what they are."""
+    flat = depth_z.reshape(*depth_z.shape[:-2], H * W) if tuple(depth_z.shape[-2:]) == (H, W) else depth_z
+    assert flat.shape[-1] == H * W, f"depth_z must end in H*W = {H * W} (or H, W), got {tuple(depth_z.shape)}"
+    pid = torch.arange(H * W)
+    p = torch.stack([(pid % W).double() + 0.5, torch.div(pid, W, rounding_mode="floor").double() + 0.5, torch.ones(H * W, dtype=torch.float64)])
+    norm = (torch.linalg.inv(K.double().cpu()) @ p).norm(dim=-2)               # [H*W], or [C, H*W]
+    return (flat.double() * norm.to(flat.device)).to(depth_z.dtype).reshape(depth_z.shape)
 
 
 def blender_pose_to_reference(c2w: np.ndarray) -> np.ndarray:

@@ -39,6 +39,15 @@ def dist_weight_setting(sys_param):
     return float(w)
 
 
+def depth_weight_setting(sys_param):
+    """This build's own sys_param key "depth_weight" (DESIGN.md 4j): the weight lambda >= 0 of the depth term, a finite float (an int
+    counts, a bool does not); 0.0, the default, is today's path.  A ValueError names the key.  NOT tuned: there is no recommended value."""
+    w = sys_param.get("depth_weight", 0.0)
+    if isinstance(w, bool) or not isinstance(w, (int, float)) or not 0.0 <= w < float("inf"):
+        raise ValueError(f"depth_weight must be a finite float >= 0, got {w!r}")
+    return float(w)
+
+
 class MC_NeRF_Loss(nn.Module):
     def __init__(self, sys_param, tblogger=None):
         super().__init__()
@@ -50,8 +59,15 @@ class MC_NeRF_Loss(nn.Module):
         self.color_reg = color_calib_settings(sys_param)[1]
         self.mask_weight = mask_weight_setting(sys_param)
         self.dist_weight = dist_weight_setting(sys_param)
+        self.depth_weight = depth_weight_setting(sys_param)
 
     def forward(self, loss_dict, epoch_type):
+        if "depth" in loss_dict:
+            # depth mode: the other keys exactly as without it (the mask and distortion terms included), plus the depth
+            # term of the two expected depths over the depth range of the renderer
+            rest = dict(loss_dict)
+            depth = rest.pop("depth")
+            return self.forward(rest, epoch_type) + self.get_depth_loss(depth, self.sys_param["near"], self.sys_param["far"])
         self.global_step += 1
         if "dist" in loss_dict:
             # distortion mode: the other keys exactly as without it (the mask term included), plus the distortion term
@@ -131,6 +147,19 @@ class MC_NeRF_Loss(nn.Module):
         if dist_f is not None:
             total = total + dist_f.mean()
         return weight * total
+
+    def get_depth_loss(self, depth_list, near, far, weight=None):
+        """weight * (1 / max(n_valid, 1)) sum_valid [(s(zexp_c) - s(d))^2 + (s(zexp_f) - s(d))^2], s(z) = (z - near) / (far - near), of
+        [zexp_c, zexp_f | None, d_gt]: the expected depths [N] a depth-mode NeRF_Model keeps in `last_expected_depth`, and the drawn
+        pixels' targets [N] as RAY DISTANCE in world units (MC_Model gathers them from the image set's depth, a loop that drives
+        NeRF_Model directly supplies them); a target is a measurement iff it is finite and > 0, a batch without one gives an exact zero.
+        `weight` None: the model's "depth_weight".  Two launches (render.DepthLossFn); device tensors only."""
+        zexp_c, zexp_f, d_gt = depth_list
+        weight = self.depth_weight if weight is None else float(weight)
+        if not 0.0 <= weight < float("inf"):
+            raise ValueError(f"depth_weight must be a finite float >= 0, got {weight!r}")
+        from .render import DepthLossFn
+        return DepthLossFn.apply(zexp_c, zexp_f, d_gt, float(near), float(far), weight)
 
     def get_rgb_loss_calibrated(self, rgbs_list, weights_color, cams, seg_start, reg=None):
         """get_rgb_loss with the per-camera colour calibration weights_color [C,6], for loops that drive NeRF_Model

@@ -23,7 +23,7 @@ import torch.distributed as dist
 from .. import ops
 from ..data import DeviceImageSet
 from ..lens import distort_pixels, lens_model_setting
-from .loss import color_calib_settings, dist_weight_setting, mask_weight_setting
+from .loss import color_calib_settings, depth_weight_setting, dist_weight_setting, mask_weight_setting
 from .net_block import CorseFine_NeRF, SinCosEmbedding
 from .render import CameraFn, RayBatchFn, RaygenFn, Rays, RenderCall, RenderSettings, RenderTrainFn, SamplePass, _pool, render_test, run_pass
 
@@ -122,6 +122,12 @@ class NeRF_Model(nn.Module):
         # `last_distortion`; 0.0 (the default) is today's path: the regulariser library is not even loaded
         self.dist_weight = dist_weight_setting(sys_param)
         self.last_distortion = None       # distortion mode: (dist_c, dist_f | None) [N] of the last train render, attached to its graph
+        # "depth_weight" is this build's own key too: lambda > 0 makes each pass's expected depth -- sum w z on the rgb
+        # composite's weights, the far-plane sample included -- one more differentiable output of the train render, kept for the loss in
+        # `last_expected_depth`; 0.0 (the default) is today's path: the geometry library is not even loaded
+        self.depth_weight = depth_weight_setting(sys_param)
+        self.settings.want_zexp = self.depth_weight > 0.0
+        self.last_expected_depth = None   # depth mode: (zexp_c, zexp_f | None) [N] of the last train render, attached to its graph
         self.last_coarse_selection = None  # (idx_c, count_c) of the last pruned coarse pass; None in "dense" mode and in the warm-up
         self.last_selection = None        # (idx, count) of the last fine pass in "threshold" mode; None in "pdf" mode
         self.last_z_all = None            # the fine pass's depth rows [N, samples + n_importance] in "pdf" mode
@@ -251,7 +257,11 @@ class NeRF_Model(nn.Module):
         want_dist = self.dist_weight > 0.0
         if want_dist and not rays_d.is_cuda:
             raise ops._lib.McnerfError(f"dist_weight = {self.dist_weight}: the distortion term is a HIP kernel, got rays on {dev} (no CPU fallback)")
+        want_zexp = self.settings.want_zexp
+        if want_zexp and not rays_d.is_cuda:
+            raise ops._lib.McnerfError(f"depth_weight = {self.depth_weight}: the expected depth is a HIP kernel, got rays on {dev} (no CPU fallback)")
         if N == 0:                                  # empty batch: empty results (the reference's tensor ops do the same)
+            self.last_expected_depth = (rays_d.new_zeros(0), None if only_coarse else rays_d.new_zeros(0)) if want_zexp else None
             e3, e1 = rays_d.new_zeros(0, 3), rays_d.new_zeros(0, 1)
             self.last_front_weight = (rays_d.new_zeros(0), None if only_coarse else rays_d.new_zeros(0)) if want_fg else None
             self.last_distortion = (rays_d.new_zeros(0), None if only_coarse else rays_d.new_zeros(0)) if want_dist else None
@@ -263,7 +273,8 @@ class NeRF_Model(nn.Module):
         call = RenderCall(self, self.nerf_coarse, self.nerf_fine, step_r, only_coarse, *draws, cap_perm,
                           prune=self.settings.voxel and cur_epoch >= self.settings.voxel_warmup_epoch, want_dist=want_dist,
                           want_fg=want_fg)
-        rgb_c, rgb_f, depth_c, fg_c, fg_f, dist_c, dist_f = RenderTrainFn.apply(rays_d, rays_o, call, *params)
+        rgb_c, rgb_f, depth_c, fg_c, fg_f, dist_c, dist_f, zexp_c, zexp_f = RenderTrainFn.apply(rays_d, rays_o, call, *params)
+        self.last_expected_depth = (zexp_c, zexp_f) if want_zexp else None
         self.last_front_weight = (fg_c, fg_f) if want_fg else None
         self.last_distortion = (dist_c, dist_f) if want_dist else None
         return (rgb_c, None, depth_c) if only_coarse else (rgb_c, rgb_f)
@@ -536,6 +547,9 @@ class MC_Model(nn.Module):
         # "dist_weight" likewise: lambda > 0 adds the distortion term of the renderer's two passes to the NeRF stages'
         # loss; no parameter, no extra data
         self.dist_weight = dist_weight_setting(sys_param)
+        # "depth_weight" likewise: lambda > 0 adds the depth term of the renderer's two expected depths to the NeRF
+        # stages' loss, the targets of the drawn pixels gathered from the image set's device-resident depth; no parameter
+        self.depth_weight = depth_weight_setting(sys_param)
         self._error_map = None            # ops.ErrorMap, allocated on first use ("error" mode only): not a parameter, not a buffer
         if self.pixel_sampler == "error":
             self.error_tile, self.error_beta, self.error_uniform_frac = self._error_settings(sys_param)
@@ -736,6 +750,12 @@ class MC_Model(nn.Module):
                                  + ("a host float image stack" if images is None else f"{images.images.shape[2]}-channel images"))
         if self.dist_weight > 0.0 and not self.weights_pose.is_cuda:
             raise ops._lib.McnerfError(f"dist_weight = {self.dist_weight}: the distortion term runs on the GPU only, the model is on {self.weights_pose.device}")
+        if self.depth_weight > 0.0:
+            if not self.weights_pose.is_cuda:
+                raise ops._lib.McnerfError(f"depth_weight = {self.depth_weight}: depth supervision runs on the GPU only, the model is on {self.weights_pose.device}")
+            if images is None or getattr(images, "depth", None) is None:
+                raise ValueError(f"depth_weight = {self.depth_weight} needs a device-resident image set with depth (DeviceImageSet(..., depth=...)), got "
+                                 + ("a host float image stack" if images is None else "an image set without depth"))
         seg_start = ops.ray_segments(self.batch, K)
         if K == 1:      # pixel subset first (same device randperm as :329), rays only for those pixels
             pix = self._draw_error_pixels(cams, seg_start) if error else self.sample_pixels(npix)
@@ -768,6 +788,8 @@ class MC_Model(nn.Module):
             loss_dict["mask"] = [*self.nerf.last_front_weight, ops.gather_alpha(images.images, cams, seg_start, pix.contiguous())]
         if self.dist_weight > 0.0:
             loss_dict["dist"] = [*self.nerf.last_distortion]
+        if self.depth_weight > 0.0:
+            loss_dict["depth"] = [*self.nerf.last_expected_depth, ops.gather_depth(images.depth, cams, seg_start, pix.contiguous())]
         self.opt_idx = 1 if joint else 2
         if K > 1 or error:
             self.last_step_segments, self.last_step_pix = (cams, seg_start), pix

@@ -55,6 +55,9 @@ class RenderSettings:
     voxel_beta: float = 0.1
     voxel_thresh: float = 0.0
     voxel_warmup_epoch: int = 1
+    # depth mode: each pass's expected depth on the rgb composite's own weights is one more differentiable output of
+    # the train render.  The switch rides here, not on RenderCall (its field list is pinned); NeRF_Model sets it from "depth_weight"
+    want_zexp: bool = False
 
     @property
     def samples_f(self):
@@ -215,16 +218,28 @@ def distortion(p: SamplePass, span):
     return dist
 
 
+def expected_depth(p: SamplePass):
+    """zexp [N] of a pass that `run_pass` has composited (ops.expected_depth: sum w z on the rgb composite's weights, the far-plane
+    sample included)."""
+    return ops.expected_depth(p.out, p.zgrid, p.jitter, p.eps, z_rows=p.z_rows)
+
+
 def pass_backward(p: SamplePass, st: RenderSettings, rays: Rays, d_rgb, grads, d_o, d_d, lease: WorkspaceLease, d_fg=None, d_dist=None,
-                  span=None):
+                  span=None, d_zexp=None):
     """The pass's composite backward, dX chain (into d_o / d_d [N,3] when given) and weight gradients (into `grads`); nothing when
-    `d_rgb`, `d_fg` and `d_dist` are None.  Either way the pass's saved-operand set goes back to the pool.  `d_fg` [N] (mask mode): the
+    `d_rgb`, `d_fg`, `d_dist` and `d_zexp` are None.  Either way the pass's saved-operand set goes back to the pool.  `d_fg` [N] (mask mode): the
     gradient on the pass's front weight; the composite backward is then the extension library's, which takes both (d_rgb None: zeros).
     `d_dist` [N] (distortion mode, with `span` = (near, far)): the gradient on the pass's distortion term; the composite backward is
-    then the regulariser library's, which takes all three."""
+    then the regulariser library's, which takes all three.  `d_zexp` [N] (depth mode): the gradient on the pass's expected depth; the
+    composite backward is then the geometry library's, which takes whatever of the other gradients is there."""
     net = p.model.net
-    if d_rgb is not None or d_fg is not None or d_dist is not None:
-        if d_dist is not None:
+    if d_rgb is not None or d_fg is not None or d_dist is not None or d_zexp is not None:
+        if d_zexp is not None:
+            d_rgb = torch.zeros(p.out.shape[0], 3, dtype=torch.float32, device=p.out.device) if d_rgb is None else d_rgb.contiguous()
+            d_out, gmax = ops.composite_bwd_z(p.out, p.zgrid, p.jitter, p.eps, d_rgb, None if d_fg is None else d_fg.contiguous(),
+                                              None if d_dist is None else d_dist.contiguous(), p.moments, d_zexp.contiguous(), *span,
+                                              st.white_back, want_gmax=True, z_rows=p.z_rows)
+        elif d_dist is not None:
             d_rgb = torch.zeros(p.out.shape[0], 3, dtype=torch.float32, device=p.out.device) if d_rgb is None else d_rgb.contiguous()
             d_out, gmax = ops.composite_bwd_w(p.out, p.zgrid, p.jitter, p.eps, d_rgb, None if d_fg is None else d_fg.contiguous(),
                                               d_dist.contiguous(), p.moments, *span, st.white_back, want_gmax=True, z_rows=p.z_rows)
@@ -307,10 +322,11 @@ RenderCall = namedtuple("RenderCall", "owner model_c model_f step_r only_coarse 
 
 
 class RenderTrainFn(torch.autograd.Function):
-    """rgb_c, rgb_f, depth_c, fg_c, fg_f, dist_c, dist_f = f(rays_d, rays_o, call, *coarse_params, *fine_params); `call` (RenderCall)
+    """rgb_c, rgb_f, depth_c, fg_c, fg_f, dist_c, dist_f, zexp_c, zexp_f = f(rays_d, rays_o, call, *coarse_params, *fine_params); `call` (RenderCall)
     holds the explicit draws.  fg_c / fg_f [N]: the passes' front weights with `call.want_fg`, else None (and nothing of the extension
     library runs).  dist_c / dist_f [N]: the passes' distortion terms with `call.want_dist`, else None (and nothing of the
-    regulariser library runs)."""
+    regulariser library runs).  zexp_c / zexp_f [N]: the passes' expected depths with `settings.want_zexp`, else None (and nothing of
+    the geometry library runs); zexp_f is None after an only_coarse call."""
 
     @staticmethod
     def forward(ctx, rays_d, rays_o, call: RenderCall, *params):
@@ -327,10 +343,11 @@ class RenderTrainFn(torch.autograd.Function):
             fg_c = front_weight(coarse) if call.want_fg else None
             span = (float(owner.near), float(owner.far))
             dist_c = distortion(coarse, span) if call.want_dist else None
+            zexp_c = expected_depth(coarse) if st.want_zexp else None
             if st.voxel:
                 ops.voxel_update(owner.voxel_grid(), st.voxel_beta, rays.o, rays.d, coarse.zgrid, jit, coarse.out,
                                  coarse.idx, coarse.count, coarse.max_rows)
-            passes, rgb_f, fg_f, dist_f = [coarse], None, None, None
+            passes, rgb_f, fg_f, dist_f, zexp_f = [coarse], None, None, None, None
             if not call.only_coarse:
                 flat_f = call.model_f.flat_params()
                 fine = fine_pass(owner, call.model_f, flat_f, _packed(call.model_f, flat_f, st, dev), rays, jit, w_sel, wmax,
@@ -338,6 +355,7 @@ class RenderTrainFn(torch.autograd.Function):
                 rgb_f = run_pass(fine, st, rays, saving)[0]
                 fg_f = front_weight(fine) if call.want_fg else None
                 dist_f = distortion(fine, span) if call.want_dist else None
+                zexp_f = expected_depth(fine) if st.want_zexp else None
                 passes.append(fine)
         if need_grad:                                       # the lease, with the sets it holds, waits in ctx for the backward
             ctx.owner, ctx.model_f, ctx.lease = owner, call.model_f, lease          # (not `call`: it would keep every draw alive)
@@ -345,10 +363,10 @@ class RenderTrainFn(torch.autograd.Function):
             ctx.save_for_backward(*rays, *(t for p in passes for t in p.tensors()))
         if depth_c is not None:                             # (only_coarse; rgb_f is None then)
             ctx.mark_non_differentiable(depth_c)
-        return rgb_c, rgb_f, depth_c, fg_c, fg_f, dist_c, dist_f
+        return rgb_c, rgb_f, depth_c, fg_c, fg_f, dist_c, dist_f, zexp_c, zexp_f
 
     @staticmethod
-    def backward(ctx, d_rgb_c, d_rgb_f, _d_depth, d_fg_c=None, d_fg_f=None, d_dist_c=None, d_dist_f=None):
+    def backward(ctx, d_rgb_c, d_rgb_f, _d_depth, d_fg_c=None, d_fg_f=None, d_dist_c=None, d_dist_f=None, d_zexp_c=None, d_zexp_f=None):
         if getattr(ctx, "workspaces_given_back", False):
             # retain_graph=True + a second backward: the saved-operand set went back to the pool after the first one and the next
             # forward may already have overwritten it -- refuse instead of returning gradients of clobbered operands
@@ -377,8 +395,8 @@ class RenderTrainFn(torch.autograd.Function):
         with lease:
             for p in fine:                                  # (none after an only_coarse call)
                 g_f = arena[n_c:n_c + n_f] if arena is not None else torch.zeros_like(p.flat)
-                pass_backward(p, st, rays, d_rgb_f, g_f, d_o, d_d, lease, d_fg_f, d_dist_f, span)
-            pass_backward(coarse, st, rays, d_rgb_c, g_c, d_o, d_d, lease, d_fg_c, d_dist_c, span)
+                pass_backward(p, st, rays, d_rgb_f, g_f, d_o, d_d, lease, d_fg_f, d_dist_f, span, d_zexp_f)
+            pass_backward(coarse, st, rays, d_rgb_c, g_c, d_o, d_d, lease, d_fg_c, d_dist_c, span, d_zexp_c)
         grads_c = coarse.model.grad_views(g_c)
         grads_f = model_f.grad_views(g_f) if g_f is not None else [None] * len(model_f.ordered_parameters())
         owner.last_flat_grads = (g_c, g_f)
@@ -549,6 +567,35 @@ class MaskLossFn(torch.autograd.Function):
         ops.scale3_(None, d_c, d_f, g.contiguous().float().reshape(1))
         ctx.grads = None
         return d_c.reshape(ctx.shapes[0]), None if d_f is None else d_f.reshape(ctx.shapes[1]), None, None
+
+
+class DepthLossFn(torch.autograd.Function):
+    """weight * (1 / max(n_valid, 1)) sum_valid [(s(zexp_c) - s(d_gt))^2 + (s(zexp_f) - s(d_gt))^2], s(z) = (z - near) / (far - near)
+    (csrc/depth.hip), value and both gradients in the geometry library's two launches; backward scales the saved gradients
+    by the upstream scalar on the device.  `zexp_f` may be None (only_coarse); `d_gt` [n] is a constant, valid where finite and > 0.
+    An empty batch is a zero that carries no gradient; a batch without a valid target is an exact zero with exact-zero gradients."""
+
+    @staticmethod
+    def forward(ctx, zexp_c, zexp_f, d_gt, near, far, weight):
+        cf = lambda t: None if t is None else t.contiguous().float().reshape(-1)
+        ctx.shapes = (zexp_c.shape, None if zexp_f is None else zexp_f.shape)
+        zexp_c, zexp_f, d_gt = cf(zexp_c), cf(zexp_f), cf(d_gt)
+        ctx.grads = None
+        if zexp_c.numel() == 0:
+            return zexp_c.new_zeros(())
+        out, d_c, d_f = ops.depth_loss(zexp_c, zexp_f, d_gt, near, far, weight)
+        ctx.grads = (d_c, d_f)
+        ctx.parts = out
+        return out[0]
+
+    @staticmethod
+    def backward(ctx, g):
+        if ctx.grads is None:
+            return None, None, None, None, None, None
+        d_c, d_f = ctx.grads
+        ops.scale3_(None, d_c, d_f, g.contiguous().float().reshape(1))
+        ctx.grads = None
+        return d_c.reshape(ctx.shapes[0]), None if d_f is None else d_f.reshape(ctx.shapes[1]), None, None, None, None
 
 
 class ReprojLossFn(torch.autograd.Function):

@@ -12,7 +12,7 @@ from typing import Optional, Tuple
 
 import torch
 
-from . import _ext, _lib, _reg
+from . import _ext, _geo, _lib, _reg
 
 Tensor = torch.Tensor
 
@@ -30,6 +30,8 @@ TRAIN_LOSS_CALIB_WS = _lib.DEFINES["MCNERF_TRAIN_LOSS_CALIB_WS"]
 MASK_LOSS_OUT = _ext.DEFINES["MCNERF_EXT_MASK_LOSS_OUT"]
 # ... and include/mcnerf_reg.h, the regulariser library's (`_reg`: loaded on the first call of one of its entry points as well)
 DIST_MOMENT_BYTES = _reg.DEFINES["MCNERF_REG_MOMENT_BYTES"]
+# ... and include/mcnerf_geo.h, the geometry library's (`_geo`: loaded on the first call of one of its entry points too)
+DEPTH_LOSS_OUT = _geo.DEFINES["MCNERF_GEO_DEPTH_LOSS_OUT"]
 
 
 def skip_code(skips, depth: int, deg: int = 2, n_freqs: int = 10) -> int:
@@ -641,6 +643,62 @@ def composite_bwd_w(sig_rgb: Tensor, zgrid: Tensor, jitter: Optional[Tensor], ep
     _reg.call("mcnerf_reg_composite_bwd_w", sig_rgb, zgrid, zs, jitter, eps, d_rgb, d_fg, d_dist, moments if d_dist is not None else None,
               *_z_span(near, far), N, S, int(bool(white_back)), d, gmax, _stream())
     return (d, gmax) if want_gmax else d
+
+
+# --------------------------------------------------------------------------- depth supervision (the geometry library)
+def expected_depth(sig_rgb: Tensor, zgrid: Tensor, jitter: Optional[Tensor], eps: Tensor, *, z_rows: Optional[Tensor] = None) -> Tensor:
+    """-> zexp [N] = sum_j w_j z_j of the rgb composite's weights of `composite_fwd` on the same inputs, z_j = fl32(z + jitter): the
+    far-plane sample (delta = 1e10) takes part at its depth.  Not `composite_fwd`'s `depth` (noise-free, |d|-scaled weights)."""
+    N = sig_rgb.shape[0]
+    zgrid, S, zs = _depths(zgrid, z_rows, N)
+    zexp = torch.empty(N, dtype=torch.float32, device=sig_rgb.device)
+    _geo.call("mcnerf_geo_depth_fwd", sig_rgb, zgrid, zs, jitter, eps, N, S, zexp, _stream())
+    return zexp
+
+
+def composite_bwd_z(sig_rgb: Tensor, zgrid: Tensor, jitter: Optional[Tensor], eps: Tensor, d_rgb: Tensor, d_fg: Optional[Tensor],
+                    d_dist: Optional[Tensor], moments: Optional[Tensor], d_zexp: Optional[Tensor], near: float, far: float,
+                    white_back: bool = True, want_gmax: bool = False, *, z_rows: Optional[Tensor] = None):
+    """`composite_bwd` of  sum rgb * d_rgb + sum fg * d_fg + sum dist * d_dist + sum zexp * d_zexp  (d_fg, d_dist, d_zexp [N] or None;
+    d_dist with the `moments` of `distortion_fwd` on the same inputs, near and far).  With d_zexp None the bits of `composite_bwd_w`."""
+    N = d_rgb.shape[0]
+    zgrid, S, zs = _depths(zgrid, z_rows, N)
+    if d_dist is not None and (moments is None or tuple(moments.shape) != (N, DIST_MOMENT_BYTES)):
+        raise _lib.McnerfError(f"d_dist needs the moments [{N}, {DIST_MOMENT_BYTES}] of distortion_fwd, got "
+                               + ("None" if moments is None else str(tuple(moments.shape))))
+    if d_zexp is not None and d_zexp.numel() != N:
+        raise _lib.McnerfError(f"d_zexp must hold the {N} rays of d_rgb, got {tuple(d_zexp.shape)}")
+    d = torch.empty(N, S, 4, dtype=torch.float32, device=d_rgb.device)
+    gmax = torch.zeros(1, dtype=torch.int32, device=d_rgb.device) if want_gmax else None
+    _geo.call("mcnerf_geo_composite_bwd_z", sig_rgb, zgrid, zs, jitter, eps, d_rgb, d_fg, d_dist, moments if d_dist is not None else None,
+              d_zexp, *_z_span(near, far), N, S, int(bool(white_back)), d, gmax, _stream())
+    return (d, gmax) if want_gmax else d
+
+
+def gather_depth(depth: Tensor, seg_cam, seg_start, pix: Tensor) -> Tensor:
+    """depth [C, H*W] fp32 on the device (ray distance in world units), pix [n] int64 (segment k = rays [seg_start[k], seg_start[k+1])
+    of camera seg_cam[k]; host lists) -> d_gt [n] fp32: the stored value where it is finite and > 0, else 0.0 (no measurement; a pixel
+    id outside the image as well)."""
+    cams, start, K, n = _seg_arrays(seg_cam, seg_start)
+    if depth.dim() != 2 or pix.numel() != n:
+        raise _lib.McnerfError(f"depth must be [C, H*W] and pix must hold seg_start[-1] = {n} ids, got {tuple(depth.shape)}, {pix.numel()}")
+    out = torch.empty(n, dtype=torch.float32, device=pix.device)
+    _geo.call("mcnerf_geo_gather_depth", depth, int(depth.shape[0]), int(depth.shape[1]), cams, start, K, pix, n, out, _stream())
+    return out
+
+
+def depth_loss(zexp_c: Tensor, zexp_f: Optional[Tensor], d_gt: Tensor, near: float, far: float, weight: float):
+    """-> out [3] = (weight * m, m, n_valid), m = (1 / max(n_valid, 1)) sum_valid (s(zexp_c) - s(d_gt))^2 + (s(zexp_f) - s(d_gt))^2 with
+    s(z) = (z - near) / (far - near) over the rays whose target is finite and > 0, and d_c, d_f | None =
+    (2 weight z_scale / n_valid) (s(zexp) - s(d_gt)) on those rays, exactly 0 on the others; two launches, deterministic."""
+    n = zexp_c.numel()
+    if d_gt.numel() != n or (zexp_f is not None and zexp_f.numel() != n):
+        raise _lib.McnerfError(f"zexp_c, zexp_f and d_gt must hold the same {n} rays")
+    out = torch.zeros(DEPTH_LOSS_OUT, dtype=torch.float32, device=zexp_c.device)   # [3] = the kernel's arrival counter: zero on entry
+    d_c = torch.empty_like(zexp_c)
+    d_f = torch.empty_like(zexp_f) if zexp_f is not None else None
+    _geo.call("mcnerf_geo_depth_loss", zexp_c, zexp_f, d_gt, n, *_z_span(near, far), float(weight), out, d_c, d_f, _stream())
+    return out[:3], d_c, d_f
 
 
 def _list_buffers(N: int, S: int, prefill: bool, idx: Optional[Tensor], dev):

@@ -289,6 +289,16 @@ def blob_scene_alpha(rays_d, rays_o, near=1.0, far=8.0, n_quad=384):
 
 
 @torch.no_grad()
+def blob_scene_depth(rays_d, rays_o, near=1.0, far=8.0, n_quad=384):
+    """Ground-truth depth [M] of the blob scene along unit rays, as ray distance: sum w z / sum w of `blob_scene_render`'s quadrature
+    where the ray's alpha (sum w) is >= 0.5, else 0 -- "no measurement", what a depth sensor reports off the object."""
+    wt, _ = _blob_quadrature(rays_d, rays_o, near, far, n_quad)
+    a = wt.sum(1)
+    z = torch.linspace(near, far, n_quad, device=rays_d.device)
+    return torch.where(a >= 0.5, (wt * z).sum(1) / a.clamp_min(1e-8), torch.zeros_like(a))
+
+
+@torch.no_grad()
 def lens_rays(pose, K, lens, H, W):
     """All H*W rays (rays_d, rays_o [H*W,3] fp32) of ONE radially distorted camera (pose [3,4], K [3,3], lens [2] = (k1, k2)), built in
     fp64 on the host: pixel centre -> normalised observed coordinates -> undistorted (the root to convergence) -> rotated, normalised."""
@@ -339,6 +349,20 @@ def blob_scene_alpha_images(pose, K, H, W, chunk=8192):
     for i in range(pose.shape[0]):
         d, o = ops.raygen_fwd(pose[i].contiguous(), Kinv[i].contiguous(), allpix, W)
         out.append(torch.cat([blob_scene_alpha(d[j:j + chunk], o[j:j + chunk]) for j in range(0, H * W, chunk)]))
+    return torch.stack(out)
+
+
+@torch.no_grad()
+def blob_scene_depth_images(pose, K, H, W, chunk=8192):
+    """[C, H*W] fp32 ground-truth depth (ray distance; 0 = no measurement) of the blob scene for the pinhole cameras of
+    `blob_scene_images` (same rays): what `DeviceImageSet(..., depth=...)` takes."""
+    from . import ops
+    Kinv = torch.linalg.inv(K)
+    allpix = torch.arange(H * W, device=pose.device)
+    out = []
+    for i in range(pose.shape[0]):
+        d, o = ops.raygen_fwd(pose[i].contiguous(), Kinv[i].contiguous(), allpix, W)
+        out.append(torch.cat([blob_scene_depth(d[j:j + chunk], o[j:j + chunk]) for j in range(0, H * W, chunk)]))
     return torch.stack(out)
 
 
