@@ -867,12 +867,21 @@ def cap_gather(idx: Tensor, perm: Tensor, keep: int):
     return idx2, count
 
 
-def cap_random(idx: Tensor, count: Tensor, max_rows: int, keep: int, seed: Tensor):
-    """Device-side random cap (model/mc_nerf.py:630-632 without the host sync): -> idx2 [keep,2], count2 = min(count, keep)."""
+def cap_random(idx: Tensor, count: Tensor, max_rows: int, keep: int, seed: Tensor, ws: Optional[Tensor] = None,
+               out: Optional[Tensor] = None):
+    """Device-side random cap (model/mc_nerf.py:630-632 without the host sync): -> idx2 [keep,2], count2 = min(count, keep).
+    `ws`: the caller's own scratch of mcnerf_cap_ws_words() int32 words (whatever it holds; the call clears it first); `out`: the
+    caller's own [keep,2] list buffer (rows beyond count2 are left as they are)."""
     dev = idx.device
-    idx2 = torch.empty(keep, 2, dtype=torch.int32, device=dev)
+    n_ws = int(_lib.lib().mcnerf_cap_ws_words())
+    if ws is not None and ws.numel() < n_ws:
+        raise _lib.McnerfError(f"cap_random: ws must hold {n_ws} words, got {tuple(ws.shape)}")
+    if out is not None and out.numel() < keep * 2:
+        raise _lib.McnerfError(f"cap_random: out must hold keep = {keep} pairs, got {tuple(out.shape)}")
+    idx2 = torch.empty(keep, 2, dtype=torch.int32, device=dev) if out is None else out
     count2 = torch.empty(1, dtype=torch.int32, device=dev)
-    ws = torch.empty(int(_lib.lib().mcnerf_cap_ws_words()), dtype=torch.int32, device=dev)
+    if ws is None:
+        ws = torch.empty(n_ws, dtype=torch.int32, device=dev)
     _lib.call("mcnerf_cap_random", idx, count, int(max_rows), int(keep), seed,
               ws, idx2, count2, _stream())
     return idx2, count2

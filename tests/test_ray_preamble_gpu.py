@@ -15,6 +15,7 @@ import pytest
 import torch
 
 from conftest import GOLDEN, load_golden
+from list_ref import hash32
 
 pytestmark = pytest.mark.gpu
 
@@ -44,17 +45,12 @@ def _same(got, recorded, prefix, n_expected):
 
 def feistel_perm(i, n, seed):
     """mcn_feistel_perm(i, n, &seed, 0) in numpy: uint32 arithmetic held in uint64 (a product of two 32-bit words fits)."""
-    u, M = np.uint64, np.uint64(0xFFFFFFFF)
+    u = np.uint64
     bits = 1
     while bits < 32 and (1 << bits) < n:
         bits += 1
     half = u((bits + 1) // 2)
     mask = u((1 << int(half)) - 1)
-
-    def hash32(sd, x):
-        x = (x * u(0x9E3779B9) + u(sd)) & M
-        x ^= x >> u(16); x = (x * u(0x85EBCA6B)) & M; x ^= x >> u(13); x = (x * u(0xC2B2AE35)) & M; x ^= x >> u(16)
-        return x
     x = np.asarray(i, dtype=u)
     walking = np.ones(x.shape, dtype=bool)
     while walking.any():
