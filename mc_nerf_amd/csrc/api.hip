@@ -445,7 +445,9 @@ int mcnerf_select_fine(const float* w_sel, const uint32_t* wmax_bits, float thre
 }
 int mcnerf_sample_pdf(const float* w, const float* zgrid, const float* jitter, const float* u, int N, int Sc, int I,
                       float* z_all, void* stream) {
-    REQ(w && zgrid && u && z_all && N >= 0 && Sc >= 3 && I >= 1 && Sc + I <= MCN_PDF_MAX_SAMPLES, "mcnerf_sample_pdf");
+    REQ(N >= 0 && Sc >= 3 && I >= 1 && Sc + I <= MCN_PDF_MAX_SAMPLES, "mcnerf_sample_pdf");
+    if (N == 0) return 0;                 // (as mcnerf_composite_fwd)
+    REQ(w && zgrid && u && z_all, "mcnerf_sample_pdf");
     REQ((long long)N * (Sc + I) < (1ll << 31), "mcnerf_sample_pdf");
     McnSamplePdfArgs a = {w, zgrid, jitter, u, N, Sc, I, z_all};
     return check("mcnerf_sample_pdf", mcn_launch_sample_pdf(a, (hipStream_t)stream));

@@ -3,8 +3,11 @@
 // distortion.hip (the regulariser library: a gradient on the distortion loss) and depth.hip (the geometry library: a gradient on the
 // expected depth).  Device code and the launch helper only; every library compiles its own instantiations.
 //
-// The mask, distortion and depth paths (mcn_weight_sweep64, and the backward with FRONT, DIST or ZEXP) form the per-sample quantities and the
-// transmittance product in FP64 (mcn_sample64, wave_incl_prod_f64).  The fp32 form does not hold the feature's parity bar on
+// The mask, distortion and depth paths (mcn_weight_sweep64) and EVERY backward form the per-sample quantities and the
+// transmittance product in FP64 (mcn_sample64, wave_incl_prod_f64).  The plain rgb backward had an fp32 prefix pass of its own: the
+// sigma head's gradient, a sum over all samples that cancels 10- to 80-fold, came out 3e-4 of its value off an fp64 evaluation (at
+// 8 and at 96 samples per ray alike; 1e-4 with this prefix pass, 4e-5 .. 9e-5 for torch's fp32 autograd on the same inputs).
+// The fp32 form also does not hold the features' parity bar on
 // semi-transparent rays of a thousand samples: u = 0.997 there, the device's expf near 1 is biased by -0.10 * 2^-24 (measured; the host's by +0.005), and the
 // bias adds LINEARLY over the product -- 5e-6 in fg and 1e-5 in d_sig_rgb at S = 1024, five times the bar -- where rounding errors add
 // as a random walk.  The weights are those of the colour composite to that difference (<= 6e-6 at S >= 1024, <= 6e-7 at S <= 128).
@@ -95,9 +98,9 @@ struct McnCompositeBwdView {
 //   d alpha_j = dw_j T_j - (sum_{k>j} dw_k w_k) / u_j      (the cumprod gradient, division form)
 // with dw_j = d_rgb . (c_j - wb).  Per-ray intermediates are staged in LDS (5 floats per sample per wave, `sm`) between the prefix
 // and the suffix pass.  One wave per ray, grid-strided, in blocks of 4 waves.
-// With FRONT the prefix pass forms T, u, e and w in fp64 (rounded once into the same LDS words; the suffix pass is the same) and
-// d_fg[n] d fg / d alpha_j is added for j + 1 < S: what dw_j + d_fg would give, in a form that does not cancel (below).
-// With DIST the prefix pass is the fp64 one as well, forms A_j, B_j by fp64 scans (W, M from the forward's moments) and adds
+// The prefix pass forms T, u, e and w in fp64 (rounded once into the LDS words; the suffix pass reads them as fp32).
+// With FRONT d_fg[n] d fg / d alpha_j is added for j + 1 < S: what dw_j + d_fg would give, in a form that does not cancel (below).
+// With DIST the prefix pass forms A_j, B_j by fp64 scans (W, M from the forward's moments) and adds
 // d_dist[n] d dist / d w_j to dw_j BEFORE sDW / sDWW are stored (dw and dw w are formed in fp64 and rounded once); the suffix sum of
 // dw w then runs in fp64 over those words.  The d_fg term, when both are given, is the closed form unchanged.
 //   d dist / d w_j = 2 [ s_j (2 A_j + w_j - W) + M - 2 B_j - w_j s_j ]  +  (2/3) w_j (s_{j+1} - s_j) [j < S-1]      (distortion.hip)
@@ -119,7 +122,6 @@ __device__ __forceinline__ void mcn_composite_bwd_rays(const McnCompositeBwdView
     const float wb = a.white_back ? 1.f : 0.f;
     const f32x4* sr = reinterpret_cast<const f32x4*>(a.sig_rgb) + (size_t)n * S;
     f32x4* dst = reinterpret_cast<f32x4*>(a.d_sig_rgb) + (size_t)n * S;
-    float carryT = 1.f;
     double carryT64 = 1.0;
     double gd = 0.0, Wt = 0.0, Mt = 0.0, carryA = 0.0, carryB = 0.0;
     if constexpr (DIST) { gd = (double)a.d_dist[n]; Wt = a.moments[(size_t)n * 2]; Mt = a.moments[(size_t)n * 2 + 1]; }
@@ -139,56 +141,32 @@ __device__ __forceinline__ void mcn_composite_bwd_rays(const McnCompositeBwdView
         const int j = base + lane;
         const bool ok = j < S;
         f32x4 v = {0.f, 0.f, 0.f, 0.f};
-        if constexpr (FRONT || DIST || ZEXP) {     // the sample and the transmittance in fp64, see the top
-            float e1 = 0.f;
-            if (ok) { v = sr[j]; e1 = a.eps[(size_t)n * S + j]; }
-            const McnWeight64 q = mcn_weight_sweep64(v[0], e1, zrow, jit, j, S, carryT64);
-            double sj = 0.0, ds = 0.0;
-            McnDistScan p = {0.0, 0.0};
-            if constexpr (DIST) {          // + the two sums; the depths are constants of the backward
-                if (ok) {
-                    sj = ((double)__fadd_rn(zrow[j], jit) - zn) * zs;
-                    ds = (j + 1 < S) ? q.delta * zs : 0.0;
+        // the sample and the transmittance in fp64, see the top
+        float e1 = 0.f;
+        if (ok) { v = sr[j]; e1 = a.eps[(size_t)n * S + j]; }
+        const McnWeight64 q = mcn_weight_sweep64(v[0], e1, zrow, jit, j, S, carryT64);
+        double sj = 0.0, ds = 0.0;
+        McnDistScan p = {0.0, 0.0};
+        if constexpr (DIST) {          // + the two sums; the depths are constants of the backward
+            if (ok) {
+                sj = ((double)__fadd_rn(zrow[j], jit) - zn) * zs;
+                ds = (j + 1 < S) ? q.delta * zs : 0.0;
+            }
+            p = mcn_dist_scan(q.w, sj, carryA, carryB);
+        }
+        if (ok) {
+            const float w = (float)q.w;
+            const float dwc = g0 * (v[1] - wb) + g1 * (v[2] - wb) + g2 * (v[3] - wb);
+            if constexpr (DIST || ZEXP) {
+                double dw = (double)dwc;
+                if constexpr (DIST) {
+                    const double ddw = 2.0 * (sj * (2.0 * p.A + q.w - Wt) + Mt - 2.0 * p.B - q.w * sj) + (2.0 / 3.0) * q.w * ds;
+                    dw = (double)dwc + gd * ddw;
                 }
-                p = mcn_dist_scan(q.w, sj, carryA, carryB);
-            }
-            if (ok) {
-                const float w = (float)q.w;
-                const float dwc = g0 * (v[1] - wb) + g1 * (v[2] - wb) + g2 * (v[3] - wb);
-                if constexpr (DIST || ZEXP) {
-                    double dw = (double)dwc;
-                    if constexpr (DIST) {
-                        const double ddw = 2.0 * (sj * (2.0 * p.A + q.w - Wt) + Mt - 2.0 * p.B - q.w * sj) + (2.0 / 3.0) * q.w * ds;
-                        dw = (double)dwc + gd * ddw;
-                    }
-                    if constexpr (ZEXP) dw += gz * (double)__fadd_rn(zrow[j], jit);      // the depths are constants of the backward
-                    stage(j, (float)q.T, (float)q.u, (float)q.e, w, (float)dw, (float)(dw * q.w));
-                } else {
-                    stage(j, (float)q.T, (float)q.u, (float)q.e, w, dwc, dwc * w);
-                }
-            }
-        } else {
-            float delta = 0.f, e1 = 0.f;
-            if (ok) {
-                v = sr[j];
-                const float z = __fadd_rn(zrow[j], jit);
-                delta = (j + 1 < S) ? __fsub_rn(__fadd_rn(zrow[j + 1], jit), z) : 1e10f;
-                e1 = a.eps[(size_t)n * S + j];
-            }
-            const float sx = v[0] + e1;
-            const float sp = softplus_t(sx);
-            const float ex = ok ? expf(-delta * sp) : 1.f;
-            const float alpha = 1.f - ex;
-            const float u = ok ? (1.f - alpha) + 1e-10f : 1.f;
-            const float inc = wave_incl_prod(u);
-            const float excl = wave_shr1(inc, 1.f);
-            const float T = carryT * excl;
-            carryT *= wave_last(inc);
-            if (ok) {
-                const float w = alpha * T;
-                const float dw = g0 * (v[1] - wb) + g1 * (v[2] - wb) + g2 * (v[3] - wb);
-                const float dsp = sx > 20.f ? 1.f : 1.f / (1.f + expf(-sx));      // d softplus
-                stage(j, T, u, ex * delta * dsp, w, dw, dw * w);
+                if constexpr (ZEXP) dw += gz * (double)__fadd_rn(zrow[j], jit);      // the depths are constants of the backward
+                stage(j, (float)q.T, (float)q.u, (float)q.e, w, (float)dw, (float)(dw * q.w));
+            } else {
+                stage(j, (float)q.T, (float)q.u, (float)q.e, w, dwc, dwc * w);
             }
         }
     }

@@ -723,17 +723,22 @@ def select_fine(w_sel: Tensor, wmax: Tensor, thresh: float, scale: int, sigma_de
     return idx, count, out_f
 
 
-def sample_pdf(w_sel: Tensor, zgrid: Tensor, jitter: Optional[Tensor], u: Tensor) -> Tensor:
+def sample_pdf(w_sel: Tensor, zgrid: Tensor, jitter: Optional[Tensor], u: Tensor, out: Optional[Tensor] = None) -> Tensor:
     """Inverse-CDF hierarchical sampling (include/mcnerf.h: mcnerf_sample_pdf): coarse selection weights w_sel [N,Sc], the coarse
     grid zgrid [Sc], jitter [N] | None and uniform draws u [N,I] -> z_all [N,Sc+I] = sort(coarse depths ++ importance samples).
-    Not differentiable (z_all is a constant of the fine pass, as in vanilla NeRF)."""
+    Not differentiable (z_all is a constant of the fine pass, as in vanilla NeRF).
+    `out`: the caller's own z_all (fp32, contiguous, [N,Sc+I], on w_sel's device), e.g. rows of a larger buffer; it is returned."""
     N, Sc = w_sel.shape
     if u.dim() != 2 or u.shape[0] != N or zgrid.numel() != Sc or (jitter is not None and jitter.numel() != N):
         raise _lib.McnerfError(f"sample_pdf: w_sel [N,Sc] {tuple(w_sel.shape)}, zgrid [Sc] {tuple(zgrid.shape)}, u [N,I] {tuple(u.shape)}")
     I = u.shape[1]
-    z_all = torch.empty(N, Sc + I, dtype=torch.float32, device=w_sel.device)
-    _lib.call("mcnerf_sample_pdf", w_sel, zgrid, jitter, u, N, Sc, I, z_all, _stream())
-    return z_all
+    if out is None:
+        out = torch.empty(N, Sc + I, dtype=torch.float32, device=w_sel.device)
+    elif tuple(out.shape) != (N, Sc + I) or out.dtype != torch.float32 or out.device != w_sel.device or not out.is_contiguous():
+        raise _lib.McnerfError(f"sample_pdf: out must be a contiguous fp32 [N = {N}, Sc + I = {Sc + I}] tensor on {w_sel.device}, got "
+                               f"{out.dtype} {tuple(out.shape)} on {out.device}{'' if out.is_contiguous() else ', not contiguous'}")
+    _lib.call("mcnerf_sample_pdf", w_sel, zgrid, jitter, u, N, Sc, I, out, _stream())
+    return out
 
 
 # --------------------------------------------------------------------------- voxel sigma cache (include/mcnerf.h: mcnerf_voxel_*)

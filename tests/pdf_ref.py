@@ -5,6 +5,16 @@ checked with the oracle's general `inference()` / `composite()`, which take any 
 import torch
 
 
+def pdf_cdf_ref(w):
+    """w [N,Sc] coarse selection weights -> (pdf [N,Sc-2], cdf [N,Sc-1]) of the interior bins, cdf[:, 0] = 0."""
+    wb = w.float()[:, 1:-1] + 1e-5                                        # interior weights, floored [N, Sc-2]
+    # the total and the running sums are the correctly rounded ones (fp64 accumulation, one rounding to fp32): the sampler's CDF does
+    # not depend on the order of a sum
+    pdf = wb / wb.double().sum(-1, keepdim=True).float()
+    cdf = torch.cat([torch.zeros_like(pdf[:, :1]), torch.cumsum(pdf.double(), -1).float()], -1)       # [N, Sc-1]
+    return pdf, cdf
+
+
 def sample_pdf_ref(w, zgrid, jitter, u):
     """w [N,Sc] coarse selection weights, zgrid [Sc], jitter [N] / [N,1] or None, u [N,I] in [0,1] (any order)
     -> (z_all [N,Sc+I] sorted, zs [N,I] the importance samples in u's order, zc [N,Sc] the coarse depths)."""
@@ -13,11 +23,7 @@ def sample_pdf_ref(w, zgrid, jitter, u):
     jit = torch.zeros(N, dtype=torch.float32, device=w.device) if jitter is None else jitter.reshape(N).float()
     zc = zgrid.reshape(1, Sc).float() + jit.unsqueeze(1)                 # the coarse pass's depths (one fp32 rounding)
     mid = 0.5 * (zc[:, :-1] + zc[:, 1:])                                  # bin edges [N, Sc-1]
-    wb = w[:, 1:-1] + 1e-5                                                # interior weights, floored [N, Sc-2]
-    # the total and the running sums are the correctly rounded ones (fp64 accumulation, one rounding to fp32): the sampler's CDF does
-    # not depend on the order of a sum
-    pdf = wb / wb.double().sum(-1, keepdim=True).float()
-    cdf = torch.cat([torch.zeros_like(pdf[:, :1]), torch.cumsum(pdf.double(), -1).float()], -1)       # [N, Sc-1]
+    pdf, cdf = pdf_cdf_ref(w)
     ind = torch.searchsorted(cdf, u.contiguous(), right=True)             # #{i : cdf[i] <= u}
     below = (ind - 1).clamp(min=0)
     above = ind.clamp(max=Sc - 2)
