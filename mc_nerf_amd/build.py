@@ -1,5 +1,6 @@
 """Builds mc_nerf_amd/libmcnerf.so and, beside it, the extension library mc_nerf_amd/libmcnext.so, the regulariser library
-mc_nerf_amd/libmcnreg.so and the geometry library mc_nerf_amd/libmcngeo.so (hipcc, gfx950 only) in-tree.
+mc_nerf_amd/libmcnreg.so, the geometry library mc_nerf_amd/libmcngeo.so and the bounds library mc_nerf_amd/libmcnbox.so (hipcc,
+gfx950 only) in-tree.
 
     python -m mc_nerf_amd.build [--force]
 
@@ -14,7 +15,8 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 OUT = os.path.join(HERE, "libmcnerf.so")
 SOURCES = ["api.hip", "pack.hip", "mlp_fwd.hip", "mlp_bwd.hip", "mlp_dw.hip", "pack16.hip", "mlp16_fwd.hip", "mlp16_bwd.hip", "mlp16_dw.hip", "mlp_x3_fwd.hip", "mlp_x3_bwd.hip", "mlp_x3_dw.hip", "composite.hip", "sample_pdf.hip", "select.hip", "rays.hip", "voxel.hip", "optim.hip", "optim_rows.hip", "camera.hip", "color_calib.hip", "errmap.hip", "lens.hip"]
-HEADERS = ["mcnerf_common.h", "mcnerf_kernels.h", "mcnerf_wave.h", "mcnerf_composite.h", "mcnerf_16.h", "mcnerf_x3.h", "mcnerf_launch.h", "mcnerf_voxel.h", "mcnerf_multicam.h", "mcnerf_colorcal.h", "mcnerf_errmap.h", "mcnerf_maxkey.h", "mcnerf_compact.h", "mcnerf_hash.h", "mcnerf_rays.h", "mcnerf_lens.h", "mcnerf_optim_rows.h", os.path.join("..", "..", "include", "mcnerf.h")]
+HEADERS = ["mcnerf_common.h", "mcnerf_kernels.h", "mcnerf_wave.h", "mcnerf_composite.h", "mcnerf_16.h", "mcnerf_x3.h", "mcnerf_launch.h", "mcnerf_voxel.h",
+           "mcnerf_sample_pdf.h", "mcnerf_multicam.h", "mcnerf_colorcal.h", "mcnerf_errmap.h", "mcnerf_maxkey.h", "mcnerf_compact.h", "mcnerf_hash.h", "mcnerf_rays.h", "mcnerf_lens.h", "mcnerf_optim_rows.h", os.path.join("..", "..", "include", "mcnerf.h")]
 # The extension library (include/mcnerf_ext.h): opt-in features whose entry points are not part of the core ABI.  Its
 # objects share the object directory; nothing of it is linked into libmcnerf.so and it links none of the core's objects.
 EXT_OUT = os.path.join(HERE, "libmcnext.so")
@@ -32,6 +34,15 @@ GEO_OUT = os.path.join(HERE, "libmcngeo.so")
 GEO_SOURCES = ["geo_api.hip", "depth.hip"]
 GEO_HEADERS = ["mcnerf_common.h", "mcnerf_wave.h", "mcnerf_composite.h", "mcnerf_multicam.h", "mcnerf_depth.h", os.path.join("..", "..", "include", "mcnerf.h"),
                os.path.join("..", "..", "include", "mcnerf_geo.h")]
+# The bounds library (include/mcnerf_box.h): the geometry library's ABI is pinned too, so per-ray sample bounds have a
+# fifth library, built the same way.  The sampler's device code reaches it through mcnerf_sample_pdf.h and the voxel kernels by
+# ray_bounds.hip including voxel.hip (listed with the headers: a change of it recompiles ray_bounds.hip); none of its objects is
+# linked into the other four and it links none of theirs.
+BOX_OUT = os.path.join(HERE, "libmcnbox.so")
+BOX_SOURCES = ["box_api.hip", "ray_bounds.hip"]
+BOX_HEADERS = ["mcnerf_common.h", "mcnerf_kernels.h", "mcnerf_wave.h", "mcnerf_voxel.h", "voxel.hip", "mcnerf_compact.h", "mcnerf_maxkey.h",
+               "mcnerf_sample_pdf.h", "mcnerf_ray_bounds.h", os.path.join("..", "..", "include", "mcnerf.h"),
+               os.path.join("..", "..", "include", "mcnerf_box.h")]
 # the f16x3 chains: a layer body is ~400 MFMAs with its epilogue slices, fully unrolled (beyond hipcc's default pragma-unroll budget);
 # their 256-wide instantiations run one wave per SIMD with 512 registers, where hipcc would otherwise put the MFMA
 # accumulators in AGPRs (every epilogue read then costs a v_accvgpr_read behind a full MFMA drain)
@@ -47,7 +58,8 @@ def _newer(a, b):
 
 
 def build(force=False, verbose=True):
-    """All four libraries; returns the core library's path."""
+    """All five libraries; returns the core library's path."""
+    _build_library(BOX_SOURCES, BOX_HEADERS, BOX_OUT, force, verbose)
     _build_library(GEO_SOURCES, GEO_HEADERS, GEO_OUT, force, verbose)
     _build_library(EXT_SOURCES, EXT_HEADERS, EXT_OUT, force, verbose)
     _build_library(REG_SOURCES, REG_HEADERS, REG_OUT, force, verbose)

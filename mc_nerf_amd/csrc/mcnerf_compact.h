@@ -48,6 +48,67 @@ __device__ __forceinline__ void mcn_compact_write(int N, int S, int scale, const
     }
 }
 
+// The body of the scan kernel (one workgroup of 1024; described at select_scan_kernel, select.hip): exclusive scan of ray_counts [N] ->
+// ray_offsets [N], total -> *count.
+__device__ __forceinline__ void mcn_scan_counts(int N, const int* ray_counts, int* ray_offsets, int* count) {
+    __shared__ int wsum[16];
+    constexpr int MAXQ = 16;
+    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    const int per = (((N + 1023) / 1024) + 3) & ~3;
+    const int lo = min(tid * per, N), hi = min(lo + per, N);
+    const bool vec = per <= 4 * MAXQ && ((reinterpret_cast<size_t>(ray_counts) | reinterpret_cast<size_t>(ray_offsets)) & 15) == 0;
+    int4 v[MAXQ];
+    int s = 0;
+    if (vec) {
+#pragma unroll
+        for (int q = 0; q < MAXQ; ++q) {
+            const int b = lo + 4 * q;
+            int4 x = make_int4(0, 0, 0, 0);
+            if (4 * q < per) {
+                if (b + 3 < hi) x = *reinterpret_cast<const int4*>(ray_counts + b);
+                else {
+                    if (b < hi) x.x = ray_counts[b];
+                    if (b + 1 < hi) x.y = ray_counts[b + 1];
+                    if (b + 2 < hi) x.z = ray_counts[b + 2];
+                }
+            }
+            v[q] = x;
+        }
+#pragma unroll
+        for (int q = 0; q < MAXQ; ++q) s += (v[q].x + v[q].y) + (v[q].z + v[q].w);
+    } else {
+        for (int i = lo; i < hi; ++i) s += ray_counts[i];
+    }
+    int inc = s;
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) { const int t = __shfl_up(inc, o); if (lane >= o) inc += t; }
+    if (lane == 63) wsum[wv] = inc;
+    __syncthreads();
+    int woff = 0, total = 0;
+#pragma unroll
+    for (int w = 0; w < 16; ++w) { const int t = wsum[w]; woff += w < wv ? t : 0; total += t; }
+    int run = woff + inc - s;
+    if (vec) {
+#pragma unroll
+        for (int q = 0; q < MAXQ; ++q) {
+            const int b = lo + 4 * q;
+            if (4 * q < per && b < hi) {
+                int4 o;
+                o.x = run; run += v[q].x; o.y = run; run += v[q].y; o.z = run; run += v[q].z; o.w = run; run += v[q].w;
+                if (b + 3 < hi) *reinterpret_cast<int4*>(ray_offsets + b) = o;
+                else {
+                    ray_offsets[b] = o.x;
+                    if (b + 1 < hi) ray_offsets[b + 1] = o.y;
+                    if (b + 2 < hi) ray_offsets[b + 2] = o.z;
+                }
+            }
+        }
+    } else {
+        for (int i = lo; i < hi; ++i) { const int t = ray_counts[i]; ray_offsets[i] = run; run += t; }
+    }
+    if (tid == 0) *count = total;
+}
+
 // the scan alone (select.hip), N >= 1: ray_counts [N] -> exclusive ray_offsets [N], total -> *count
 hipError_t mcn_launch_select_scan(int N, int* ray_counts, int* ray_offsets, int* count, hipStream_t st);
 

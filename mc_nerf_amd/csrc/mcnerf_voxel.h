@@ -10,7 +10,7 @@ struct McnVoxelSelectArgs {
     float bmin, s, thresh;    // a sample is listed when vox[cell] > thresh
     const float* rays_o;      // [N,3]
     const float* rays_d;      // [N,3]
-    const float* zgrid;       // [Sc]
+    const float* zgrid;       // [Sc], or [N,Sc] with z_stride = Sc
     const float* jitter;      // [N] or null
     int N, Sc;
     float sigma_default;
@@ -19,6 +19,7 @@ struct McnVoxelSelectArgs {
     int2* idx;                // [N*Sc] out, torch.nonzero order
     int* count;               // out (device)
     float* out_c;             // [N,Sc,4] prefilled with (sigma_default,1,1,1), or null
+    int z_stride = 0;         // 0: zgrid is the shared grid [Sc]; Sc: zgrid holds one row of depths per ray, [N,Sc]
 };
 hipError_t mcn_launch_voxel_select(const McnVoxelSelectArgs& a, hipStream_t st);
 struct McnVoxelUpdateArgs {
@@ -31,13 +32,14 @@ struct McnVoxelUpdateArgs {
     int M;
     const float* rays_o;      // [N,3]
     const float* rays_d;      // [N,3]
-    const float* zgrid;       // [Sc]
+    const float* zgrid;       // [Sc], or [N,Sc] with z_stride = Sc
     const float* jitter;      // [N] or null
     int N, Sc;
     const int2* idx;          // [max_rows] (ray, sample) pairs with *count of them valid, or null = all N * Sc pairs
     const int* count;
     int max_rows;
     const float* sig_rgb;     // [N,Sc,4]: sigma of pair (n, j) at ((n * Sc) + j) * 4
+    int z_stride = 0;         // as McnVoxelSelectArgs::z_stride
 };
 hipError_t mcn_launch_voxel_update(const McnVoxelUpdateArgs& a, hipStream_t st);
 hipError_t mcn_launch_voxel_query(const float* vox, int G, float bmin, float s, const float* pts, int M, float* out, hipStream_t st);

@@ -20,68 +20,13 @@ __global__ __launch_bounds__(256) void select_count_kernel(McnSelectArgs a) {
     mcn_compact_count<SelectPred>(a.N, a.Sc, a.scale, a.sigma_default, a.ray_counts, a.out_f, a);
 }
 
-// Exclusive scan of ray_counts -> ray_offsets, total -> *count.  One workgroup; N is at most ~1e6.  Every thread owns one
-// contiguous run of `per` rays per thread: a private sum, ONE block-wide scan of the 1024 run sums, then the run's offsets -- two
+// Exclusive scan of ray_counts -> ray_offsets, total -> *count; the body is mcn_scan_counts (mcnerf_compact.h), shared with the bounds
+// library.  One workgroup; N is at most ~1e6.  Every thread owns one contiguous run of `per` rays per thread: a private sum, ONE block-wide scan of the 1024 run sums, then the run's offsets -- two
 // barriers in all.  A run is a multiple of four rays held in registers as int4 vectors: its loads (and its stores) are independent
 // 16-byte operations in flight together (the scalar loop of dependent 4-byte loads over a 32-ray run took 53 us at 32768 rays);
 // runs longer than 64 rays (N > 65536) or unaligned workspaces take the scalar loop.
 __global__ __launch_bounds__(1024) void select_scan_kernel(McnSelectArgs a) {
-    __shared__ int wsum[16];
-    constexpr int MAXQ = 16;
-    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-    const int per = (((a.N + 1023) / 1024) + 3) & ~3;
-    const int lo = min(tid * per, a.N), hi = min(lo + per, a.N);
-    const bool vec = per <= 4 * MAXQ && ((reinterpret_cast<size_t>(a.ray_counts) | reinterpret_cast<size_t>(a.ray_offsets)) & 15) == 0;
-    int4 v[MAXQ];
-    int s = 0;
-    if (vec) {
-#pragma unroll
-        for (int q = 0; q < MAXQ; ++q) {
-            const int b = lo + 4 * q;
-            int4 x = make_int4(0, 0, 0, 0);
-            if (4 * q < per) {
-                if (b + 3 < hi) x = *reinterpret_cast<const int4*>(a.ray_counts + b);
-                else {
-                    if (b < hi) x.x = a.ray_counts[b];
-                    if (b + 1 < hi) x.y = a.ray_counts[b + 1];
-                    if (b + 2 < hi) x.z = a.ray_counts[b + 2];
-                }
-            }
-            v[q] = x;
-        }
-#pragma unroll
-        for (int q = 0; q < MAXQ; ++q) s += (v[q].x + v[q].y) + (v[q].z + v[q].w);
-    } else {
-        for (int i = lo; i < hi; ++i) s += a.ray_counts[i];
-    }
-    int inc = s;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) { const int t = __shfl_up(inc, o); if (lane >= o) inc += t; }
-    if (lane == 63) wsum[wv] = inc;
-    __syncthreads();
-    int woff = 0, total = 0;
-#pragma unroll
-    for (int w = 0; w < 16; ++w) { const int t = wsum[w]; woff += w < wv ? t : 0; total += t; }
-    int run = woff + inc - s;
-    if (vec) {
-#pragma unroll
-        for (int q = 0; q < MAXQ; ++q) {
-            const int b = lo + 4 * q;
-            if (4 * q < per && b < hi) {
-                int4 o;
-                o.x = run; run += v[q].x; o.y = run; run += v[q].y; o.z = run; run += v[q].z; o.w = run; run += v[q].w;
-                if (b + 3 < hi) *reinterpret_cast<int4*>(a.ray_offsets + b) = o;
-                else {
-                    a.ray_offsets[b] = o.x;
-                    if (b + 1 < hi) a.ray_offsets[b + 1] = o.y;
-                    if (b + 2 < hi) a.ray_offsets[b + 2] = o.z;
-                }
-            }
-        }
-    } else {
-        for (int i = lo; i < hi; ++i) { const int t = a.ray_counts[i]; a.ray_offsets[i] = run; run += t; }
-    }
-    if (tid == 0) *a.count = total;
+    mcn_scan_counts(a.N, a.ray_counts, a.ray_offsets, a.count);
 }
 
 __global__ __launch_bounds__(256) void select_write_kernel(McnSelectArgs a) {

@@ -9,6 +9,8 @@
 // division);  i = (int) min(max(t, 0), G - 1) -- fmaxf(NaN, 0) = 0, so a NaN lands in cell 0 and nothing indexes outside the grid;
 // linear index (ix * G + iy) * G + iz in 64 bits.  Sample j of ray n sits at p = o + d * z, z = zgrid[j] + jitter[n], every step a
 // separately rounded fp32 operation (as sample_pdf.hip forms its depths): the cell of a sample is a pure function of its inputs.
+// With z_stride = Sc (McnVoxelSelectArgs / McnVoxelUpdateArgs) zgrid holds one row of depths per ray, z = zgrid[n * Sc + j] (+ jitter[n]):
+// the bounds library (ray_bounds.hip) compiles this file into itself for its per-ray-rows entry points, so every kernel here exists once.
 //
 // SELECT: the ordered list compaction of mcnerf_compact.h with scale 1 under the predicate vox[cell] > thresh (a NaN cell is empty).
 // UPDATE: the "max per cell, single writer" protocol of mcnerf_maxkey.h on the grid, an item being a sample and its raw sigma.
@@ -25,9 +27,10 @@ __device__ __forceinline__ size_t vox_cell(float x, float y, float z, float bmin
     return (ix * (size_t)G + iy) * (size_t)G + iz;
 }
 // the cell of sample j of ray n
-__device__ __forceinline__ size_t vox_sample_cell(const float* rays_o, const float* rays_d, const float* zgrid, const float* jitter,
+__device__ __forceinline__ size_t vox_sample_cell(const float* rays_o, const float* rays_d, const float* zgrid, int z_stride, const float* jitter,
                                                   int n, int j, float bmin, float s, int G) {
-    const float z = jitter ? __fadd_rn(zgrid[j], jitter[n]) : zgrid[j];
+    const float zr = zgrid[(size_t)n * z_stride + j];
+    const float z = jitter ? __fadd_rn(zr, jitter[n]) : zr;
     const float* o = rays_o + (size_t)n * 3;
     const float* d = rays_d + (size_t)n * 3;
     return vox_cell(__fadd_rn(o[0], __fmul_rn(d[0], z)), __fadd_rn(o[1], __fmul_rn(d[1], z)), __fadd_rn(o[2], __fmul_rn(d[2], z)), bmin, s, G);
@@ -37,7 +40,7 @@ __device__ __forceinline__ size_t vox_sample_cell(const float* rays_o, const flo
 struct VoxelPred {
     const McnVoxelSelectArgs& a;
     __device__ __forceinline__ bool operator()(int n, int j) const {
-        return a.vox[vox_sample_cell(a.rays_o, a.rays_d, a.zgrid, a.jitter, n, j, a.bmin, a.s, a.G)] > a.thresh;
+        return a.vox[vox_sample_cell(a.rays_o, a.rays_d, a.zgrid, a.z_stride, a.jitter, n, j, a.bmin, a.s, a.G)] > a.thresh;
     }
 };
 __global__ __launch_bounds__(256) void voxel_count_kernel(McnVoxelSelectArgs a) {
@@ -69,7 +72,7 @@ __device__ __forceinline__ bool vox_item(const McnVoxelUpdateArgs& a, long long 
             if (i >= (long long)a.N * a.Sc) return false;
             n = (int)(i / a.Sc); j = (int)(i - (long long)n * a.Sc);
         }
-        cell = vox_sample_cell(a.rays_o, a.rays_d, a.zgrid, a.jitter, n, j, a.bmin, a.s, a.G);
+        cell = vox_sample_cell(a.rays_o, a.rays_d, a.zgrid, a.z_stride, a.jitter, n, j, a.bmin, a.s, a.G);
         sig = a.sig_rgb[((size_t)n * a.Sc + j) * 4];
     }
     return (__float_as_uint(sig) & 0x7F800000u) != 0x7F800000u;

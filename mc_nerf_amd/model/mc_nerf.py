@@ -128,6 +128,15 @@ class NeRF_Model(nn.Module):
         self.depth_weight = depth_weight_setting(sys_param)
         self.settings.want_zexp = self.depth_weight > 0.0
         self.last_expected_depth = None   # depth mode: (zexp_c, zexp_f | None) [N] of the last train render, attached to its graph
+        # "ray_bounds" is this build's own key too: "global" (every ray on linspace(near, far); the default and today's path:
+        # nothing is allocated, the bounds library is not even loaded) or "aabb" (every ray on the part of [near, far] inside the scene
+        # box "ray_bounds_box", by default the cube [boader_min, boader_max]^3 of the voxel cache)
+        self.ray_bounds = sys_param.get("ray_bounds", "global")
+        if self.ray_bounds not in ("global", "aabb"):
+            raise ValueError(f"ray_bounds must be 'global' or 'aabb', got {self.ray_bounds!r}")
+        if self.ray_bounds == "aabb":
+            self.settings.ray_bounds, self.settings.box = "aabb", self._bounds_box(sys_param)
+        self.last_ray_span = None         # "aabb" mode: (lo, hi) [N,2] of the last render's rays; (near, far) on a ray the box does not clip
         self.last_coarse_selection = None  # (idx_c, count_c) of the last pruned coarse pass; None in "dense" mode and in the warm-up
         self.last_selection = None        # (idx, count) of the last fine pass in "threshold" mode; None in "pdf" mode
         self.last_z_all = None            # the fine pass's depth rows [N, samples + n_importance] in "pdf" mode
@@ -159,6 +168,27 @@ class NeRF_Model(nn.Module):
             raise ValueError(f"voxel_beta must be in (0, 1], got {beta!r}")
         thresh = number("voxel_thresh", 0.0)
         return dict(voxel_beta=float(beta), voxel_thresh=float(thresh), voxel_warmup_epoch=_int_key(sys_param, "voxel_warmup_epoch", 1, 0))
+
+    @staticmethod
+    def _bounds_box(sys_param):
+        """Reads and validates the box of "aabb" mode (a ValueError names the key) -> (xmin, ymin, zmin, xmax, ymax, zmax) as fp32 values."""
+        if "ray_bounds_box" in sys_param:
+            box = sys_param["ray_bounds_box"]
+            if isinstance(box, (str, bytes)) or not hasattr(box, "__len__") or len(box) != 6:
+                raise ValueError(f"ray_bounds_box must be six numbers (xmin, ymin, zmin, xmax, ymax, zmax), got {box!r}")
+            box = [_number_key({"ray_bounds_box": v}, "ray_bounds_box", None, finite=True) for v in box]
+        else:
+            for key in ("boader_min", "boader_max"):
+                if key not in sys_param:
+                    raise ValueError(f"ray_bounds = 'aabb' needs ray_bounds_box or the cube of boader_min / boader_max: {key} is missing")
+            bmin, bmax = (_number_key(sys_param, key, None, finite=True) for key in ("boader_min", "boader_max"))
+            if not bmin < bmax:
+                raise ValueError(f"boader_min must be below boader_max, got {bmin!r} and {bmax!r}")
+            box = [bmin] * 3 + [bmax] * 3
+        box = tuple(float(torch.tensor(float(v), dtype=torch.float32)) for v in box)
+        if not all(v == v and abs(v) != float("inf") for v in box) or not all(lo < hi for lo, hi in zip(box[:3], box[3:])):
+            raise ValueError(f"ray_bounds_box: every min must be below its max, as fp32 values, got {box!r}")
+        return box
 
     def voxel_grid(self) -> ops.VoxelGrid:
         """The cache's two grids (allocated and filled with `sigma_init` on first use; each rank has its own)."""
@@ -260,6 +290,8 @@ class NeRF_Model(nn.Module):
         want_zexp = self.settings.want_zexp
         if want_zexp and not rays_d.is_cuda:
             raise ops._lib.McnerfError(f"depth_weight = {self.depth_weight}: the expected depth is a HIP kernel, got rays on {dev} (no CPU fallback)")
+        if self.settings.aabb and not rays_d.is_cuda:
+            raise ops._lib.McnerfError(f"ray_bounds = 'aabb': the per-ray depths are a HIP kernel, got rays on {dev} (no CPU fallback)")
         if N == 0:                                  # empty batch: empty results (the reference's tensor ops do the same)
             self.last_expected_depth = (rays_d.new_zeros(0), None if only_coarse else rays_d.new_zeros(0)) if want_zexp else None
             e3, e1 = rays_d.new_zeros(0, 3), rays_d.new_zeros(0, 1)
@@ -285,6 +317,8 @@ class NeRF_Model(nn.Module):
         `u` [N, n_importance] defaults to linspace(0, 1, n_importance) for every ray (a deterministic render) and eps_f is
         [N, samples + n_importance]."""
         N, dev = rays_d.shape[0], rays_d.device
+        if self.settings.aabb and not rays_d.is_cuda:
+            raise ops._lib.McnerfError(f"ray_bounds = 'aabb': the per-ray depths are a HIP kernel, got rays on {dev} (no CPU fallback)")
         if N == 0:
             return rays_d.new_zeros(0, 3), rays_d.new_zeros(0, 1), rays_d.new_zeros(0, 1)
         _, eps_c, eps_sel, u, eps_f = self._draws(N, dev, False, False, None, eps_c, eps_sel, u, eps_f)

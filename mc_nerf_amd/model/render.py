@@ -16,6 +16,9 @@ What a sampler setting changes in its pass:
       the pass: no gradient through the sampler); the rows hold the jitter.
   coarse_sampler "voxel": the list ops.voxel_select reads off the owner's sigma grid, over the prefill.  Train calls keep the grid
       current from their evaluated samples (ops.voxel_update) and run dense in the warm-up; rendering only queries.
+  ray_bounds "aabb": both passes take per-ray rows (`bounds_rows`: ops.ray_depths on the scene box; the rows hold the jitter) where
+      they took the shared grid plus jitter: the voxel list and update, the pdf sampler and the threshold fine pass, which is then a
+      listed pass on rows [N,Sf].  The rows are constants of the backward.
 
 Every random draw of the reference (jitter, the three N(0,1) tensors of sigma2weights, the cap permutation; in "pdf" mode the
 sampler's U(0,1) draws) is an explicit tensor argument: drawn from torch's device RNG by the caller, or passed in by the parity tests.
@@ -55,9 +58,17 @@ class RenderSettings:
     voxel_beta: float = 0.1
     voxel_thresh: float = 0.0
     voxel_warmup_epoch: int = 1
+    # "global": every ray on linspace(near, far) (the reference); "aabb" (DESIGN.md 4k): every ray on its own rows of depths, the grids
+    # mapped onto the part of [near, far] inside `box` = (xmin, ymin, zmin, xmax, ymax, zmax) (ops.ray_depths).  (Ahead of want_zexp: its place at the end of the field list is pinned.)
+    ray_bounds: str = "global"
+    box: Optional[tuple] = None
     # depth mode: each pass's expected depth on the rgb composite's own weights is one more differentiable output of
     # the train render.  The switch rides here, not on RenderCall (its field list is pinned); NeRF_Model sets it from "depth_weight"
     want_zexp: bool = False
+
+    @property
+    def aabb(self) -> bool:
+        return self.ray_bounds == "aabb"
 
     @property
     def samples_f(self):
@@ -279,33 +290,50 @@ def select_and_cap(st: RenderSettings, w_sel, wmax, n_rays, cap_perm, train: boo
     return idx, count, out_f, max_rows
 
 
-def coarse_pass(owner, model, flat, packed, rays: Rays, jitter, eps, prune: bool) -> SamplePass:
+def bounds_rows(owner, rays: Rays, jitter):
+    """(z_c [N,Sc], z_f [N,Sf] | None) of a render in "aabb" mode -- the model's own grids mapped onto every ray's part of [near, far]
+    inside the box, jitter included (ops.ray_depths; z_f in "threshold" mode only: the pdf sampler draws its own fine depths) -- and
+    None in "global" mode, where nothing is allocated.  The (lo, hi) of every ray stays with the owner in `last_ray_span`."""
+    st: RenderSettings = owner.settings
+    if not st.aabb:
+        return None
+    if not rays.d.is_cuda:
+        raise ops._lib.McnerfError(f"ray_bounds = 'aabb': the per-ray depths are a HIP kernel, got rays on {rays.d.device} (no CPU fallback)")
+    z_c, z_f, owner.last_ray_span = ops.ray_depths(rays.o, rays.d, st.box, float(owner.near), float(owner.far), jitter, owner.z_vals_c,
+                                                   None if st.pdf else owner.z_vals_f)
+    return z_c, z_f
+
+
+def coarse_pass(owner, model, flat, packed, rays: Rays, jitter, eps, prune: bool, rows=None) -> SamplePass:
     """The coarse pass: the dense [N,Sc] grid, or (`prune`, read in "voxel" mode only: a train call past the warm-up, or rendering)
-    the sigma grid's list over the default prefill."""
+    the sigma grid's list over the default prefill.  `rows` (`bounds_rows`; "aabb" mode): the depths are its coarse rows."""
     st: RenderSettings = owner.settings
     N = rays.d.shape[0]
     grid = owner.voxel_grid() if st.voxel else None
+    zgrid, jitter, z_rows = (owner.z_vals_c, jitter, None) if rows is None else (None, None, rows[0])
     idx = count = None
     if grid is not None and prune:
-        idx, count, out = ops.voxel_select(grid, st.voxel_thresh, rays.o, rays.d, owner.z_vals_c, jitter, st.sigma_default)
+        idx, count, out = ops.voxel_select(grid, st.voxel_thresh, rays.o, rays.d, zgrid, jitter, st.sigma_default, z_rows=z_rows)
     else:
         out = torch.empty(N, st.samples_c, 4, dtype=torch.float32, device=rays.d.device)
     owner.last_coarse_selection = None if idx is None else (idx, count)
-    return SamplePass(model, flat, packed, owner.z_vals_c, jitter, None, eps, out, idx, count, N * st.samples_c if idx is not None else 0)
+    return SamplePass(model, flat, packed, zgrid, jitter, z_rows, eps, out, idx, count, N * st.samples_c if idx is not None else 0)
 
 
-def fine_pass(owner, model, flat, packed, rays: Rays, jitter, w_sel, wmax, eps, u, cap_perm, train: bool) -> SamplePass:
+def fine_pass(owner, model, flat, packed, rays: Rays, jitter, w_sel, wmax, eps, u, cap_perm, train: bool, rows=None) -> SamplePass:
     """The fine pass from the coarse composite's selection weights: the selected (ray, sample) list over the default prefill (no host
-    sync), or in "pdf" mode dense rows of inverse-CDF depths drawn with `u`."""
+    sync), or in "pdf" mode dense rows of inverse-CDF depths drawn with `u`.  `rows` (`bounds_rows`; "aabb" mode): the sampler reads
+    its coarse rows, the listed pass runs on its fine rows."""
     st: RenderSettings = owner.settings
     if st.pdf:
-        z_all = ops.sample_pdf(w_sel, owner.z_vals_c, jitter, u)
+        z_all = ops.sample_pdf(w_sel, owner.z_vals_c, jitter, u) if rows is None else ops.sample_pdf(w_sel, None, None, u, z_rows=rows[0])
         out = torch.empty(*z_all.shape, 4, dtype=torch.float32, device=rays.d.device)
         p = SamplePass(model, flat, packed, None, None, z_all, eps, out)
     else:
         idx, count, out, max_rows = select_and_cap(st, w_sel, wmax, rays.d.shape[0], cap_perm, train)
-        p = SamplePass(model, flat, packed, owner.z_vals_f, jitter, None, eps, out, idx, count, max_rows)
-    owner.last_selection, owner.last_z_all = None if p.idx is None else (p.idx, p.count), p.z_rows
+        zgrid, jitter, z_rows = (owner.z_vals_f, jitter, None) if rows is None else (None, None, rows[1])
+        p = SamplePass(model, flat, packed, zgrid, jitter, z_rows, eps, out, idx, count, max_rows)
+    owner.last_selection, owner.last_z_all = None if p.idx is None else (p.idx, p.count), p.z_rows if st.pdf else None
     return p
 
 
@@ -337,7 +365,8 @@ class RenderTrainFn(torch.autograd.Function):
         with WorkspaceLease(_pool(owner), st.precision) as lease:
             saving = lease if need_grad else None
             flat_c = call.model_c.flat_params()
-            coarse = coarse_pass(owner, call.model_c, flat_c, _packed(call.model_c, flat_c, st, dev), rays, jit, call.eps_c, call.prune)
+            rows = bounds_rows(owner, rays, jit)
+            coarse = coarse_pass(owner, call.model_c, flat_c, _packed(call.model_c, flat_c, st, dev), rays, jit, call.eps_c, call.prune, rows)
             rgb_c, depth_c, _, w_sel, wmax = run_pass(coarse, st, rays, saving, None if call.only_coarse else call.eps_sel,
                                                       want_depth=call.only_coarse)
             fg_c = front_weight(coarse) if call.want_fg else None
@@ -345,13 +374,13 @@ class RenderTrainFn(torch.autograd.Function):
             dist_c = distortion(coarse, span) if call.want_dist else None
             zexp_c = expected_depth(coarse) if st.want_zexp else None
             if st.voxel:
-                ops.voxel_update(owner.voxel_grid(), st.voxel_beta, rays.o, rays.d, coarse.zgrid, jit, coarse.out,
-                                 coarse.idx, coarse.count, coarse.max_rows)
+                ops.voxel_update(owner.voxel_grid(), st.voxel_beta, rays.o, rays.d, coarse.zgrid, coarse.jitter, coarse.out,
+                                 coarse.idx, coarse.count, coarse.max_rows, z_rows=coarse.z_rows)
             passes, rgb_f, fg_f, dist_f, zexp_f = [coarse], None, None, None, None
             if not call.only_coarse:
                 flat_f = call.model_f.flat_params()
                 fine = fine_pass(owner, call.model_f, flat_f, _packed(call.model_f, flat_f, st, dev), rays, jit, w_sel, wmax,
-                                 call.eps_f, call.u, call.cap_perm, train=True)
+                                 call.eps_f, call.u, call.cap_perm, train=True, rows=rows)
                 rgb_f = run_pass(fine, st, rays, saving)[0]
                 fg_f = front_weight(fine) if call.want_fg else None
                 dist_f = distortion(fine, span) if call.want_dist else None
@@ -413,9 +442,10 @@ def render_test(owner, model_c, model_f, rays_d, rays_o, eps_c, eps_sel, eps_f, 
         prepared = (_packed(model_c, flat_c, st, dev), _packed(model_f, flat_f, st, dev), owner.emmbedding_xyz.barf_weights_on(1, dev, pad=10))
     packed_c, packed_f, barf_w = prepared
     rays = Rays(d=rays_d.contiguous(), o=rays_o.contiguous(), barf_w=barf_w)
-    coarse = coarse_pass(owner, model_c, flat_c, packed_c, rays, None, eps_c, prune=True)
+    rows = bounds_rows(owner, rays, None)
+    coarse = coarse_pass(owner, model_c, flat_c, packed_c, rays, None, eps_c, prune=True, rows=rows)
     _, _, _, w_sel, wmax = run_pass(coarse, st, rays, eps_sel=eps_sel)
-    fine = fine_pass(owner, model_f, flat_f, packed_f, rays, None, w_sel, wmax, eps_f, u, None, train=False)
+    fine = fine_pass(owner, model_f, flat_f, packed_f, rays, None, w_sel, wmax, eps_f, u, None, train=False, rows=rows)
     return run_pass(fine, st, rays, want_depth=True)[:3]                    # rgb, depth, opacity
 
 

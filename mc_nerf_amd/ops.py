@@ -12,7 +12,7 @@ from typing import Optional, Tuple
 
 import torch
 
-from . import _ext, _geo, _lib, _reg
+from . import _box, _ext, _geo, _lib, _reg
 
 Tensor = torch.Tensor
 
@@ -723,22 +723,52 @@ def select_fine(w_sel: Tensor, wmax: Tensor, thresh: float, scale: int, sigma_de
     return idx, count, out_f
 
 
-def sample_pdf(w_sel: Tensor, zgrid: Tensor, jitter: Optional[Tensor], u: Tensor, out: Optional[Tensor] = None) -> Tensor:
+def sample_pdf(w_sel: Tensor, zgrid: Optional[Tensor], jitter: Optional[Tensor], u: Tensor, out: Optional[Tensor] = None, *,
+               z_rows: Optional[Tensor] = None) -> Tensor:
     """Inverse-CDF hierarchical sampling (include/mcnerf.h: mcnerf_sample_pdf): coarse selection weights w_sel [N,Sc], the coarse
     grid zgrid [Sc], jitter [N] | None and uniform draws u [N,I] -> z_all [N,Sc+I] = sort(coarse depths ++ importance samples).
     Not differentiable (z_all is a constant of the fine pass, as in vanilla NeRF).
-    `out`: the caller's own z_all (fp32, contiguous, [N,Sc+I], on w_sel's device), e.g. rows of a larger buffer; it is returned."""
+    `out`: the caller's own z_all (fp32, contiguous, [N,Sc+I], on w_sel's device), e.g. rows of a larger buffer; it is returned.
+    `z_rows` [N,Sc]: the coarse depths of every ray (zgrid and jitter None); the bounds library's entry point
+    (include/mcnerf_box.h: mcnerf_box_sample_pdf_rows), the same device code."""
     N, Sc = w_sel.shape
-    if u.dim() != 2 or u.shape[0] != N or zgrid.numel() != Sc or (jitter is not None and jitter.numel() != N):
+    if z_rows is not None:
+        if zgrid is not None or jitter is not None or tuple(z_rows.shape) != (N, Sc):
+            raise _lib.McnerfError(f"sample_pdf: z_rows must be [N = {N}, Sc = {Sc}] with zgrid and jitter None, got {tuple(z_rows.shape)}")
+    elif zgrid.numel() != Sc or (jitter is not None and jitter.numel() != N):
         raise _lib.McnerfError(f"sample_pdf: w_sel [N,Sc] {tuple(w_sel.shape)}, zgrid [Sc] {tuple(zgrid.shape)}, u [N,I] {tuple(u.shape)}")
+    if u.dim() != 2 or u.shape[0] != N:
+        raise _lib.McnerfError(f"sample_pdf: w_sel [N,Sc] {tuple(w_sel.shape)}, u [N,I] {tuple(u.shape)}")
     I = u.shape[1]
     if out is None:
         out = torch.empty(N, Sc + I, dtype=torch.float32, device=w_sel.device)
     elif tuple(out.shape) != (N, Sc + I) or out.dtype != torch.float32 or out.device != w_sel.device or not out.is_contiguous():
         raise _lib.McnerfError(f"sample_pdf: out must be a contiguous fp32 [N = {N}, Sc + I = {Sc + I}] tensor on {w_sel.device}, got "
                                f"{out.dtype} {tuple(out.shape)} on {out.device}{'' if out.is_contiguous() else ', not contiguous'}")
-    _lib.call("mcnerf_sample_pdf", w_sel, zgrid, jitter, u, N, Sc, I, out, _stream())
+    if z_rows is not None:
+        _box.call("mcnerf_box_sample_pdf_rows", w_sel, z_rows, u, N, Sc, I, out, _stream())
+    else:
+        _lib.call("mcnerf_sample_pdf", w_sel, zgrid, jitter, u, N, Sc, I, out, _stream())
     return out
+
+
+# --------------------------------------------------------------------------- per-ray sample bounds (include/mcnerf_box.h)
+def ray_depths(rays_o: Tensor, rays_d: Tensor, box, near: float, far: float, jitter: Optional[Tensor], zgrid_c: Tensor,
+               zgrid_f: Optional[Tensor] = None, want_span: bool = True):
+    """Per-ray depth rows from the scene box (mcnerf_box_ray_depths; the rule: include/mcnerf_box.h): rays [N,3], box = (xmin, ymin,
+    zmin, xmax, ymax, zmax), jitter [N] | None, the grids zgrid_c [Sc] and zgrid_f [Sf] | None -> z_c [N,Sc], z_f [N,Sf] | None,
+    span [N,2] = (lo, hi) | None.  One launch, no host synchronisation; constants of the backward."""
+    N, dev = rays_d.shape[0], rays_d.device
+    box = [float(v) for v in box]
+    if len(box) != 6 or tuple(rays_o.shape) != (N, 3) or tuple(rays_d.shape) != (N, 3) or (jitter is not None and jitter.numel() != N):
+        raise _lib.McnerfError(f"ray_depths: rays_o / rays_d [N,3] {tuple(rays_o.shape)} / {tuple(rays_d.shape)}, a box of six numbers, jitter [N]")
+    Sc, Sf = zgrid_c.numel(), 0 if zgrid_f is None else zgrid_f.numel()
+    z_c = torch.empty(N, Sc, dtype=torch.float32, device=dev)
+    z_f = torch.empty(N, Sf, dtype=torch.float32, device=dev) if Sf else None
+    span = torch.empty(N, 2, dtype=torch.float32, device=dev) if want_span else None
+    _box.call("mcnerf_box_ray_depths", rays_o, rays_d, N, *box, float(near), float(far), jitter, zgrid_c, Sc, zgrid_f if Sf else None, Sf,
+              z_c, z_f, span, _stream())
+    return z_c, z_f, span
 
 
 # --------------------------------------------------------------------------- voxel sigma cache (include/mcnerf.h: mcnerf_voxel_*)
@@ -772,29 +802,47 @@ class VoxelGrid:
         return self.G, self.bmin, self.s
 
 
-def voxel_select(grid: VoxelGrid, thresh: float, rays_o: Tensor, rays_d: Tensor, zgrid: Tensor, jitter: Optional[Tensor],
-                 sigma_default: float, prefill: bool = True, idx: Optional[Tensor] = None):
+def _voxel_rows(name: str, zgrid, jitter, z_rows: Tensor, N: int):
+    if zgrid is not None or jitter is not None or z_rows.dim() != 2 or z_rows.shape[0] != N:
+        raise _lib.McnerfError(f"{name}: z_rows must be [N = {N}, Sc] with zgrid and jitter None, got {tuple(z_rows.shape)}")
+    return z_rows.shape[1]
+
+
+def voxel_select(grid: VoxelGrid, thresh: float, rays_o: Tensor, rays_d: Tensor, zgrid: Optional[Tensor], jitter: Optional[Tensor],
+                 sigma_default: float, prefill: bool = True, idx: Optional[Tensor] = None, *, z_rows: Optional[Tensor] = None):
     """-> idx [N*Sc,2] int32 (first *count rows valid, torch.nonzero order), count [1] int32, out_c [N,Sc,4] | None: the (ray, sample)
     pairs whose cell holds a sigma > thresh, and the (sigma_default, 1, 1, 1) prefill of the coarse pass.  No host synchronisation.
-    `idx`: the caller's own list buffer (rows beyond *count are left as they are)."""
-    N, Sc = rays_d.shape[0], zgrid.numel()
+    `idx`: the caller's own list buffer (rows beyond *count are left as they are).
+    `z_rows` [N,Sc]: the depths of every ray (zgrid and jitter None); the bounds library's entry point (include/mcnerf_box.h)."""
+    N = rays_d.shape[0]
+    Sc = zgrid.numel() if z_rows is None else _voxel_rows("voxel_select", zgrid, jitter, z_rows, N)
     if idx is not None and idx.numel() < N * Sc * 2:
         raise _lib.McnerfError(f"voxel_select: idx must hold N * Sc = {N * Sc} pairs, got {tuple(idx.shape)}")
     idx, count, rc, ro, out_c = _list_buffers(N, Sc, prefill, idx, rays_d.device)
-    _lib.call("mcnerf_voxel_select", grid.vox, *grid.geom, float(thresh), rays_o, rays_d, zgrid, jitter, N, Sc,
-              float(sigma_default), rc, ro, idx, count, out_c, _stream())
+    if z_rows is not None:
+        _box.call("mcnerf_box_voxel_select_rows", grid.vox, *grid.geom, float(thresh), rays_o, rays_d, z_rows, N, Sc,
+                  float(sigma_default), rc, ro, idx, count, out_c, _stream())
+    else:
+        _lib.call("mcnerf_voxel_select", grid.vox, *grid.geom, float(thresh), rays_o, rays_d, zgrid, jitter, N, Sc,
+                  float(sigma_default), rc, ro, idx, count, out_c, _stream())
     return idx, count, out_c
 
 
-def voxel_update(grid: VoxelGrid, beta: float, rays_o: Tensor, rays_d: Tensor, zgrid: Tensor, jitter: Optional[Tensor], sig_rgb: Tensor,
-                 idx: Optional[Tensor] = None, count: Optional[Tensor] = None, max_rows: int = 0) -> None:
+def voxel_update(grid: VoxelGrid, beta: float, rays_o: Tensor, rays_d: Tensor, zgrid: Optional[Tensor], jitter: Optional[Tensor], sig_rgb: Tensor,
+                 idx: Optional[Tensor] = None, count: Optional[Tensor] = None, max_rows: int = 0, *, z_rows: Optional[Tensor] = None) -> None:
     """The update rule on the listed (ray, sample) pairs (idx None: all N * Sc) with sigma = sig_rgb[n, j, 0]: per touched cell
-    V <- (1 - beta) V + beta max(sigma), deterministic in the order of arrival; grid.scratch is all zero again afterwards."""
-    N, Sc = rays_d.shape[0], zgrid.numel()
+    V <- (1 - beta) V + beta max(sigma), deterministic in the order of arrival; grid.scratch is all zero again afterwards.
+    `z_rows` [N,Sc]: the depths of every ray (zgrid and jitter None); the bounds library's entry point (include/mcnerf_box.h)."""
+    N = rays_d.shape[0]
+    Sc = zgrid.numel() if z_rows is None else _voxel_rows("voxel_update", zgrid, jitter, z_rows, N)
     if sig_rgb.numel() != N * Sc * 4 or (jitter is not None and jitter.numel() != N):
         raise _lib.McnerfError(f"voxel_update: sig_rgb must be [N = {N}, Sc = {Sc}, 4], got {tuple(sig_rgb.shape)}")
-    _lib.call("mcnerf_voxel_update", grid.vox, grid.scratch, *grid.geom, *voxel_blend(beta), rays_o, rays_d,
-              zgrid, jitter, N, Sc, idx, count, int(max_rows), sig_rgb, _stream())
+    if z_rows is not None:
+        _box.call("mcnerf_box_voxel_update_rows", grid.vox, grid.scratch, *grid.geom, *voxel_blend(beta), rays_o, rays_d,
+                  z_rows, N, Sc, idx, count, int(max_rows), sig_rgb, _stream())
+    else:
+        _lib.call("mcnerf_voxel_update", grid.vox, grid.scratch, *grid.geom, *voxel_blend(beta), rays_o, rays_d,
+                  zgrid, jitter, N, Sc, idx, count, int(max_rows), sig_rgb, _stream())
 
 
 def voxel_query(grid: VoxelGrid, xyz: Tensor) -> Tensor:
