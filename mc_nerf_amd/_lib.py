@@ -1,4 +1,5 @@
-"""ctypes binding of libmcnerf.so, DERIVED from include/mcnerf.h, the one statement of the C ABI.
+"""ctypes binding of libmcnerf.so, DERIVED from include/mcnerf.h, the one statement of the C ABI, and the `Binding` class that the
+libraries beside it (`_ext`, `_reg`, `_geo`, `_box`) are bound with as well.
 
 The header is parsed once at import (`parse_header`): every prototype gives an entry point's ctypes signature (`SIGNATURES`), its
 parameter names and, per pointer, the dtype a tensor handed to it must have (`PARAMS`); every decimal `#define MCNERF_*` gives a
@@ -17,8 +18,6 @@ from ctypes import c_char_p, c_float, c_int, c_longlong, c_void_p
 import torch
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
-# MCNERF_LIB selects another build of the same ABI, e.g. the parent commit's
-LIB_PATH = os.environ.get("MCNERF_LIB") or os.path.join(_HERE, "libmcnerf.so")
 HOST = "host table"      # element class of a pointer into HOST memory: long long*, T* const*, and what the header marks MCNERF_HOST
 BY_VALUE = {"int": c_int, "long long": c_longlong, "float": c_float}
 # element type of a pointer -> dtype of the device tensor it takes (the unsigned words travel in signed tensors, void* is bytes)
@@ -62,12 +61,6 @@ def parse_header(text):
     return functions, defines
 
 
-with open(os.path.join(_HERE, "csrc", "..", "..", "include", "mcnerf.h")) as _f:      # (the path csrc/api.hip includes it by)
-    PARAMS, DEFINES = parse_header(_f.read())
-SIGNATURES = {name: (res, [p[2] for p in params]) for name, (res, params) in PARAMS.items()}      # name -> (restype, argtypes)
-ABI_VERSION = DEFINES["MCNERF_ABI_VERSION"]
-
-
 def _pointer(fn, pname, ctype, want):
     """Converter of a tensor at one pointer position -> its checked device address."""
     def conv(a):
@@ -83,37 +76,60 @@ def _pointer(fn, pname, ctype, want):
     return conv
 
 
-# per entry point one converter per position (None: by value); whatever is not a tensor goes to ctypes as it is: None (NULL), raw
-# addresses (data_ptr(), the stream), ctypes arrays and casts
-_CONVERTERS = {name: tuple(cls and _pointer(name, pname, ctype, cls) for pname, ctype, _, cls in params) for name, (_, params) in PARAMS.items()}
-_lib = None
+class Binding:
+    """One library and the header it is derived from: include/<header> is parsed when the binding is made, mc_nerf_amd/<soname> (or
+    the build of the same ABI that the environment variable `env` names, e.g. the parent commit's) is opened by the first `lib()` /
+    `call()` only.  `prefix` is that of the library's `<prefix>_abi_version` / `<prefix>_last_error` pair and, in capitals, of its
+    `<PREFIX>_ABI_VERSION`; `noun` is what the "not found" text calls the library."""
+
+    def __init__(self, header, soname, env, prefix, noun):
+        self.soname, self.prefix, self.noun = soname, prefix, noun
+        self.LIB_PATH = os.environ.get(env) or os.path.join(_HERE, soname)
+        with open(os.path.join(_HERE, "..", "include", header)) as f:
+            self.PARAMS, self.DEFINES = parse_header(f.read())
+        self.SIGNATURES = {name: (res, [p[2] for p in params]) for name, (res, params) in self.PARAMS.items()}      # name -> (restype, argtypes)
+        self.ABI_VERSION = self.DEFINES[prefix.upper() + "_ABI_VERSION"]
+        # per entry point one converter per position (None: by value); whatever is not a tensor goes to ctypes as it is: None (NULL),
+        # raw addresses (data_ptr(), the stream), ctypes arrays and casts
+        self._converters = {name: tuple(cls and _pointer(name, pname, ctype, cls) for pname, ctype, _, cls in params)
+                            for name, (_, params) in self.PARAMS.items()}
+        self._lib = None
+
+    def lib(self):
+        """Returns the loaded library; raises McnerfError if it is missing (``python -m mc_nerf_amd.build`` builds every library)."""
+        if self._lib is not None:
+            return self._lib
+        if not os.path.exists(self.LIB_PATH):
+            raise McnerfError(f"{self.LIB_PATH} not found: the HIP {self.noun} is required (python -m mc_nerf_amd.build); there is no CPU fallback")
+        try:
+            l = ctypes.CDLL(self.LIB_PATH)
+        except OSError as e:  # pragma: no cover
+            raise McnerfError(f"cannot load {self.LIB_PATH}: {e}") from e
+        for name, (res, args) in self.SIGNATURES.items():
+            if not hasattr(l, name):
+                raise McnerfError(f"{self.LIB_PATH} does not export {name}")
+            getattr(l, name).restype, getattr(l, name).argtypes = res, args
+        if getattr(l, self.prefix + "_abi_version")() != self.ABI_VERSION:
+            raise McnerfError(f"{self.soname} ABI version mismatch; rebuild")
+        self._lib = l
+        return l
+
+    def loaded(self) -> bool:
+        return self._lib is not None
+
+    def call(self, name, *args):
+        """Calls a status-returning entry point and raises with the library's message on failure.  Tensor arguments are first checked
+        against the header: a host tensor is refused before the library is opened."""
+        args = [c(a) if c and isinstance(a, torch.Tensor) else a for c, a in zip(self._converters[name], args, strict=True)]
+        l = self.lib()
+        rc = getattr(l, name)(*args)
+        if rc != 0:
+            raise McnerfError(f"{name} failed ({rc}): {getattr(l, self.prefix + '_last_error')().decode()}")
 
 
-def lib():
-    """Returns the loaded library; raises McnerfError if it is missing (build it with ``python -m mc_nerf_amd.build``)."""
-    global _lib
-    if _lib is not None:
-        return _lib
-    if not os.path.exists(LIB_PATH):
-        raise McnerfError(f"{LIB_PATH} not found: the HIP extension is required (python -m mc_nerf_amd.build); there is no CPU fallback")
-    try:
-        l = ctypes.CDLL(LIB_PATH)
-    except OSError as e:  # pragma: no cover
-        raise McnerfError(f"cannot load {LIB_PATH}: {e}") from e
-    for name, (res, args) in SIGNATURES.items():
-        if not hasattr(l, name):
-            raise McnerfError(f"{LIB_PATH} does not export {name}")
-        getattr(l, name).restype, getattr(l, name).argtypes = res, args
-    if l.mcnerf_abi_version() != ABI_VERSION:
-        raise McnerfError("libmcnerf.so ABI version mismatch; rebuild")
-    _lib = l
-    return l
+# libmcnerf.so, the core library (include/mcnerf.h).  There is no fallback: if it is missing or does not load, `lib()` raises
+_CORE = Binding("mcnerf.h", "libmcnerf.so", "MCNERF_LIB", "mcnerf", "extension")
+LIB_PATH, PARAMS, DEFINES, SIGNATURES, ABI_VERSION = _CORE.LIB_PATH, _CORE.PARAMS, _CORE.DEFINES, _CORE.SIGNATURES, _CORE.ABI_VERSION
+lib, loaded, call = _CORE.lib, _CORE.loaded, _CORE.call
 
 
-def call(name, *args):
-    """Calls a status-returning entry point (tensor arguments are first checked against the header) and raises with the library's message on failure."""
-    args = [c(a) if c and isinstance(a, torch.Tensor) else a for c, a in zip(_CONVERTERS[name], args, strict=True)]
-    l = lib()
-    rc = getattr(l, name)(*args)
-    if rc != 0:
-        raise McnerfError(f"{name} failed ({rc}): {l.mcnerf_last_error().decode()}")

@@ -1,6 +1,4 @@
-"""Builds mc_nerf_amd/libmcnerf.so and, beside it, the extension library mc_nerf_amd/libmcnext.so, the regulariser library
-mc_nerf_amd/libmcnreg.so, the geometry library mc_nerf_amd/libmcngeo.so and the bounds library mc_nerf_amd/libmcnbox.so (hipcc,
-gfx950 only) in-tree.
+"""Builds mc_nerf_amd/libmcnerf.so and, beside it, the libraries of the opt-in features (LIBRARIES below; hipcc, gfx950 only) in-tree.
 
     python -m mc_nerf_amd.build [--force]
 
@@ -13,36 +11,36 @@ from concurrent.futures import ThreadPoolExecutor
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
-OUT = os.path.join(HERE, "libmcnerf.so")
-SOURCES = ["api.hip", "pack.hip", "mlp_fwd.hip", "mlp_bwd.hip", "mlp_dw.hip", "pack16.hip", "mlp16_fwd.hip", "mlp16_bwd.hip", "mlp16_dw.hip", "mlp_x3_fwd.hip", "mlp_x3_bwd.hip", "mlp_x3_dw.hip", "composite.hip", "sample_pdf.hip", "select.hip", "rays.hip", "voxel.hip", "optim.hip", "optim_rows.hip", "camera.hip", "color_calib.hip", "errmap.hip", "lens.hip"]
-HEADERS = ["mcnerf_common.h", "mcnerf_kernels.h", "mcnerf_wave.h", "mcnerf_composite.h", "mcnerf_16.h", "mcnerf_x3.h", "mcnerf_launch.h", "mcnerf_voxel.h",
-           "mcnerf_sample_pdf.h", "mcnerf_multicam.h", "mcnerf_colorcal.h", "mcnerf_errmap.h", "mcnerf_maxkey.h", "mcnerf_compact.h", "mcnerf_hash.h", "mcnerf_rays.h", "mcnerf_lens.h", "mcnerf_optim_rows.h", os.path.join("..", "..", "include", "mcnerf.h")]
-# The extension library (include/mcnerf_ext.h): opt-in features whose entry points are not part of the core ABI.  Its
-# objects share the object directory; nothing of it is linked into libmcnerf.so and it links none of the core's objects.
-EXT_OUT = os.path.join(HERE, "libmcnext.so")
-EXT_SOURCES = ["ext_api.hip", "mask.hip"]
-EXT_HEADERS = ["mcnerf_common.h", "mcnerf_wave.h", "mcnerf_composite.h", "mcnerf_multicam.h", "mcnerf_mask.h", os.path.join("..", "..", "include", "mcnerf.h"),
-               os.path.join("..", "..", "include", "mcnerf_ext.h")]
-# The regulariser library (include/mcnerf_reg.h): the extension library's ABI is pinned too, so the distortion loss has
-# a third library, built the same way.  None of its objects is linked into the other two and it links none of theirs.
-REG_OUT = os.path.join(HERE, "libmcnreg.so")
-REG_SOURCES = ["reg_api.hip", "distortion.hip"]
-REG_HEADERS = ["mcnerf_common.h", "mcnerf_wave.h", "mcnerf_composite.h", "mcnerf_distortion.h", os.path.join("..", "..", "include", "mcnerf_reg.h")]
-# The geometry library (include/mcnerf_geo.h): the regulariser library's ABI is pinned as well, so depth supervision has
-# a fourth library, built the same way.  None of its objects is linked into the other three and it links none of theirs.
-GEO_OUT = os.path.join(HERE, "libmcngeo.so")
-GEO_SOURCES = ["geo_api.hip", "depth.hip"]
-GEO_HEADERS = ["mcnerf_common.h", "mcnerf_wave.h", "mcnerf_composite.h", "mcnerf_multicam.h", "mcnerf_depth.h", os.path.join("..", "..", "include", "mcnerf.h"),
-               os.path.join("..", "..", "include", "mcnerf_geo.h")]
-# The bounds library (include/mcnerf_box.h): the geometry library's ABI is pinned too, so per-ray sample bounds have a
-# fifth library, built the same way.  The sampler's device code reaches it through mcnerf_sample_pdf.h and the voxel kernels by
-# ray_bounds.hip including voxel.hip (listed with the headers: a change of it recompiles ray_bounds.hip); none of its objects is
-# linked into the other four and it links none of theirs.
-BOX_OUT = os.path.join(HERE, "libmcnbox.so")
-BOX_SOURCES = ["box_api.hip", "ray_bounds.hip"]
-BOX_HEADERS = ["mcnerf_common.h", "mcnerf_kernels.h", "mcnerf_wave.h", "mcnerf_voxel.h", "voxel.hip", "mcnerf_compact.h", "mcnerf_maxkey.h",
-               "mcnerf_sample_pdf.h", "mcnerf_ray_bounds.h", os.path.join("..", "..", "include", "mcnerf.h"),
-               os.path.join("..", "..", "include", "mcnerf_box.h")]
+_INC = os.path.join("..", "..", "include")
+# One entry per library, in build order: prefix of its module attributes -> (.so, sources, what a change of recompiles them).  The
+# libraries share the object directory; none links an object of another.  Every list names mcnerf_api.h, the preamble of the
+# library's *_api.hip, and mcnerf_multicam.h, which that includes.  A new library is one more entry (the recipe).
+LIBRARIES = {
+    # per-ray sample bounds (include/mcnerf_box.h).  The sampler's device code reaches it through mcnerf_sample_pdf.h and
+    # the voxel kernels by ray_bounds.hip including voxel.hip (listed with the headers: a change of it recompiles ray_bounds.hip)
+    "BOX_": ("libmcnbox.so", ["box_api.hip", "ray_bounds.hip"],
+             ["mcnerf_api.h", "mcnerf_common.h", "mcnerf_kernels.h", "mcnerf_wave.h", "mcnerf_voxel.h", "voxel.hip", "mcnerf_compact.h", "mcnerf_maxkey.h",
+              "mcnerf_sample_pdf.h", "mcnerf_multicam.h", "mcnerf_ray_bounds.h", os.path.join(_INC, "mcnerf.h"), os.path.join(_INC, "mcnerf_box.h")]),
+    # depth supervision (include/mcnerf_geo.h)
+    "GEO_": ("libmcngeo.so", ["geo_api.hip", "depth.hip"],
+             ["mcnerf_api.h", "mcnerf_common.h", "mcnerf_wave.h", "mcnerf_composite.h", "mcnerf_multicam.h", "mcnerf_depth.h", os.path.join(_INC, "mcnerf.h"),
+              os.path.join(_INC, "mcnerf_geo.h")]),
+    # alpha-mask supervision (include/mcnerf_ext.h): the first library beside the core, whose ABI is frozen
+    "EXT_": ("libmcnext.so", ["ext_api.hip", "mask.hip"],
+             ["mcnerf_api.h", "mcnerf_common.h", "mcnerf_wave.h", "mcnerf_composite.h", "mcnerf_multicam.h", "mcnerf_mask.h", os.path.join(_INC, "mcnerf.h"),
+              os.path.join(_INC, "mcnerf_ext.h")]),
+    # the distortion loss (include/mcnerf_reg.h)
+    "REG_": ("libmcnreg.so", ["reg_api.hip", "distortion.hip"],
+             ["mcnerf_api.h", "mcnerf_common.h", "mcnerf_wave.h", "mcnerf_composite.h", "mcnerf_multicam.h", "mcnerf_distortion.h", os.path.join(_INC, "mcnerf_reg.h")]),
+    # the core library (include/mcnerf.h), last: build() returns its path
+    "": ("libmcnerf.so",
+         ["api.hip", "pack.hip", "mlp_fwd.hip", "mlp_bwd.hip", "mlp_dw.hip", "pack16.hip", "mlp16_fwd.hip", "mlp16_bwd.hip", "mlp16_dw.hip", "mlp_x3_fwd.hip", "mlp_x3_bwd.hip", "mlp_x3_dw.hip", "composite.hip", "sample_pdf.hip", "select.hip", "rays.hip", "voxel.hip", "optim.hip", "optim_rows.hip", "camera.hip", "color_calib.hip", "errmap.hip", "lens.hip"],
+         ["mcnerf_api.h", "mcnerf_common.h", "mcnerf_kernels.h", "mcnerf_wave.h", "mcnerf_composite.h", "mcnerf_16.h", "mcnerf_x3.h", "mcnerf_launch.h", "mcnerf_voxel.h",
+          "mcnerf_sample_pdf.h", "mcnerf_multicam.h", "mcnerf_colorcal.h", "mcnerf_errmap.h", "mcnerf_maxkey.h", "mcnerf_compact.h", "mcnerf_hash.h", "mcnerf_rays.h", "mcnerf_lens.h", "mcnerf_optim_rows.h", os.path.join(_INC, "mcnerf.h")]),
+}
+# OUT, SOURCES, HEADERS of the core library and EXT_OUT, EXT_SOURCES, EXT_HEADERS, REG_*, GEO_*, BOX_* of the others
+for _prefix, (_so, _sources, _headers) in LIBRARIES.items():
+    globals().update({_prefix + "OUT": os.path.join(HERE, _so), _prefix + "SOURCES": _sources, _prefix + "HEADERS": _headers})
 # the f16x3 chains: a layer body is ~400 MFMAs with its epilogue slices, fully unrolled (beyond hipcc's default pragma-unroll budget);
 # their 256-wide instantiations run one wave per SIMD with 512 registers, where hipcc would otherwise put the MFMA
 # accumulators in AGPRs (every epilogue read then costs a v_accvgpr_read behind a full MFMA drain)
@@ -58,12 +56,10 @@ def _newer(a, b):
 
 
 def build(force=False, verbose=True):
-    """All five libraries; returns the core library's path."""
-    _build_library(BOX_SOURCES, BOX_HEADERS, BOX_OUT, force, verbose)
-    _build_library(GEO_SOURCES, GEO_HEADERS, GEO_OUT, force, verbose)
-    _build_library(EXT_SOURCES, EXT_HEADERS, EXT_OUT, force, verbose)
-    _build_library(REG_SOURCES, REG_HEADERS, REG_OUT, force, verbose)
-    return _build_library(SOURCES, HEADERS, OUT, force, verbose)
+    """Every library of LIBRARIES, in its order; returns the core library's path."""
+    for so, sources, headers in LIBRARIES.values():
+        out = _build_library(sources, headers, os.path.join(HERE, so), force, verbose)
+    return out
 
 
 def _build_library(sources, headers, out, force, verbose):

@@ -10,7 +10,7 @@
 #include "mcnerf_optim_rows.h"
 #include "mcnerf_16.h"
 #include "mcnerf_x3.h"
-#include <stdio.h>
+#include "mcnerf_api.h"
 #include <string.h>
 
 // the limits the public header states are the kernels' own
@@ -19,17 +19,6 @@ static_assert(MCNERF_MULTICAM_MAXSEG == MCN_MULTICAM_MAXSEG, "include/mcnerf.h: 
 static_assert(MCNERF_PDF_MAX_SAMPLES == MCN_PDF_MAX_SAMPLES, "include/mcnerf.h: MCNERF_PDF_MAX_SAMPLES");
 static_assert(MCNERF_TRAIN_LOSS_OUT == 4 + MCN_LOSS_BLOCKS, "include/mcnerf.h: MCNERF_TRAIN_LOSS_OUT");
 
-static thread_local char g_err[512] = "";
-
-static int fail(const char* where, const char* what) {
-    snprintf(g_err, sizeof(g_err), "%s: %s", where, what);
-    return -1;
-}
-static int check(const char* where, hipError_t e) {
-    if (e == hipSuccess) return 0;
-    snprintf(g_err, sizeof(g_err), "%s: HIP error %d (%s)", where, (int)e, hipGetErrorString(e));
-    return -2;
-}
 static bool net_ok(int depth, int width, int skip) {
     if (!(depth >= 1 && depth <= MCN_MAXD && (width == 32 || width == 64 || width == 128 || width == 256))) return false;
     if (skip < -1) return false;
@@ -41,9 +30,6 @@ static bool net_ok(int depth, int width, int skip) {
 static bool net16_ok(int depth, int width, int skip) {
     return net_ok(depth, width, skip) && mcn_single_skip(mcn_skip_mask(depth, skip)) != -2 && mcn_topo_deg(skip) <= 2;
 }
-// the depth layout of the sample-evaluating entry points: one grid (0) or one row per ray (S)
-static bool z_ok(int z_stride, int S) { return z_stride == 0 || z_stride == S; }
-#define REQ(cond, name) do { if (!(cond)) return fail(name, "invalid argument: " #cond); } while (0)
 // floats between the layers of the exact-fp32 workspaces
 static inline size_t act_stride(long long capacity, int width) { return (size_t)capacity * width; }
 
@@ -110,25 +96,6 @@ int mcnerf_raygen_bwd(const float* pose, const float* kinv, const int64_t* pix, 
     REQ(pose && kinv && pix && d_rays_d && d_rays_o && d_pose && d_kinv && n >= 0 && W > 0, "mcnerf_raygen_bwd");
     McnRaygenBwdArgs a = {pose, kinv, (const long long*)pix, n, W, d_rays_d, d_rays_o, d_pose, d_kinv};
     return check("mcnerf_raygen_bwd", mcn_launch_raygen_bwd(a, (hipStream_t)stream));
-}
-
-// The host-side segment table of a multi-camera ray batch, validated and copied into the by-value kernel argument.  Everything is
-// checked before any HIP call (a bad table is refused on a machine without a GPU too).  max_seg: the longest segment allowed
-// (H * W when the pixels are drawn without replacement, n otherwise).
-static int fill_segments(const char* name, McnSegTable& t, const int32_t* seg_cam, const int32_t* seg_start, int K, int C, int n, long long max_seg) {
-    REQ(seg_cam && seg_start, name);
-    REQ(K >= 1 && K <= MCN_MULTICAM_MAXSEG, name);
-    REQ(C >= 1 && n >= 0 && n <= (1 << 29), name);
-    REQ(seg_start[0] == 0 && seg_start[K] == n, name);
-    t.K = K;
-    for (int k = 0; k < K; ++k) {
-        REQ(seg_cam[k] >= 0 && seg_cam[k] < C, name);
-        REQ(seg_start[k + 1] >= seg_start[k], name);
-        REQ((long long)seg_start[k + 1] - seg_start[k] <= max_seg, name);
-        t.cam[k] = seg_cam[k]; t.start[k] = seg_start[k];
-    }
-    t.start[K] = n;
-    return 0;
 }
 
 // The ray-batch pair (rays.hip) and the pair with per-camera radial lens distortion (lens.hip) behind one binding per direction:

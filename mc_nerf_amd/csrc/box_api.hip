@@ -3,26 +3,15 @@
 // stream, nothing here synchronises or allocates, and every refusal comes ahead of any device work.
 #include "../../include/mcnerf_box.h"
 #include "mcnerf_ray_bounds.h"
-#include <stdio.h>
+#include "mcnerf_api.h"
 
 // the limits the public headers state are the kernels' own
 static_assert(MCNERF_PDF_MAX_SAMPLES == MCN_PDF_MAX_SAMPLES, "include/mcnerf.h: MCNERF_PDF_MAX_SAMPLES");
 
-static thread_local char g_err[512] = "";
-
-static int fail(const char* where, const char* what) {
-    snprintf(g_err, sizeof(g_err), "%s: %s", where, what);
-    return -1;
-}
-static int check(const char* where, hipError_t e) {
-    if (e == hipSuccess) return 0;
-    snprintf(g_err, sizeof(g_err), "%s: HIP error %d (%s)", where, (int)e, hipGetErrorString(e));
-    return -2;
-}
-static bool finite_f(float v) { return v == v && v >= -3.4028235e38f && v <= 3.4028235e38f; }
+// not mcnerf_api.h's finite_f, which stops at 3.0e38f: this library takes every finite float up to FLT_MAX, and what it refuses is as frozen as its header
+static bool box_finite(float v) { return v == v && v >= -3.4028235e38f && v <= 3.4028235e38f; }
 // the voxel grid's geometry, as api.hip: 2 <= G <= 1024 cells per axis, a finite positive cells-per-unit scale
 static bool vox_ok(int G, float bmin, float s) { return G >= 2 && G <= MCNERF_VOXEL_MAX_G && bmin == bmin && s > 0.f && s <= 3.0e38f; }
-#define REQ(cond, name) do { if (!(cond)) return fail(name, "invalid argument: " #cond); } while (0)
 
 extern "C" {
 
@@ -35,9 +24,9 @@ int mcnerf_box_ray_depths(const float* rays_o, const float* rays_d, int N,
                           float* z_c, float* z_f, float* span, void* stream) {
     REQ(N >= 0 && Sc >= 1 && Sf >= 0, "mcnerf_box_ray_depths");
     REQ((long long)N * (Sc > Sf ? Sc : Sf) < (1ll << 31), "mcnerf_box_ray_depths");
-    REQ(finite_f(xmin) && finite_f(ymin) && finite_f(zmin) && finite_f(xmax) && finite_f(ymax) && finite_f(zmax), "mcnerf_box_ray_depths");
+    REQ(box_finite(xmin) && box_finite(ymin) && box_finite(zmin) && box_finite(xmax) && box_finite(ymax) && box_finite(zmax), "mcnerf_box_ray_depths");
     REQ(xmin < xmax && ymin < ymax && zmin < zmax, "mcnerf_box_ray_depths");
-    REQ(finite_f(z_near) && finite_f(z_far) && z_far > z_near, "mcnerf_box_ray_depths");
+    REQ(box_finite(z_near) && box_finite(z_far) && z_far > z_near, "mcnerf_box_ray_depths");
     if (N == 0) return 0;                 // no rays: nothing is read or written (the empty arrays of a caller may be null pointers)
     REQ(rays_o && rays_d && zgrid_c && z_c, "mcnerf_box_ray_depths");
     REQ((zgrid_f != nullptr) == (Sf > 0) && (z_f != nullptr) == (Sf > 0), "mcnerf_box_ray_depths");

@@ -4,42 +4,12 @@
 #include "../../include/mcnerf_ext.h"
 #include "mcnerf_mask.h"
 #include "mcnerf_composite.h"
-#include <stdio.h>
+#include "mcnerf_api.h"
 
 // the limits the public headers state are the kernels' own
 static_assert(MCNERF_MULTICAM_MAXSEG == MCN_MULTICAM_MAXSEG, "include/mcnerf.h: MCNERF_MULTICAM_MAXSEG");
 static_assert(MCNERF_EXT_MASK_LOSS_OUT == 4 + MCN_MASK_LOSS_BLOCKS, "include/mcnerf_ext.h: MCNERF_EXT_MASK_LOSS_OUT");
 static_assert(MCNERF_EXT_BWD_MAX_SAMPLES == MCN_COMPOSITE_BWD_MAX_SAMPLES, "include/mcnerf_ext.h: MCNERF_EXT_BWD_MAX_SAMPLES");
-
-static thread_local char g_err[512] = "";
-
-static int fail(const char* where, const char* what) {
-    snprintf(g_err, sizeof(g_err), "%s: %s", where, what);
-    return -1;
-}
-static int check(const char* where, hipError_t e) {
-    if (e == hipSuccess) return 0;
-    snprintf(g_err, sizeof(g_err), "%s: HIP error %d (%s)", where, (int)e, hipGetErrorString(e));
-    return -2;
-}
-static bool z_ok(int z_stride, int S) { return z_stride == 0 || z_stride == S; }
-#define REQ(cond, name) do { if (!(cond)) return fail(name, "invalid argument: " #cond); } while (0)
-
-// The segment table's refusals of api.hip, before any HIP call, and its copy into the by-value kernel argument.
-static int fill_segments(const char* name, McnSegTable& t, const int32_t* seg_cam, const int32_t* seg_start, int K, int C, int n) {
-    REQ(seg_cam && seg_start, name);
-    REQ(K >= 1 && K <= MCN_MULTICAM_MAXSEG, name);
-    REQ(C >= 1 && n >= 0 && n <= (1 << 29), name);
-    REQ(seg_start[0] == 0 && seg_start[K] == n, name);
-    t.K = K;
-    for (int k = 0; k < K; ++k) {
-        REQ(seg_cam[k] >= 0 && seg_cam[k] < C, name);
-        REQ(seg_start[k + 1] >= seg_start[k], name);
-        t.cam[k] = seg_cam[k]; t.start[k] = seg_start[k];
-    }
-    t.start[K] = n;
-    return 0;
-}
 
 extern "C" {
 
@@ -74,7 +44,7 @@ int mcnerf_ext_gather_alpha(const uint8_t* images, int C, long long npix, int ch
                             const int32_t* seg_cam, const int32_t* seg_start, int K,
                             const int64_t* pix, int n, float* alpha, void* stream) {
     McnSegTable t;
-    if (int rc = fill_segments("mcnerf_ext_gather_alpha", t, seg_cam, seg_start, K, C, n)) return rc;
+    if (int rc = fill_segments("mcnerf_ext_gather_alpha", t, seg_cam, seg_start, K, C, n, MCN_ANY_SEG)) return rc;
     REQ(npix >= 1 && (channels == 3 || channels == 4), "mcnerf_ext_gather_alpha");
     if (n == 0) return 0;
     REQ(images && pix && alpha, "mcnerf_ext_gather_alpha");

@@ -4,26 +4,11 @@
 #include "../../include/mcnerf_reg.h"
 #include "mcnerf_distortion.h"
 #include "mcnerf_composite.h"
-#include <stdio.h>
+#include "mcnerf_api.h"
 
 // the limits the public header states are the kernels' own
 static_assert(MCNERF_REG_BWD_MAX_SAMPLES == MCN_COMPOSITE_BWD_MAX_SAMPLES, "include/mcnerf_reg.h: MCNERF_REG_BWD_MAX_SAMPLES");
 static_assert(MCNERF_REG_MOMENT_BYTES == MCN_DIST_MOMENT_BYTES && MCN_DIST_MOMENT_BYTES == 2 * sizeof(double), "include/mcnerf_reg.h: MCNERF_REG_MOMENT_BYTES");
-
-static thread_local char g_err[512] = "";
-
-static int fail(const char* where, const char* what) {
-    snprintf(g_err, sizeof(g_err), "%s: %s", where, what);
-    return -1;
-}
-static int check(const char* where, hipError_t e) {
-    if (e == hipSuccess) return 0;
-    snprintf(g_err, sizeof(g_err), "%s: HIP error %d (%s)", where, (int)e, hipGetErrorString(e));
-    return -2;
-}
-static bool z_ok(int z_stride, int S) { return z_stride == 0 || z_stride == S; }
-static bool finite_f(float v) { return v == v && v >= -3.0e38f && v <= 3.0e38f; }
-#define REQ(cond, name) do { if (!(cond)) return fail(name, "invalid argument: " #cond); } while (0)
 
 extern "C" {
 

@@ -546,16 +546,40 @@ def composite_fwd(sig_rgb: Tensor, rays_d: Tensor, zgrid: Tensor, jitter: Option
     return rgb, depth, opac, w_sel, wmax
 
 
+def _bwd_out(d_rgb: Tensor, S: int, want_gmax: bool):
+    """-> (d_sig_rgb [N,S,4], the zeroed word of max|d_sig_rgb| or None, what a composite backward returns: (d, gmax) with want_gmax, else d)"""
+    d = torch.empty(d_rgb.shape[0], S, 4, dtype=torch.float32, device=d_rgb.device)
+    gmax = torch.zeros(1, dtype=torch.int32, device=d_rgb.device) if want_gmax else None
+    return d, gmax, ((d, gmax) if want_gmax else d)
+
+
+def _moments_of(d_dist: Optional[Tensor], moments: Optional[Tensor], N: int) -> Optional[Tensor]:
+    """The `moments` argument of a composite backward: those of `distortion_fwd`, checked, with d_dist; None without it."""
+    if d_dist is None:
+        return None
+    if moments is None or tuple(moments.shape) != (N, DIST_MOMENT_BYTES):
+        raise _lib.McnerfError(f"d_dist needs the moments [{N}, {DIST_MOMENT_BYTES}] of distortion_fwd, got "
+                               + ("None" if moments is None else str(tuple(moments.shape))))
+    return moments
+
+
+def _gather_out(src: Tensor, dims: int, layout: str, seg_cam, seg_start, pix: Tensor):
+    """-> (cams, start, K, n, out [n]) of a gather over the per-camera pixels `src` (`dims` dimensions; `layout` words the refusal)."""
+    cams, start, K, n = _seg_arrays(seg_cam, seg_start)
+    if src.dim() != dims or pix.numel() != n:
+        raise _lib.McnerfError(f"{layout} and pix must hold seg_start[-1] = {n} ids, got {tuple(src.shape)}, {pix.numel()}")
+    return cams, start, K, n, torch.empty(n, dtype=torch.float32, device=pix.device)
+
+
 def composite_bwd(sig_rgb: Tensor, zgrid: Tensor, jitter: Optional[Tensor], eps: Tensor, d_rgb: Tensor,
                   white_back: bool = True, want_gmax: bool = False, *, z_rows: Optional[Tensor] = None):
     """-> d_sig_rgb [N,S,4] (and, with want_gmax, the int32 word holding max|d_sig_rgb| as float bits); `z_rows` as composite_fwd's"""
     N = d_rgb.shape[0]
     zgrid, S, zs = _depths(zgrid, z_rows, N)
-    d = torch.empty(N, S, 4, dtype=torch.float32, device=d_rgb.device)
-    gmax = torch.zeros(1, dtype=torch.int32, device=d_rgb.device) if want_gmax else None
+    d, gmax, out = _bwd_out(d_rgb, S, want_gmax)
     _lib.call("mcnerf_composite_bwd", sig_rgb, zgrid, zs, jitter, eps, d_rgb, N, S,
               int(bool(white_back)), d, gmax, _stream())
-    return (d, gmax) if want_gmax else d
+    return out
 
 
 # --------------------------------------------------------------------------- alpha-mask supervision (the extension library; DESIGN.md 4h)
@@ -574,20 +598,16 @@ def composite_bwd_front(sig_rgb: Tensor, zgrid: Tensor, jitter: Optional[Tensor]
     """`composite_bwd` of  sum rgb * d_rgb + sum fg * d_fg  (d_fg [N]); with d_fg None the bits of `composite_bwd`."""
     N = d_rgb.shape[0]
     zgrid, S, zs = _depths(zgrid, z_rows, N)
-    d = torch.empty(N, S, 4, dtype=torch.float32, device=d_rgb.device)
-    gmax = torch.zeros(1, dtype=torch.int32, device=d_rgb.device) if want_gmax else None
+    d, gmax, out = _bwd_out(d_rgb, S, want_gmax)
     _ext.call("mcnerf_ext_composite_bwd_front", sig_rgb, zgrid, zs, jitter, eps, d_rgb, d_fg, N, S,
               int(bool(white_back)), d, gmax, _stream())
-    return (d, gmax) if want_gmax else d
+    return out
 
 
 def gather_alpha(images_u8: Tensor, seg_cam, seg_start, pix: Tensor) -> Tensor:
     """images_u8 [C, H*W, 3|4] uint8 on the device, pix [n] int64 (segment k = rays [seg_start[k], seg_start[k+1]) of camera
     seg_cam[k]; host lists) -> alpha [n] fp32 = a / 255 of the drawn pixels, ones for 3-channel images."""
-    cams, start, K, n = _seg_arrays(seg_cam, seg_start)
-    if images_u8.dim() != 3 or pix.numel() != n:
-        raise _lib.McnerfError(f"images must be [C, H*W, channels] and pix must hold seg_start[-1] = {n} ids, got {tuple(images_u8.shape)}, {pix.numel()}")
-    alpha = torch.empty(n, dtype=torch.float32, device=pix.device)
+    cams, start, K, n, alpha = _gather_out(images_u8, 3, "images must be [C, H*W, channels]", seg_cam, seg_start, pix)
     _ext.call("mcnerf_ext_gather_alpha", images_u8, int(images_u8.shape[0]), int(images_u8.shape[1]), int(images_u8.shape[2]),
               cams, start, K, pix, n, alpha, _stream())
     return alpha
@@ -635,14 +655,11 @@ def composite_bwd_w(sig_rgb: Tensor, zgrid: Tensor, jitter: Optional[Tensor], ep
     of `composite_bwd`."""
     N = d_rgb.shape[0]
     zgrid, S, zs = _depths(zgrid, z_rows, N)
-    if d_dist is not None and (moments is None or tuple(moments.shape) != (N, DIST_MOMENT_BYTES)):
-        raise _lib.McnerfError(f"d_dist needs the moments [{N}, {DIST_MOMENT_BYTES}] of distortion_fwd, got "
-                               + ("None" if moments is None else str(tuple(moments.shape))))
-    d = torch.empty(N, S, 4, dtype=torch.float32, device=d_rgb.device)
-    gmax = torch.zeros(1, dtype=torch.int32, device=d_rgb.device) if want_gmax else None
-    _reg.call("mcnerf_reg_composite_bwd_w", sig_rgb, zgrid, zs, jitter, eps, d_rgb, d_fg, d_dist, moments if d_dist is not None else None,
+    moments = _moments_of(d_dist, moments, N)
+    d, gmax, out = _bwd_out(d_rgb, S, want_gmax)
+    _reg.call("mcnerf_reg_composite_bwd_w", sig_rgb, zgrid, zs, jitter, eps, d_rgb, d_fg, d_dist, moments,
               *_z_span(near, far), N, S, int(bool(white_back)), d, gmax, _stream())
-    return (d, gmax) if want_gmax else d
+    return out
 
 
 # --------------------------------------------------------------------------- depth supervision (the geometry library; DESIGN.md 4j)
@@ -663,26 +680,20 @@ def composite_bwd_z(sig_rgb: Tensor, zgrid: Tensor, jitter: Optional[Tensor], ep
     d_dist with the `moments` of `distortion_fwd` on the same inputs, near and far).  With d_zexp None the bits of `composite_bwd_w`."""
     N = d_rgb.shape[0]
     zgrid, S, zs = _depths(zgrid, z_rows, N)
-    if d_dist is not None and (moments is None or tuple(moments.shape) != (N, DIST_MOMENT_BYTES)):
-        raise _lib.McnerfError(f"d_dist needs the moments [{N}, {DIST_MOMENT_BYTES}] of distortion_fwd, got "
-                               + ("None" if moments is None else str(tuple(moments.shape))))
+    moments = _moments_of(d_dist, moments, N)
     if d_zexp is not None and d_zexp.numel() != N:
         raise _lib.McnerfError(f"d_zexp must hold the {N} rays of d_rgb, got {tuple(d_zexp.shape)}")
-    d = torch.empty(N, S, 4, dtype=torch.float32, device=d_rgb.device)
-    gmax = torch.zeros(1, dtype=torch.int32, device=d_rgb.device) if want_gmax else None
-    _geo.call("mcnerf_geo_composite_bwd_z", sig_rgb, zgrid, zs, jitter, eps, d_rgb, d_fg, d_dist, moments if d_dist is not None else None,
+    d, gmax, out = _bwd_out(d_rgb, S, want_gmax)
+    _geo.call("mcnerf_geo_composite_bwd_z", sig_rgb, zgrid, zs, jitter, eps, d_rgb, d_fg, d_dist, moments,
               d_zexp, *_z_span(near, far), N, S, int(bool(white_back)), d, gmax, _stream())
-    return (d, gmax) if want_gmax else d
+    return out
 
 
 def gather_depth(depth: Tensor, seg_cam, seg_start, pix: Tensor) -> Tensor:
     """depth [C, H*W] fp32 on the device (ray distance in world units), pix [n] int64 (segment k = rays [seg_start[k], seg_start[k+1])
     of camera seg_cam[k]; host lists) -> d_gt [n] fp32: the stored value where it is finite and > 0, else 0.0 (no measurement; a pixel
     id outside the image as well)."""
-    cams, start, K, n = _seg_arrays(seg_cam, seg_start)
-    if depth.dim() != 2 or pix.numel() != n:
-        raise _lib.McnerfError(f"depth must be [C, H*W] and pix must hold seg_start[-1] = {n} ids, got {tuple(depth.shape)}, {pix.numel()}")
-    out = torch.empty(n, dtype=torch.float32, device=pix.device)
+    cams, start, K, n, out = _gather_out(depth, 2, "depth must be [C, H*W]", seg_cam, seg_start, pix)
     _geo.call("mcnerf_geo_gather_depth", depth, int(depth.shape[0]), int(depth.shape[1]), cams, start, K, pix, n, out, _stream())
     return out
 

@@ -199,3 +199,33 @@ def test_the_composite_backward_and_its_helpers_are_defined_once():
     for headers in (build.HEADERS, build.EXT_HEADERS, build.REG_HEADERS):
         assert "mcnerf_composite.h" in headers and "mcnerf_wave.h" in headers
     assert "mcnerf_composite.h" not in bench.MLP_KERNEL_SOURCES
+
+
+API_ONCE = ("fail", "check", "z_ok", "finite_f", "fill_segments")
+MLP_SOURCE_DIGEST = "7c1c6a7b8f60d22d"      # bench.csrc_digest() of the commit before the libraries' preamble moved into mcnerf_api.h
+
+
+def test_the_libraries_api_preamble_binding_and_build_recipe_are_defined_once():
+    """Every library's *_api.hip takes its error reporters and shared argument checks from ONE header (csrc/mcnerf_api.h; the same
+    column-0 rule as above), every library's header list names it, the four bindings beside `_lib` are one `Binding` line each, and
+    none of it is part of the MLP source digest that the recorded traffic profiles are tied to."""
+    import bench
+    from mc_nerf_amd import build
+    defined, req = {name: [] for name in API_ONCE}, []
+    for fn in sorted(f for f in os.listdir(build.CSRC) if f.endswith((".hip", ".h"))):
+        text = open(os.path.join(build.CSRC, fn)).read()
+        req += [fn] * len(re.findall(r"^\s*#\s*define\s+REQ\b", text, flags=re.M))
+        for line in text.split("\n"):
+            code = re.sub(r"//.*", "", line).rstrip()
+            for name in API_ONCE:
+                if re.match(rf"[A-Za-z_][^=;]*\b{name}\s*\(", code) and not code.endswith(";"):
+                    defined[name].append(fn)
+    for name, files in defined.items():
+        assert files == ["mcnerf_api.h"], f"{name} is defined in {files}"
+    assert req == ["mcnerf_api.h"], f"REQ is defined in {req}"
+    for headers in (build.HEADERS, build.EXT_HEADERS, build.REG_HEADERS, build.GEO_HEADERS, build.BOX_HEADERS):
+        assert "mcnerf_api.h" in headers and "mcnerf_multicam.h" in headers
+    for module in ("_ext.py", "_reg.py", "_geo.py", "_box.py"):
+        text = open(os.path.join(ROOT, "mc_nerf_amd", module)).read()
+        assert "def " not in text and "CDLL" not in text and "Binding(" in text, module
+    assert "mcnerf_api.h" not in bench.MLP_KERNEL_SOURCES and bench.csrc_digest() == MLP_SOURCE_DIGEST
