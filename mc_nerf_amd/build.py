@@ -16,11 +16,18 @@ _INC = os.path.join("..", "..", "include")
 # libraries share the object directory; none links an object of another.  Every list names mcnerf_api.h, the preamble of the
 # library's *_api.hip, and mcnerf_multicam.h, which that includes.  A new library is one more entry (the recipe).
 LIBRARIES = {
-    # per-ray sample bounds (include/mcnerf_box.h).  The sampler's device code reaches it through mcnerf_sample_pdf.h and
-    # the voxel kernels by ray_bounds.hip including voxel.hip (listed with the headers: a change of it recompiles ray_bounds.hip)
+    # skipping the rays that miss the scene box (include/mcnerf_hit.h).  ray_skip.hip includes ray_bounds.hip, and with it
+    # select.hip and voxel.hip (listed with the headers: a change of one recompiles ray_skip.hip)
+    "HIT_": ("libmcnhit.so", ["hit_api.hip", "ray_skip.hip"],
+             ["mcnerf_api.h", "mcnerf_common.h", "mcnerf_kernels.h", "mcnerf_wave.h", "mcnerf_voxel.h", "voxel.hip", "select.hip", "ray_bounds.hip", "mcnerf_compact.h",
+              "mcnerf_maxkey.h", "mcnerf_hash.h", "mcnerf_sample_pdf.h", "mcnerf_multicam.h", "mcnerf_ray_bounds.h", "mcnerf_ray_skip.h", os.path.join(_INC, "mcnerf.h"),
+              os.path.join(_INC, "mcnerf_hit.h")]),
+    # per-ray sample bounds (include/mcnerf_box.h).  The sampler's device code reaches it through mcnerf_sample_pdf.h, the
+    # voxel kernels and the lists' scan by ray_bounds.hip including voxel.hip and select.hip (listed with the headers: a change of one
+    # recompiles ray_bounds.hip)
     "BOX_": ("libmcnbox.so", ["box_api.hip", "ray_bounds.hip"],
-             ["mcnerf_api.h", "mcnerf_common.h", "mcnerf_kernels.h", "mcnerf_wave.h", "mcnerf_voxel.h", "voxel.hip", "mcnerf_compact.h", "mcnerf_maxkey.h",
-              "mcnerf_sample_pdf.h", "mcnerf_multicam.h", "mcnerf_ray_bounds.h", os.path.join(_INC, "mcnerf.h"), os.path.join(_INC, "mcnerf_box.h")]),
+             ["mcnerf_api.h", "mcnerf_common.h", "mcnerf_kernels.h", "mcnerf_wave.h", "mcnerf_voxel.h", "voxel.hip", "select.hip", "mcnerf_compact.h", "mcnerf_maxkey.h",
+              "mcnerf_hash.h", "mcnerf_sample_pdf.h", "mcnerf_multicam.h", "mcnerf_ray_bounds.h", os.path.join(_INC, "mcnerf.h"), os.path.join(_INC, "mcnerf_box.h")]),
     # depth supervision (include/mcnerf_geo.h)
     "GEO_": ("libmcngeo.so", ["geo_api.hip", "depth.hip"],
              ["mcnerf_api.h", "mcnerf_common.h", "mcnerf_wave.h", "mcnerf_composite.h", "mcnerf_multicam.h", "mcnerf_depth.h", os.path.join(_INC, "mcnerf.h"),
@@ -38,7 +45,7 @@ LIBRARIES = {
          ["mcnerf_api.h", "mcnerf_common.h", "mcnerf_kernels.h", "mcnerf_wave.h", "mcnerf_composite.h", "mcnerf_16.h", "mcnerf_x3.h", "mcnerf_launch.h", "mcnerf_voxel.h",
           "mcnerf_sample_pdf.h", "mcnerf_multicam.h", "mcnerf_colorcal.h", "mcnerf_errmap.h", "mcnerf_maxkey.h", "mcnerf_compact.h", "mcnerf_hash.h", "mcnerf_rays.h", "mcnerf_lens.h", "mcnerf_optim_rows.h", os.path.join(_INC, "mcnerf.h")]),
 }
-# OUT, SOURCES, HEADERS of the core library and EXT_OUT, EXT_SOURCES, EXT_HEADERS, REG_*, GEO_*, BOX_* of the others
+# OUT, SOURCES, HEADERS of the core library and EXT_OUT, EXT_SOURCES, EXT_HEADERS, REG_*, GEO_*, BOX_*, HIT_* of the others
 for _prefix, (_so, _sources, _headers) in LIBRARIES.items():
     globals().update({_prefix + "OUT": os.path.join(HERE, _so), _prefix + "SOURCES": _sources, _prefix + "HEADERS": _headers})
 # the f16x3 chains: a layer body is ~400 MFMAs with its epilogue slices, fully unrolled (beyond hipcc's default pragma-unroll budget);

@@ -18,6 +18,7 @@ struct McnRayDepthsArgs {
     float* z_c;               // [N,Sc] out
     float* z_f;               // [N,Sf] out, or null
     float* span;              // [N,2] out (lo, hi), or null
+    int* hit = nullptr;       // [N] out, 1 iff the ray is CLIPPED, or null (the hit library's entry point gives it: include/mcnerf_hit.h)
 };
 hipError_t mcn_launch_ray_depths(const McnRayDepthsArgs& a, hipStream_t st);
 // the sampler on rows: a.zgrid is [N,Sc], z_stride = Sc.  (The voxel select / update on rows are mcnerf_voxel.h's launchers with

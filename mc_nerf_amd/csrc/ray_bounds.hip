@@ -13,15 +13,19 @@
 //     data-dependent loop; every store is behind j < S of a ray behind n < N.
 // (2) The inverse-CDF sampler and the voxel select / update reading their depths from rows [N,Sc], z_stride = Sc: the sampler's body
 //     of mcnerf_sample_pdf.h under a kernel of this library's own, and the voxel kernels by compiling voxel.hip into this library as it
-//     stands (the library links none of the core library's objects, voxel.o included).
+//     stands (the library links none of the core library's objects, voxel.o included).  The scan between a list's count and its write
+//     comes the same way, with select.hip.
+// The hit library (ray_skip.hip) compiles this file into itself in turn: box_ray_span returns the flag it forms, and ray_depths_kernel
+// writes it where McnRayDepthsArgs::hit is given.
 #include "mcnerf_ray_bounds.h"
 #include "mcnerf_sample_pdf.h"
+#include "select.hip"
 #include "voxel.hip"
 
 __device__ __forceinline__ bool box_finite(float v) { return (__float_as_uint(v) & 0x7F800000u) != 0x7F800000u; }
 
-// (lo, hi) of ray (o, d): the clipped interval, or (near, far)
-__device__ __forceinline__ void box_ray_span(const McnRayDepthsArgs& a, const float* o, const float* d, float& lo, float& hi) {
+// (lo, hi) of ray (o, d): the clipped interval, or (near, far); true iff the ray is CLIPPED
+__device__ __forceinline__ bool box_ray_span(const McnRayDepthsArgs& a, const float* o, const float* d, float& lo, float& hi) {
     bool miss = false;
     float t_in = -INFINITY, t_out = INFINITY;
 #pragma unroll
@@ -38,7 +42,9 @@ __device__ __forceinline__ void box_ray_span(const McnRayDepthsArgs& a, const fl
     }
     lo = fmaxf(a.z_near, t_in);
     hi = fminf(a.z_far, t_out);
-    if (miss || !box_finite(lo) || !box_finite(hi) || !(hi > lo)) { lo = a.z_near; hi = a.z_far; }
+    const bool clipped = !(miss || !box_finite(lo) || !box_finite(hi) || !(hi > lo));
+    if (!clipped) { lo = a.z_near; hi = a.z_far; }
+    return clipped;
 }
 
 __global__ __launch_bounds__(256) void ray_depths_kernel(McnRayDepthsArgs a) {
@@ -46,7 +52,7 @@ __global__ __launch_bounds__(256) void ray_depths_kernel(McnRayDepthsArgs a) {
     const int n = blockIdx.x * 4 + (threadIdx.x >> 6);
     if (n >= a.N) return;
     float lo, hi;
-    box_ray_span(a, a.rays_o + (size_t)n * 3, a.rays_d + (size_t)n * 3, lo, hi);
+    const bool clipped = box_ray_span(a, a.rays_o + (size_t)n * 3, a.rays_d + (size_t)n * 3, lo, hi);
     const float av = __fdiv_rn(__fsub_rn(hi, lo), __fsub_rn(a.z_far, a.z_near));
     const float bv = __fsub_rn(lo, __fmul_rn(av, a.z_near));
     const bool jit = a.jitter != nullptr;
@@ -64,6 +70,7 @@ __global__ __launch_bounds__(256) void ray_depths_kernel(McnRayDepthsArgs a) {
         }
     }
     if (a.span && lane == 0) { a.span[(size_t)n * 2] = lo; a.span[(size_t)n * 2 + 1] = hi; }
+    if (a.hit && lane == 0) a.hit[n] = clipped ? 1 : 0;
 }
 hipError_t mcn_launch_ray_depths(const McnRayDepthsArgs& a, hipStream_t st) {
     if (a.N <= 0) return hipSuccess;
@@ -82,11 +89,4 @@ hipError_t mcn_launch_sample_pdf_rows(const McnSamplePdfArgs& a, hipStream_t st)
 
 // ------------------------------------------------------------------ the voxel select / update on rows
 // voxel.hip itself, compiled into this library (above): its kernels read z_stride from their arguments.  The scan between the count and
-// the write is select.hip's in the core library; here it is this kernel on the same body (mcn_scan_counts, mcnerf_compact.h).
-__global__ __launch_bounds__(1024) void box_scan_kernel(int N, const int* ray_counts, int* ray_offsets, int* count) {
-    mcn_scan_counts(N, ray_counts, ray_offsets, count);
-}
-hipError_t mcn_launch_select_scan(int N, int* ray_counts, int* ray_offsets, int* count, hipStream_t st) {
-    hipLaunchKernelGGL(box_scan_kernel, dim3(1), dim3(1024), 0, st, N, (const int*)ray_counts, ray_offsets, count);
-    return hipGetLastError();
-}
+// the write is select.hip's, compiled into this library beside it (mcn_launch_select_scan on mcn_scan_counts, mcnerf_compact.h).

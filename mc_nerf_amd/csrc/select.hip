@@ -16,12 +16,15 @@ struct SelectPred {             // (built behind the bounds check of the shared 
     __device__ __forceinline__ SelectPred(const McnSelectArgs& a) : a(a), thr(sel_threshold(a)) {}
     __device__ __forceinline__ bool operator()(int n, int j) const { return a.w_sel[(size_t)n * a.Sc + j] >= thr; }
 };
-__global__ __launch_bounds__(256) void select_count_kernel(McnSelectArgs a) {
-    mcn_compact_count<SelectPred>(a.N, a.Sc, a.scale, a.sigma_default, a.ray_counts, a.out_f, a);
+// The count and the write kernel of a list over [N, Sc] with `scale`, under any predicate on arguments that carry McnSelectArgs' names:
+// the fine list below, and the hit library's lists (ray_skip.hip: the same predicate behind a ray's hit flag, and the flag alone).
+template <typename Pred, typename Args>
+__global__ __launch_bounds__(256) void select_count_kernel(Args a) {
+    mcn_compact_count<Pred>(a.N, a.Sc, a.scale, a.sigma_default, a.ray_counts, a.out_f, a);
 }
 
-// Exclusive scan of ray_counts -> ray_offsets, total -> *count; the body is mcn_scan_counts (mcnerf_compact.h), shared with the bounds
-// library.  One workgroup; N is at most ~1e6.  Every thread owns one contiguous run of `per` rays per thread: a private sum, ONE block-wide scan of the 1024 run sums, then the run's offsets -- two
+// Exclusive scan of ray_counts -> ray_offsets, total -> *count; the body is mcn_scan_counts (mcnerf_compact.h).  (The bounds and the hit
+// library compile this file into themselves for it: ray_bounds.hip.)  One workgroup; N is at most ~1e6.  Every thread owns one contiguous run of `per` rays per thread: a private sum, ONE block-wide scan of the 1024 run sums, then the run's offsets -- two
 // barriers in all.  A run is a multiple of four rays held in registers as int4 vectors: its loads (and its stores) are independent
 // 16-byte operations in flight together (the scalar loop of dependent 4-byte loads over a 32-ray run took 53 us at 32768 rays);
 // runs longer than 64 rays (N > 65536) or unaligned workspaces take the scalar loop.
@@ -29,12 +32,13 @@ __global__ __launch_bounds__(1024) void select_scan_kernel(McnSelectArgs a) {
     mcn_scan_counts(a.N, a.ray_counts, a.ray_offsets, a.count);
 }
 
-__global__ __launch_bounds__(256) void select_write_kernel(McnSelectArgs a) {
-    mcn_compact_write<SelectPred>(a.N, a.Sc, a.scale, a.ray_offsets, a.idx, a);
+template <typename Pred, typename Args>
+__global__ __launch_bounds__(256) void select_write_kernel(Args a) {
+    mcn_compact_write<Pred>(a.N, a.Sc, a.scale, a.ray_offsets, a.idx, a);
 }
 
 hipError_t mcn_launch_select(const McnSelectArgs& a, hipStream_t st) {
-    return mcn_launch_compact<McnSelectArgs, select_count_kernel, select_write_kernel>(a, st);
+    return mcn_launch_compact<McnSelectArgs, select_count_kernel<SelectPred, McnSelectArgs>, select_write_kernel<SelectPred, McnSelectArgs>>(a, st);
 }
 hipError_t mcn_launch_select_scan(int N, int* ray_counts, int* ray_offsets, int* count, hipStream_t st) {
     McnSelectArgs a = {};       // (the scan reads these four fields alone)

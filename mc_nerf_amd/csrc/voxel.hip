@@ -43,14 +43,17 @@ struct VoxelPred {
         return a.vox[vox_sample_cell(a.rays_o, a.rays_d, a.zgrid, a.z_stride, a.jitter, n, j, a.bmin, a.s, a.G)] > a.thresh;
     }
 };
-__global__ __launch_bounds__(256) void voxel_count_kernel(McnVoxelSelectArgs a) {
-    mcn_compact_count<VoxelPred>(a.N, a.Sc, 1, a.sigma_default, a.ray_counts, a.out_c, a);
+// (templates, as select.hip's pair: the hit library runs them under VoxelPred behind a ray's hit flag, ray_skip.hip)
+template <typename Pred, typename Args>
+__global__ __launch_bounds__(256) void voxel_count_kernel(Args a) {
+    mcn_compact_count<Pred>(a.N, a.Sc, 1, a.sigma_default, a.ray_counts, a.out_c, a);
 }
-__global__ __launch_bounds__(256) void voxel_write_kernel(McnVoxelSelectArgs a) {
-    mcn_compact_write<VoxelPred>(a.N, a.Sc, 1, a.ray_offsets, a.idx, a);
+template <typename Pred, typename Args>
+__global__ __launch_bounds__(256) void voxel_write_kernel(Args a) {
+    mcn_compact_write<Pred>(a.N, a.Sc, 1, a.ray_offsets, a.idx, a);
 }
 hipError_t mcn_launch_voxel_select(const McnVoxelSelectArgs& a, hipStream_t st) {
-    return mcn_launch_compact<McnVoxelSelectArgs, voxel_count_kernel, voxel_write_kernel>(a, st);
+    return mcn_launch_compact<McnVoxelSelectArgs, voxel_count_kernel<VoxelPred, McnVoxelSelectArgs>, voxel_write_kernel<VoxelPred, McnVoxelSelectArgs>>(a, st);
 }
 
 // ------------------------------------------------------------------ update

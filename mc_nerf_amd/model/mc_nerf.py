@@ -136,9 +136,16 @@ class NeRF_Model(nn.Module):
             raise ValueError(f"ray_bounds must be 'global' or 'aabb', got {self.ray_bounds!r}")
         if self.ray_bounds == "aabb":
             self.settings.ray_bounds, self.settings.box = "aabb", self._bounds_box(sys_param)
+            # "ray_bounds_miss" is this build's own key too, read in "aabb" mode only, as the box: "sample" (a ray that
+            # misses the box is sampled on [near, far]; the default and today's path: the hit library is not even loaded) or "skip"
+            # (neither net evaluates a sample of such a ray: its rows are the prefill, its gradients exact zeros)
+            self.settings.ray_bounds_miss = sys_param.get("ray_bounds_miss", "sample")
+            if self.settings.ray_bounds_miss not in ("sample", "skip"):
+                raise ValueError(f"ray_bounds_miss must be 'sample' or 'skip', got {self.settings.ray_bounds_miss!r}")
         self.last_ray_span = None         # "aabb" mode: (lo, hi) [N,2] of the last render's rays; (near, far) on a ray the box does not clip
-        self.last_coarse_selection = None  # (idx_c, count_c) of the last pruned coarse pass; None in "dense" mode and in the warm-up
-        self.last_selection = None        # (idx, count) of the last fine pass in "threshold" mode; None in "pdf" mode
+        self.last_ray_hit = None          # "skip" mode: [N] int32 of the last render's rays, 1 iff the box clips the ray
+        self.last_coarse_selection = None  # (idx_c, count_c) of the last listed coarse pass (pruned, or "skip" mode); else None
+        self.last_selection = None        # (idx, count) of the last listed fine pass ("threshold" mode, or "skip" mode); else None
         self.last_z_all = None            # the fine pass's depth rows [N, samples + n_importance] in "pdf" mode
         self.last_flat_grads = None
         self.grad_arena = None            # set per step by distributed.FlatGradSync.prepare()

@@ -16,6 +16,8 @@ What a sampler setting changes in its pass:
       the pass: no gradient through the sampler); the rows hold the jitter.
   coarse_sampler "voxel": the list ops.voxel_select reads off the owner's sigma grid, over the prefill.  Train calls keep the grid
       current from their evaluated samples (ops.voxel_update) and run dense in the warm-up; rendering only queries.
+  ray_bounds_miss "skip" ("aabb" mode): every pass is a listed one, its list built behind the per-ray hit flag (ops.list_rays, or
+      `hit=` of ops.select_fine / ops.voxel_select): no sample of a ray that misses the box reaches a net, its rows stay the prefill.
   ray_bounds "aabb": both passes take per-ray rows (`bounds_rows`: ops.ray_depths on the scene box; the rows hold the jitter) where
       they took the shared grid plus jitter: the voxel list and update, the pdf sampler and the threshold fine pass, which is then a
       listed pass on rows [N,Sf].  The rows are constants of the backward.
@@ -62,6 +64,10 @@ class RenderSettings:
     # mapped onto the part of [near, far] inside `box` = (xmin, ymin, zmin, xmax, ymax, zmax) (ops.ray_depths).  (Ahead of want_zexp: its place at the end of the field list is pinned.)
     ray_bounds: str = "global"
     box: Optional[tuple] = None
+    # read in "aabb" mode only.  "sample": a ray that misses the box is sampled on [near, far] (today's launches and bits;
+    # the hit library is not loaded); "skip": neither net evaluates a sample of it -- both passes are listed passes over the prefill, their
+    # lists built behind the per-ray hit flag of ops.ray_depths
+    ray_bounds_miss: str = "sample"
     # depth mode: each pass's expected depth on the rgb composite's own weights is one more differentiable output of
     # the train render.  The switch rides here, not on RenderCall (its field list is pinned); NeRF_Model sets it from "depth_weight"
     want_zexp: bool = False
@@ -69,6 +75,10 @@ class RenderSettings:
     @property
     def aabb(self) -> bool:
         return self.ray_bounds == "aabb"
+
+    @property
+    def skip_misses(self) -> bool:
+        return self.aabb and self.ray_bounds_miss == "skip"
 
     @property
     def samples_f(self):
@@ -268,12 +278,13 @@ def pass_backward(p: SamplePass, st: RenderSettings, rays: Rays, d_rgb, grads, d
     lease.give(p.save)
 
 
-def select_and_cap(st: RenderSettings, w_sel, wmax, n_rays, cap_perm, train: bool):
-    """Device-side selection; applies the random cap in training.  Returns idx, count, out_f, max_rows.
+def select_and_cap(st: RenderSettings, w_sel, wmax, n_rays, cap_perm, train: bool, hit=None):
+    """Device-side selection; applies the random cap in training.  Returns idx, count, out_f, max_rows.  `hit` [N] (skipping the rays
+    that miss the box): only rays with hit[n] != 0 are selected from; the cap then acts on that list, with the same row capacities.
     No host synchronisation: the cap's random subset is drawn on the device (ops.cap_random) with a seed word taken
     from torch's device generator.  Only a caller-supplied permutation (`cap_perm`, the parity-test input that replays
     the reference's CPU randperm, :631) goes through the host: its length IS the host-side count."""
-    idx, count, out_f = ops.select_fine(w_sel, wmax, st.weight_thresh, st.scale, st.sigma_default)
+    idx, count, out_f = ops.select_fine(w_sel, wmax, st.weight_thresh, st.scale, st.sigma_default, hit=hit)
     max_rows, keep = st.fine_rows(n_rays, train=False), st.fine_rows(n_rays, train=True)
     if train and keep < max_rows:
         if cap_perm is not None:
@@ -291,29 +302,35 @@ def select_and_cap(st: RenderSettings, w_sel, wmax, n_rays, cap_perm, train: boo
 
 
 def bounds_rows(owner, rays: Rays, jitter):
-    """(z_c [N,Sc], z_f [N,Sf] | None) of a render in "aabb" mode -- the model's own grids mapped onto every ray's part of [near, far]
-    inside the box, jitter included (ops.ray_depths; z_f in "threshold" mode only: the pdf sampler draws its own fine depths) -- and
-    None in "global" mode, where nothing is allocated.  The (lo, hi) of every ray stays with the owner in `last_ray_span`."""
+    """(z_c [N,Sc], z_f [N,Sf] | None, hit [N] int32 | None) of a render in "aabb" mode -- the model's own grids mapped onto every ray's
+    part of [near, far] inside the box, jitter included (ops.ray_depths; z_f in "threshold" mode only: the pdf sampler draws its own
+    fine depths), and with `ray_bounds_miss` = "skip" the flag of the rays the box clips, from the same launch -- and None in "global"
+    mode, where nothing is allocated.  The (lo, hi) of every ray stays with the owner in `last_ray_span`, the flags in `last_ray_hit`."""
     st: RenderSettings = owner.settings
     if not st.aabb:
         return None
     if not rays.d.is_cuda:
         raise ops._lib.McnerfError(f"ray_bounds = 'aabb': the per-ray depths are a HIP kernel, got rays on {rays.d.device} (no CPU fallback)")
-    z_c, z_f, owner.last_ray_span = ops.ray_depths(rays.o, rays.d, st.box, float(owner.near), float(owner.far), jitter, owner.z_vals_c,
-                                                   None if st.pdf else owner.z_vals_f)
-    return z_c, z_f
+    z_c, z_f, owner.last_ray_span, *hit = ops.ray_depths(rays.o, rays.d, st.box, float(owner.near), float(owner.far), jitter, owner.z_vals_c,
+                                                         None if st.pdf else owner.z_vals_f, want_hit=st.skip_misses)
+    owner.last_ray_hit = hit[0] if hit else None
+    return z_c, z_f, owner.last_ray_hit
 
 
 def coarse_pass(owner, model, flat, packed, rays: Rays, jitter, eps, prune: bool, rows=None) -> SamplePass:
     """The coarse pass: the dense [N,Sc] grid, or (`prune`, read in "voxel" mode only: a train call past the warm-up, or rendering)
-    the sigma grid's list over the default prefill.  `rows` (`bounds_rows`; "aabb" mode): the depths are its coarse rows."""
+    the sigma grid's list over the default prefill.  `rows` (`bounds_rows`; "aabb" mode): the depths are its coarse rows.  With its
+    hit flags the pass is always a listed one: the grid's list behind the flag, or every sample of the rays that hit (ops.list_rays)."""
     st: RenderSettings = owner.settings
     N = rays.d.shape[0]
     grid = owner.voxel_grid() if st.voxel else None
     zgrid, jitter, z_rows = (owner.z_vals_c, jitter, None) if rows is None else (None, None, rows[0])
+    hit = None if rows is None else rows[2]
     idx = count = None
     if grid is not None and prune:
-        idx, count, out = ops.voxel_select(grid, st.voxel_thresh, rays.o, rays.d, zgrid, jitter, st.sigma_default, z_rows=z_rows)
+        idx, count, out = ops.voxel_select(grid, st.voxel_thresh, rays.o, rays.d, zgrid, jitter, st.sigma_default, z_rows=z_rows, hit=hit)
+    elif hit is not None:
+        idx, count, out = ops.list_rays(hit, st.samples_c, st.sigma_default)
     else:
         out = torch.empty(N, st.samples_c, 4, dtype=torch.float32, device=rays.d.device)
     owner.last_coarse_selection = None if idx is None else (idx, count)
@@ -323,14 +340,20 @@ def coarse_pass(owner, model, flat, packed, rays: Rays, jitter, eps, prune: bool
 def fine_pass(owner, model, flat, packed, rays: Rays, jitter, w_sel, wmax, eps, u, cap_perm, train: bool, rows=None) -> SamplePass:
     """The fine pass from the coarse composite's selection weights: the selected (ray, sample) list over the default prefill (no host
     sync), or in "pdf" mode dense rows of inverse-CDF depths drawn with `u`.  `rows` (`bounds_rows`; "aabb" mode): the sampler reads
-    its coarse rows, the listed pass runs on its fine rows."""
+    its coarse rows, the listed pass runs on its fine rows.  With its hit flags the selection is made behind them, and the "pdf" pass is
+    a listed pass too, on the sampler's rows of the rays that hit."""
     st: RenderSettings = owner.settings
+    hit = None if rows is None else rows[2]
     if st.pdf:
         z_all = ops.sample_pdf(w_sel, owner.z_vals_c, jitter, u) if rows is None else ops.sample_pdf(w_sel, None, None, u, z_rows=rows[0])
-        out = torch.empty(*z_all.shape, 4, dtype=torch.float32, device=rays.d.device)
-        p = SamplePass(model, flat, packed, None, None, z_all, eps, out)
+        if hit is not None:
+            idx, count, out = ops.list_rays(hit, z_all.shape[1], st.sigma_default)
+            p = SamplePass(model, flat, packed, None, None, z_all, eps, out, idx, count, z_all.shape[0] * z_all.shape[1])
+        else:
+            out = torch.empty(*z_all.shape, 4, dtype=torch.float32, device=rays.d.device)
+            p = SamplePass(model, flat, packed, None, None, z_all, eps, out)
     else:
-        idx, count, out, max_rows = select_and_cap(st, w_sel, wmax, rays.d.shape[0], cap_perm, train)
+        idx, count, out, max_rows = select_and_cap(st, w_sel, wmax, rays.d.shape[0], cap_perm, train, hit)
         zgrid, jitter, z_rows = (owner.z_vals_f, jitter, None) if rows is None else (None, None, rows[1])
         p = SamplePass(model, flat, packed, zgrid, jitter, z_rows, eps, out, idx, count, max_rows)
     owner.last_selection, owner.last_z_all = None if p.idx is None else (p.idx, p.count), p.z_rows if st.pdf else None

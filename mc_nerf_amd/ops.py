@@ -12,7 +12,7 @@ from typing import Optional, Tuple
 
 import torch
 
-from . import _box, _ext, _geo, _lib, _reg
+from . import _box, _ext, _geo, _hit, _lib, _reg
 
 Tensor = torch.Tensor
 
@@ -723,15 +723,40 @@ def _list_buffers(N: int, S: int, prefill: bool, idx: Optional[Tensor], dev):
     return idx, count, rc, ro, torch.empty(N, S, 4, dtype=torch.float32, device=dev) if prefill else None
 
 
+def _hit_flags(name: str, hit: Tensor, N: int) -> Tensor:
+    if hit.dim() != 1 or hit.shape[0] != N:
+        raise _lib.McnerfError(f"{name}: hit must be [N = {N}] int32, got {tuple(hit.shape)}")
+    return hit
+
+
 def select_fine(w_sel: Tensor, wmax: Tensor, thresh: float, scale: int, sigma_default: float,
-                prefill: bool = True):
-    """-> idx [N*Sc*scale,2] int32 (first *count rows valid), count [1] int32, out_f [N,Sf,4] | None"""
+                prefill: bool = True, hit: Optional[Tensor] = None):
+    """-> idx [N*Sc*scale,2] int32 (first *count rows valid), count [1] int32, out_f [N,Sf,4] | None
+    `hit` [N] int32: only rays with hit[n] != 0 are listed; the hit library's entry point (include/mcnerf_hit.h)."""
     N, Sc = w_sel.shape
     idx, count, rc, ro, out_f = _list_buffers(N, Sc * scale, prefill, None, w_sel.device)
-    _lib.call("mcnerf_select_fine", w_sel, wmax, float(thresh), N, Sc, scale,
-              float(sigma_default), rc, ro, idx,
-              count, out_f, _stream())
+    if hit is not None:
+        _hit.call("mcnerf_hit_select_fine", w_sel, wmax, float(thresh), N, Sc, scale, float(sigma_default), rc, ro, idx, count, out_f,
+                  _hit_flags("select_fine", hit, N), _stream())
+    else:
+        _lib.call("mcnerf_select_fine", w_sel, wmax, float(thresh), N, Sc, scale,
+                  float(sigma_default), rc, ro, idx,
+                  count, out_f, _stream())
     return idx, count, out_f
+
+
+def list_rays(hit: Tensor, S: int, sigma_default: float, prefill: bool = True, idx: Optional[Tensor] = None):
+    """-> idx [N*S,2] int32 (first *count rows valid, torch.nonzero order), count [1] int32 = S * (rays with hit[n] != 0), out [N,S,4] |
+    None: every (ray, sample) pair of the rays that hit the scene box and the (sigma_default, 1, 1, 1) prefill of all rays
+    (include/mcnerf_hit.h: mcnerf_hit_list_rays).  No host synchronisation.  `idx`: the caller's own list buffer (rows beyond *count are
+    left as they are)."""
+    N, S = hit.shape[0], int(S)
+    _hit_flags("list_rays", hit, N)
+    if idx is not None and idx.numel() < N * S * 2:
+        raise _lib.McnerfError(f"list_rays: idx must hold N * S = {N * S} pairs, got {tuple(idx.shape)}")
+    idx, count, rc, ro, out = _list_buffers(N, S, prefill, idx, hit.device)
+    _hit.call("mcnerf_hit_list_rays", hit, N, S, float(sigma_default), rc, ro, idx, count, out, _stream())
+    return idx, count, out
 
 
 def sample_pdf(w_sel: Tensor, zgrid: Optional[Tensor], jitter: Optional[Tensor], u: Tensor, out: Optional[Tensor] = None, *,
@@ -765,10 +790,12 @@ def sample_pdf(w_sel: Tensor, zgrid: Optional[Tensor], jitter: Optional[Tensor],
 
 # --------------------------------------------------------------------------- per-ray sample bounds (include/mcnerf_box.h)
 def ray_depths(rays_o: Tensor, rays_d: Tensor, box, near: float, far: float, jitter: Optional[Tensor], zgrid_c: Tensor,
-               zgrid_f: Optional[Tensor] = None, want_span: bool = True):
+               zgrid_f: Optional[Tensor] = None, want_span: bool = True, want_hit: bool = False):
     """Per-ray depth rows from the scene box (mcnerf_box_ray_depths; the rule: include/mcnerf_box.h): rays [N,3], box = (xmin, ymin,
     zmin, xmax, ymax, zmax), jitter [N] | None, the grids zgrid_c [Sc] and zgrid_f [Sf] | None -> z_c [N,Sc], z_f [N,Sf] | None,
-    span [N,2] = (lo, hi) | None.  One launch, no host synchronisation; constants of the backward."""
+    span [N,2] = (lo, hi) | None.  One launch, no host synchronisation; constants of the backward.
+    `want_hit`: a fourth result, hit [N] int32 = 1 iff the box clips the ray, from the same launch of the same kernel in the hit library
+    (include/mcnerf_hit.h: mcnerf_hit_ray_depths); the other three are the same bits."""
     N, dev = rays_d.shape[0], rays_d.device
     box = [float(v) for v in box]
     if len(box) != 6 or tuple(rays_o.shape) != (N, 3) or tuple(rays_d.shape) != (N, 3) or (jitter is not None and jitter.numel() != N):
@@ -777,6 +804,11 @@ def ray_depths(rays_o: Tensor, rays_d: Tensor, box, near: float, far: float, jit
     z_c = torch.empty(N, Sc, dtype=torch.float32, device=dev)
     z_f = torch.empty(N, Sf, dtype=torch.float32, device=dev) if Sf else None
     span = torch.empty(N, 2, dtype=torch.float32, device=dev) if want_span else None
+    if want_hit:
+        hit = torch.empty(N, dtype=torch.int32, device=dev)
+        _hit.call("mcnerf_hit_ray_depths", rays_o, rays_d, N, *box, float(near), float(far), jitter, zgrid_c, Sc, zgrid_f if Sf else None, Sf,
+                  z_c, z_f, span, hit, _stream())
+        return z_c, z_f, span, hit
     _box.call("mcnerf_box_ray_depths", rays_o, rays_d, N, *box, float(near), float(far), jitter, zgrid_c, Sc, zgrid_f if Sf else None, Sf,
               z_c, z_f, span, _stream())
     return z_c, z_f, span
@@ -820,17 +852,24 @@ def _voxel_rows(name: str, zgrid, jitter, z_rows: Tensor, N: int):
 
 
 def voxel_select(grid: VoxelGrid, thresh: float, rays_o: Tensor, rays_d: Tensor, zgrid: Optional[Tensor], jitter: Optional[Tensor],
-                 sigma_default: float, prefill: bool = True, idx: Optional[Tensor] = None, *, z_rows: Optional[Tensor] = None):
+                 sigma_default: float, prefill: bool = True, idx: Optional[Tensor] = None, *, z_rows: Optional[Tensor] = None,
+                 hit: Optional[Tensor] = None):
     """-> idx [N*Sc,2] int32 (first *count rows valid, torch.nonzero order), count [1] int32, out_c [N,Sc,4] | None: the (ray, sample)
     pairs whose cell holds a sigma > thresh, and the (sigma_default, 1, 1, 1) prefill of the coarse pass.  No host synchronisation.
     `idx`: the caller's own list buffer (rows beyond *count are left as they are).
-    `z_rows` [N,Sc]: the depths of every ray (zgrid and jitter None); the bounds library's entry point (include/mcnerf_box.h)."""
+    `z_rows` [N,Sc]: the depths of every ray (zgrid and jitter None); the bounds library's entry point (include/mcnerf_box.h).
+    `hit` [N] int32 (with `z_rows` only): only rays with hit[n] != 0 are listed; the hit library's entry point (include/mcnerf_hit.h)."""
     N = rays_d.shape[0]
+    if hit is not None and z_rows is None:
+        raise _lib.McnerfError("voxel_select: hit is taken together with z_rows only")
     Sc = zgrid.numel() if z_rows is None else _voxel_rows("voxel_select", zgrid, jitter, z_rows, N)
     if idx is not None and idx.numel() < N * Sc * 2:
         raise _lib.McnerfError(f"voxel_select: idx must hold N * Sc = {N * Sc} pairs, got {tuple(idx.shape)}")
     idx, count, rc, ro, out_c = _list_buffers(N, Sc, prefill, idx, rays_d.device)
-    if z_rows is not None:
+    if hit is not None:
+        _hit.call("mcnerf_hit_voxel_select_rows", grid.vox, *grid.geom, float(thresh), rays_o, rays_d, z_rows, N, Sc,
+                  float(sigma_default), rc, ro, idx, count, out_c, _hit_flags("voxel_select", hit, N), _stream())
+    elif z_rows is not None:
         _box.call("mcnerf_box_voxel_select_rows", grid.vox, *grid.geom, float(thresh), rays_o, rays_d, z_rows, N, Sc,
                   float(sigma_default), rc, ro, idx, count, out_c, _stream())
     else:
