@@ -1,5 +1,5 @@
 """ctypes binding of libmcnerf.so, DERIVED from include/mcnerf.h, the one statement of the C ABI, and the `Binding` class that the
-libraries beside it (`_ext`, `_reg`, `_geo`, `_box`, `_hit`) are bound with as well.
+libraries beside it (`_ext`, `_reg`, `_geo`, `_box`, `_hit`, `_fit`) are bound with as well.
 
 The header is parsed once at import (`parse_header`): every prototype gives an entry point's ctypes signature (`SIGNATURES`), its
 parameter names and, per pointer, the dtype a tensor handed to it must have (`PARAMS`); every decimal `#define MCNERF_*` gives a

@@ -1,4 +1,4 @@
-"""Builds mc_nerf_amd/libmcnerf.so and, beside it, the libraries of the opt-in features (LIBRARIES below; hipcc, gfx950 only) in-tree.
+"""Builds mc_nerf_amd/libmcnerf.so and, beside it, the libraries of the opt-in features (LIBRARIES and EXTRA_LIBRARIES below; hipcc, gfx950 only) in-tree.
 
     python -m mc_nerf_amd.build [--force]
 
@@ -45,8 +45,18 @@ LIBRARIES = {
          ["mcnerf_api.h", "mcnerf_common.h", "mcnerf_kernels.h", "mcnerf_wave.h", "mcnerf_composite.h", "mcnerf_16.h", "mcnerf_x3.h", "mcnerf_launch.h", "mcnerf_voxel.h",
           "mcnerf_sample_pdf.h", "mcnerf_multicam.h", "mcnerf_colorcal.h", "mcnerf_errmap.h", "mcnerf_maxkey.h", "mcnerf_compact.h", "mcnerf_hash.h", "mcnerf_rays.h", "mcnerf_lens.h", "mcnerf_optim_rows.h", os.path.join(_INC, "mcnerf.h")]),
 }
-# OUT, SOURCES, HEADERS of the core library and EXT_OUT, EXT_SOURCES, EXT_HEADERS, REG_*, GEO_*, BOX_*, HIT_* of the others
-for _prefix, (_so, _sources, _headers) in LIBRARIES.items():
+# The libraries added since that table's length was pinned, in the same shape and in build order: build() makes them ahead of LIBRARIES,
+# so the core library is still the last one built.  A library from now on is one more entry HERE.
+EXTRA_LIBRARIES = {
+    # the scene box fitted to the voxel sigma cache (include/mcnerf_fit.h).  scene_fit.hip includes ray_bounds.hip, and with it
+    # select.hip and voxel.hip (listed with the headers: a change of one recompiles scene_fit.hip)
+    "FIT_": ("libmcnfit.so", ["fit_api.hip", "scene_fit.hip"],
+             ["mcnerf_api.h", "mcnerf_common.h", "mcnerf_kernels.h", "mcnerf_wave.h", "mcnerf_voxel.h", "voxel.hip", "select.hip", "ray_bounds.hip", "mcnerf_compact.h",
+              "mcnerf_maxkey.h", "mcnerf_hash.h", "mcnerf_sample_pdf.h", "mcnerf_multicam.h", "mcnerf_ray_bounds.h", "mcnerf_scene_fit.h", os.path.join(_INC, "mcnerf.h"),
+              os.path.join(_INC, "mcnerf_fit.h")]),
+}
+# OUT, SOURCES, HEADERS of the core library and EXT_OUT, EXT_SOURCES, EXT_HEADERS, REG_*, GEO_*, BOX_*, HIT_*, FIT_* of the others
+for _prefix, (_so, _sources, _headers) in {**EXTRA_LIBRARIES, **LIBRARIES}.items():
     globals().update({_prefix + "OUT": os.path.join(HERE, _so), _prefix + "SOURCES": _sources, _prefix + "HEADERS": _headers})
 # the f16x3 chains: a layer body is ~400 MFMAs with its epilogue slices, fully unrolled (beyond hipcc's default pragma-unroll budget);
 # their 256-wide instantiations run one wave per SIMD with 512 registers, where hipcc would otherwise put the MFMA
@@ -63,8 +73,8 @@ def _newer(a, b):
 
 
 def build(force=False, verbose=True):
-    """Every library of LIBRARIES, in its order; returns the core library's path."""
-    for so, sources, headers in LIBRARIES.values():
+    """Every library of EXTRA_LIBRARIES and then of LIBRARIES, in their order; returns the core library's path."""
+    for so, sources, headers in [*EXTRA_LIBRARIES.values(), *LIBRARIES.values()]:
         out = _build_library(sources, headers, os.path.join(HERE, so), force, verbose)
     return out
 

@@ -1,4 +1,4 @@
-// The preamble of a library's C ABI file (api.hip, ext_api.hip, reg_api.hip, geo_api.hip, box_api.hip, hit_api.hip): the error buffer behind
+// The preamble of a library's C ABI file (api.hip, ext_api.hip, reg_api.hip, geo_api.hip, box_api.hip, hit_api.hip, fit_api.hip): the error buffer behind
 // <prefix>_last_error, the two status-returning reporters and the argument checks that more than one library makes.  Included by
 // exactly ONE translation unit per library; everything here has internal linkage, so each .so keeps a thread-local buffer of its own
 // and exports nothing but its header's names.  Host code only: no kernel source includes it, and it is no part of the MLP source digest.

@@ -16,7 +16,7 @@
 //     stands (the library links none of the core library's objects, voxel.o included).  The scan between a list's count and its write
 //     comes the same way, with select.hip.
 // The hit library (ray_skip.hip) compiles this file into itself in turn: box_ray_span returns the flag it forms, and ray_depths_kernel
-// writes it where McnRayDepthsArgs::hit is given.
+// writes it where McnRayDepthsArgs::hit is given.  The fit library (scene_fit.hip) compiles it in as well, for ray_depths_ray.
 #include "mcnerf_ray_bounds.h"
 #include "mcnerf_sample_pdf.h"
 #include "select.hip"
@@ -47,7 +47,9 @@ __device__ __forceinline__ bool box_ray_span(const McnRayDepthsArgs& a, const fl
     return clipped;
 }
 
-__global__ __launch_bounds__(256) void ray_depths_kernel(McnRayDepthsArgs a) {
+// the wave's ray: its rows, span and flag.  The whole body of ray_depths_kernel, and of the fit library's kernel (scene_fit.hip), which
+// first loads the box from the device into its copy of the arguments
+__device__ __forceinline__ void ray_depths_ray(const McnRayDepthsArgs& a) {
     const int lane = threadIdx.x & 63;
     const int n = blockIdx.x * 4 + (threadIdx.x >> 6);
     if (n >= a.N) return;
@@ -72,6 +74,7 @@ __global__ __launch_bounds__(256) void ray_depths_kernel(McnRayDepthsArgs a) {
     if (a.span && lane == 0) { a.span[(size_t)n * 2] = lo; a.span[(size_t)n * 2 + 1] = hi; }
     if (a.hit && lane == 0) a.hit[n] = clipped ? 1 : 0;
 }
+__global__ __launch_bounds__(256) void ray_depths_kernel(McnRayDepthsArgs a) { ray_depths_ray(a); }
 hipError_t mcn_launch_ray_depths(const McnRayDepthsArgs& a, hipStream_t st) {
     if (a.N <= 0) return hipSuccess;
     hipLaunchKernelGGL(ray_depths_kernel, dim3((a.N + 3) / 4), dim3(256), 0, st, a);

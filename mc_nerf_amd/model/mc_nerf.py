@@ -142,6 +142,19 @@ class NeRF_Model(nn.Module):
             self.settings.ray_bounds_miss = sys_param.get("ray_bounds_miss", "sample")
             if self.settings.ray_bounds_miss not in ("sample", "skip"):
                 raise ValueError(f"ray_bounds_miss must be 'sample' or 'skip', got {self.settings.ray_bounds_miss!r}")
+            # "ray_bounds_fit" and its two integers are this build's own keys too, read in "aabb" mode only: "fixed" (the box
+            # is the one above; the default and today's path: the fit library is not even loaded) or "voxel" (the box is fitted on the
+            # device to the occupied cells of the voxel sigma cache and refitted as training empties cells; the box above is the OUTER box)
+            self.settings.ray_bounds_fit = sys_param.get("ray_bounds_fit", "fixed")
+            if self.settings.ray_bounds_fit not in ("fixed", "voxel"):
+                raise ValueError(f"ray_bounds_fit must be 'fixed' or 'voxel', got {self.settings.ray_bounds_fit!r}")
+            if self.settings.ray_bounds_fit == "voxel" and self.coarse_sampler != "voxel":
+                raise ValueError(f"ray_bounds_fit = 'voxel' needs coarse_sampler = 'voxel' (the box is fitted to its sigma grid), got {self.coarse_sampler!r}")
+            self.settings.ray_bounds_fit_margin = _int_key(sys_param, "ray_bounds_fit_margin", 2, 0)
+            self.settings.ray_bounds_fit_every = _int_key(sys_param, "ray_bounds_fit_every", 16, 1)
+        self._scene = None                # fit mode: (scene_cells [8] int32, scene_box [6] fp32) on the device, allocated on first use: not parameters, not buffers
+        self._fit_calls = 0               # fit mode: train calls past the warm-up so far (a host counter: every ray_bounds_fit_every-th refits)
+        self.last_scene_box = None        # fit mode: the box tensor in force at the last render
         self.last_ray_span = None         # "aabb" mode: (lo, hi) [N,2] of the last render's rays; (near, far) on a ray the box does not clip
         self.last_ray_hit = None          # "skip" mode: [N] int32 of the last render's rays, 1 iff the box clips the ray
         self.last_coarse_selection = None  # (idx_c, count_c) of the last listed coarse pass (pruned, or "skip" mode); else None
@@ -159,6 +172,8 @@ class NeRF_Model(nn.Module):
             logging.info("Loading weights:{}".format(self.nerf_ckpt_name))
             if self.coarse_sampler == "voxel":          # the grid is not in the checkpoint: built from the loaded coarse net
                 self.rebuild_voxels()
+                if self.settings.fit_box:               # ... and the box from the grid, once: render calls never refit
+                    self.refit_scene_box()
 
     # ------------------------------------------------------------------ voxel sigma cache (:859-867)
     def _voxel_settings(self, sys_param):
@@ -204,6 +219,38 @@ class NeRF_Model(nn.Module):
         if self._voxels is None:
             self._voxels = ops.VoxelGrid(self.grid_nerf, self.boader_min, self.boader_max, self.sigma_init, self.z_vals_c.device)
         return self._voxels
+
+    # ------------------------------------------------------------------ the scene box fitted to the cache
+    def scene_buffers(self):
+        """(scene_cells [8] int32, scene_box [6] fp32) of `ray_bounds_fit` = "voxel" mode, in ops.voxel_box's order, on the grid's device
+        (allocated on first use; each rank has its own).  Until the first fit the box is the outer box, `settings.box`, and the cells say
+        "nothing fitted" (status 0)."""
+        if not self.settings.fit_box:
+            raise ops._lib.McnerfError("the fitted scene box exists in ray_bounds_fit = 'voxel' mode only")
+        if self._scene is None:
+            dev, G = self.z_vals_c.device, self.grid_nerf
+            self._scene = (torch.tensor([G, G, G, -1, -1, -1, 0, 0], dtype=torch.int32, device=dev),
+                           torch.tensor(self.settings.box, dtype=torch.float32, device=dev))
+        return self._scene
+
+    @property
+    def scene_box(self) -> Optional[torch.Tensor]:
+        return self.scene_buffers()[1] if self.settings.fit_box else None
+
+    @property
+    def scene_cells(self) -> Optional[torch.Tensor]:
+        return self.scene_buffers()[0] if self.settings.fit_box else None
+
+    def refit_scene_box(self) -> torch.Tensor:
+        """Fits the box to the grid as it is now (ops.voxel_box, in place: the tensor every later render reads) -> scene_box.  No host
+        synchronisation.  Train calls do this by themselves every `ray_bounds_fit_every` calls past the warm-up; render calls never do."""
+        st, (cells, box) = self.settings, self.scene_buffers()
+        return ops.voxel_box(self.voxel_grid(), st.voxel_thresh, st.ray_bounds_fit_margin, st.box, cells, box)[1]
+
+    def scene_box_status(self) -> int:
+        """0: no cell was occupied at the last fit (or nothing has been fitted), the box is the outer box; 1: the box is a fitted one;
+        2: the fit lay outside the outer box, the box is the outer box.  Reads the device: the one call of the feature that synchronises."""
+        return int(self.scene_cells[6].item())
 
     @property
     def sigma_voxels(self) -> Optional[torch.Tensor]:
@@ -299,6 +346,10 @@ class NeRF_Model(nn.Module):
             raise ops._lib.McnerfError(f"depth_weight = {self.depth_weight}: the expected depth is a HIP kernel, got rays on {dev} (no CPU fallback)")
         if self.settings.aabb and not rays_d.is_cuda:
             raise ops._lib.McnerfError(f"ray_bounds = 'aabb': the per-ray depths are a HIP kernel, got rays on {dev} (no CPU fallback)")
+        if self.settings.fit_box and cur_epoch >= self.settings.voxel_warmup_epoch:
+            if self._fit_calls % self.settings.ray_bounds_fit_every == 0:
+                self.refit_scene_box()
+            self._fit_calls += 1
         if N == 0:                                  # empty batch: empty results (the reference's tensor ops do the same)
             self.last_expected_depth = (rays_d.new_zeros(0), None if only_coarse else rays_d.new_zeros(0)) if want_zexp else None
             e3, e1 = rays_d.new_zeros(0, 3), rays_d.new_zeros(0, 1)
@@ -337,6 +388,8 @@ class NeRF_Model(nn.Module):
         dev, st, pool = self.z_vals_c.device, self.settings, _pool(self)
         if st.voxel:
             self.voxel_grid()                       # (the list itself has the dense pass's capacity: the pool's keys do not change)
+        if st.fit_box:
+            self.scene_buffers()
         for net, rows in ((self.nerf_coarse.net, n_rays * st.samples_c), (self.nerf_fine.net, st.fine_rows(n_rays, train=True))):
             save = pool.take_save(net, rows, dev, st.precision)
             pool.give_grad(net, save, st.precision, pool.take_grad(net, save, st.precision))

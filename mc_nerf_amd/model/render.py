@@ -18,6 +18,8 @@ What a sampler setting changes in its pass:
       current from their evaluated samples (ops.voxel_update) and run dense in the warm-up; rendering only queries.
   ray_bounds_miss "skip" ("aabb" mode): every pass is a listed one, its list built behind the per-ray hit flag (ops.list_rays, or
       `hit=` of ops.select_fine / ops.voxel_select): no sample of a ray that misses the box reaches a net, its rows stay the prefill.
+  ray_bounds_fit "voxel" ("aabb" mode): the box of `bounds_rows` is the owner's device tensor, fitted to the sigma grid (ops.voxel_box);
+      downstream of the rows and flags nothing changes.
   ray_bounds "aabb": both passes take per-ray rows (`bounds_rows`: ops.ray_depths on the scene box; the rows hold the jitter) where
       they took the shared grid plus jitter: the voxel list and update, the pdf sampler and the threshold fine pass, which is then a
       listed pass on rows [N,Sf].  The rows are constants of the backward.
@@ -68,6 +70,13 @@ class RenderSettings:
     # the hit library is not loaded); "skip": neither net evaluates a sample of it -- both passes are listed passes over the prefill, their
     # lists built behind the per-ray hit flag of ops.ray_depths
     ray_bounds_miss: str = "sample"
+    # read in "aabb" mode only.  "fixed": the box is `box` (today's launches and bits; the fit library is not loaded);
+    # "voxel" (needs coarse_sampler "voxel"): the box is fitted on the device to the cells of the sigma grid above voxel_thresh, padded by
+    # ray_bounds_fit_margin cells and clamped to `box`, the OUTER box, which is also the box in force until the first fit; train calls
+    # past the warm-up refit it every ray_bounds_fit_every calls (ops.voxel_box; NeRF_Model.refit_scene_box)
+    ray_bounds_fit: str = "fixed"
+    ray_bounds_fit_margin: int = 2
+    ray_bounds_fit_every: int = 16
     # depth mode: each pass's expected depth on the rgb composite's own weights is one more differentiable output of
     # the train render.  The switch rides here, not on RenderCall (its field list is pinned); NeRF_Model sets it from "depth_weight"
     want_zexp: bool = False
@@ -79,6 +88,10 @@ class RenderSettings:
     @property
     def skip_misses(self) -> bool:
         return self.aabb and self.ray_bounds_miss == "skip"
+
+    @property
+    def fit_box(self) -> bool:
+        return self.aabb and self.ray_bounds_fit == "voxel"
 
     @property
     def samples_f(self):
@@ -305,13 +318,16 @@ def bounds_rows(owner, rays: Rays, jitter):
     """(z_c [N,Sc], z_f [N,Sf] | None, hit [N] int32 | None) of a render in "aabb" mode -- the model's own grids mapped onto every ray's
     part of [near, far] inside the box, jitter included (ops.ray_depths; z_f in "threshold" mode only: the pdf sampler draws its own
     fine depths), and with `ray_bounds_miss` = "skip" the flag of the rays the box clips, from the same launch -- and None in "global"
-    mode, where nothing is allocated.  The (lo, hi) of every ray stays with the owner in `last_ray_span`, the flags in `last_ray_hit`."""
+    mode, where nothing is allocated.  The (lo, hi) of every ray stays with the owner in `last_ray_span`, the flags in `last_ray_hit`.
+    This is the one place that hands the box to the kernel: `settings.box`, or with `ray_bounds_fit` = "voxel" the owner's fitted box, a
+    device tensor that the kernel reads itself (it stays with the owner in `last_scene_box`)."""
     st: RenderSettings = owner.settings
     if not st.aabb:
         return None
     if not rays.d.is_cuda:
         raise ops._lib.McnerfError(f"ray_bounds = 'aabb': the per-ray depths are a HIP kernel, got rays on {rays.d.device} (no CPU fallback)")
-    z_c, z_f, owner.last_ray_span, *hit = ops.ray_depths(rays.o, rays.d, st.box, float(owner.near), float(owner.far), jitter, owner.z_vals_c,
+    box = owner.last_scene_box = owner.scene_box if st.fit_box else None
+    z_c, z_f, owner.last_ray_span, *hit = ops.ray_depths(rays.o, rays.d, st.box if box is None else box, float(owner.near), float(owner.far), jitter, owner.z_vals_c,
                                                          None if st.pdf else owner.z_vals_f, want_hit=st.skip_misses)
     owner.last_ray_hit = hit[0] if hit else None
     return z_c, z_f, owner.last_ray_hit

@@ -12,7 +12,7 @@ from typing import Optional, Tuple
 
 import torch
 
-from . import _box, _ext, _geo, _hit, _lib, _reg
+from . import _box, _ext, _fit, _geo, _hit, _lib, _reg
 
 Tensor = torch.Tensor
 
@@ -795,15 +795,23 @@ def ray_depths(rays_o: Tensor, rays_d: Tensor, box, near: float, far: float, jit
     zmin, xmax, ymax, zmax), jitter [N] | None, the grids zgrid_c [Sc] and zgrid_f [Sf] | None -> z_c [N,Sc], z_f [N,Sf] | None,
     span [N,2] = (lo, hi) | None.  One launch, no host synchronisation; constants of the backward.
     `want_hit`: a fourth result, hit [N] int32 = 1 iff the box clips the ray, from the same launch of the same kernel in the hit library
-    (include/mcnerf_hit.h: mcnerf_hit_ray_depths); the other three are the same bits."""
+    (include/mcnerf_hit.h: mcnerf_hit_ray_depths); the other three are the same bits.
+    `box` a Tensor [6] fp32 on the device (ops.voxel_box's): the fit library's entry point (include/mcnerf_fit.h: mcnerf_fit_ray_depths)
+    reads the six values on the device -- the same bits again, and no value of the box reaches the host."""
     N, dev = rays_d.shape[0], rays_d.device
-    box = [float(v) for v in box]
-    if len(box) != 6 or tuple(rays_o.shape) != (N, 3) or tuple(rays_d.shape) != (N, 3) or (jitter is not None and jitter.numel() != N):
+    on_device = isinstance(box, Tensor)
+    box = box if on_device else [float(v) for v in box]
+    if (box.numel() if on_device else len(box)) != 6 or tuple(rays_o.shape) != (N, 3) or tuple(rays_d.shape) != (N, 3) or (jitter is not None and jitter.numel() != N):
         raise _lib.McnerfError(f"ray_depths: rays_o / rays_d [N,3] {tuple(rays_o.shape)} / {tuple(rays_d.shape)}, a box of six numbers, jitter [N]")
     Sc, Sf = zgrid_c.numel(), 0 if zgrid_f is None else zgrid_f.numel()
     z_c = torch.empty(N, Sc, dtype=torch.float32, device=dev)
     z_f = torch.empty(N, Sf, dtype=torch.float32, device=dev) if Sf else None
     span = torch.empty(N, 2, dtype=torch.float32, device=dev) if want_span else None
+    if on_device:
+        hit = torch.empty(N, dtype=torch.int32, device=dev) if want_hit else None
+        _fit.call("mcnerf_fit_ray_depths", rays_o, rays_d, N, box, float(near), float(far), jitter, zgrid_c, Sc, zgrid_f if Sf else None, Sf,
+                  z_c, z_f, span, hit, _stream())
+        return (z_c, z_f, span, hit) if want_hit else (z_c, z_f, span)
     if want_hit:
         hit = torch.empty(N, dtype=torch.int32, device=dev)
         _hit.call("mcnerf_hit_ray_depths", rays_o, rays_d, N, *box, float(near), float(far), jitter, zgrid_c, Sc, zgrid_f if Sf else None, Sf,
@@ -824,6 +832,11 @@ def voxel_scale(G: int, bmin: float, bmax: float) -> float:
     return float(_f32(G) / _f32(float(bmax) - float(bmin)))
 
 
+def voxel_cell_edge(G: int, bmin: float, bmax: float) -> float:
+    """The edge of a cell, h = float32(bmax - bmin) / float32(G): one fp32 division on the host (the fit's rule: include/mcnerf_fit.h)."""
+    return float(_f32(float(bmax) - float(bmin)) / _f32(G))
+
+
 def voxel_blend(beta: float) -> Tuple[float, float]:
     """(beta, 1 - beta) as the fp32 values the update kernels take (1 - beta is formed here, in fp32)."""
     b = _f32(beta)
@@ -837,6 +850,7 @@ class VoxelGrid:
     def __init__(self, G: int, bmin: float, bmax: float, sigma_init: float, device):
         self.G, self.bmin, self.bmax = int(G), float(_f32(bmin)), float(bmax)
         self.s = voxel_scale(G, bmin, bmax)
+        self.h = voxel_cell_edge(G, bmin, bmax)
         self.vox = torch.full((self.G,) * 3, float(sigma_init), dtype=torch.float32, device=device)
         self.scratch = torch.zeros((self.G,) * 3, dtype=torch.int32, device=device)
 
@@ -893,6 +907,23 @@ def voxel_update(grid: VoxelGrid, beta: float, rays_o: Tensor, rays_d: Tensor, z
     else:
         _lib.call("mcnerf_voxel_update", grid.vox, grid.scratch, *grid.geom, *voxel_blend(beta), rays_o, rays_d,
                   zgrid, jitter, N, Sc, idx, count, int(max_rows), sig_rgb, _stream())
+
+
+def voxel_box(grid: VoxelGrid, thresh: float, margin: int, outer, cells: Optional[Tensor] = None, box: Optional[Tensor] = None):
+    """-> cells [8] int32, box [6] fp32, both on the device (the caller's own when given): the range of the cells with vox > thresh, padded by
+    `margin` cells, as a box clamped to `outer` = (xmin, ymin, zmin, xmax, ymax, zmax); the outer box itself when no cell is occupied
+    (cells[6] = 0) or the clamp leaves nothing (cells[6] = 2).  The rule: include/mcnerf_fit.h (mcnerf_fit_voxel_box).  One pass over the
+    grid, no host synchronisation."""
+    outer = [float(v) for v in outer]
+    if len(outer) != 6 or isinstance(margin, bool) or not isinstance(margin, int):
+        raise _lib.McnerfError(f"voxel_box: an outer box of six numbers and an integer margin, got {outer!r} and {margin!r}")
+    dev = grid.vox.device
+    cells = torch.empty(8, dtype=torch.int32, device=dev) if cells is None else cells
+    box = torch.empty(6, dtype=torch.float32, device=dev) if box is None else box
+    if cells.numel() != 8 or box.numel() != 6 or grid.vox.numel() != grid.G ** 3:
+        raise _lib.McnerfError(f"voxel_box: vox [G,G,G], cells [8] and box [6], got {tuple(grid.vox.shape)}, {tuple(cells.shape)} and {tuple(box.shape)}")
+    _fit.call("mcnerf_fit_voxel_box", grid.vox, grid.G, grid.bmin, grid.h, float(thresh), margin, *outer, cells, box, _stream())
+    return cells, box
 
 
 def voxel_query(grid: VoxelGrid, xyz: Tensor) -> Tensor:
